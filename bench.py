@@ -13,6 +13,13 @@ shared-node sums and the CG dot products), N=8 is configs[3] (64^3 elements).
 Prints ONE JSON line on rank 0.  `value` = 1e-6 * (H1 + L2 global dofs) * RK
 stages executed / wall time of the K timed steps (the reference's FOM0 with the
 whole-step wall time in the denominator; laghos_solver.cpp:727, laghos.cpp:928-935).
+
+A plain run only sets up, warms up, times the K steps and prints the line.  Everything
+else is behind --full: per-region FOMs, per-kernel timing and the roofline, exchange
+statistics, the extra legs, the CPU baseline with its parity check, and the detail
+record (--no-roofline / --no-legs / --no-cpu-baseline narrow a --full run).
+--dump-outputs DIR writes the state the last timed step left (x, v, e; float64) as
+DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -662,6 +669,31 @@ def compact_line(full, detail_path=None):
     return line
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(sim, sz, path):
+    """--dump-outputs: what the last timed step handed its caller (laghos_sim_get_state: positions x, velocities v, specific
+    internal energies e of this rank, in the caller's numbering) as <path>/state_{x,v,e}.npy, with t and dt beside them; all
+    float64.  Above DUMP_LIMIT_BYTES in all, every state array is cut to a fixed, seeded sample of its entries (sorted indices,
+    seed 0), the same for every run with the same arguments."""
+    import numpy as np
+    S = sim.state()
+    h1v = sz["dim"] * sz["N"]
+    assert S.size == 2 * h1v + sz["NE"] * sz["L1D"] ** sz["dim"], (S.size, sz)
+    arrays = {"state_x": S[:h1v], "state_v": S[h1v:2 * h1v], "state_e": S[2 * h1v:]}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES - 4096:
+        keep = (DUMP_LIMIT_BYTES - 4096) / total
+        rng = np.random.default_rng(0)
+        arrays = {k: v[np.sort(rng.choice(v.size, max(1, int(keep * v.size)), replace=False))] for k, v in arrays.items()}
+    arrays["t"] = np.array([sim.t])
+    arrays["dt"] = np.array([sim.dt])
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def write_detail(full, path):
     """the full record (per-kernel tables, legs, FOMs, exchange statistics) as a side file; never on stdout"""
     try:
@@ -681,6 +713,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2",
                     help="single-GPU workload `value` is measured on (default: BASELINE.json configs[1])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: per-region FOMs, per-kernel timing and roofline, exchange statistics, the extra legs, "
+                         "the CPU baseline and parity check, the detail record (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the state the last timed step computed (x, v, e; float64; t, dt) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="skip the extra legs (64^3 Sedov / Taylor-Green, Q5Q4, developed flow, N-rank path)")
@@ -817,11 +854,14 @@ def main():
                    "mesh_order": mesh_order_note(sim),
                    "e_norm": sim.e_norm(), "t": sim.t, "dt": sim.dt},
     }
+    if a.dump_outputs and rank == 0:
+        mark("writing the outputs")
+        dump_outputs(sim, sz, a.dump_outputs)
 
-    # ---- per-region FOMs (reference formulas, laghos_solver.cpp:722-727) and the
+    # ---- (--full) per-region FOMs (reference formulas, laghos_solver.cpp:722-727) and the
     # roofline of the dominant kernel: extra steps AFTER the timed region so the
     # stopwatch synchronisations / event records do not perturb `value`.
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         sim.enable_timers(True)
         sim.reset_timers()
         r0 = sim.rk_steps
@@ -853,7 +893,7 @@ def main():
     sim.close()
 
     # ---- the other single-GPU configs of BASELINE.json (and two views of configs[1]) as short extra legs, not part of `value`
-    if world == 1 and not a.no_legs and not a.no_roofline:
+    if a.full and world == 1 and not a.no_legs and not a.no_roofline:
         legs = {}
         for name in [n for n in a.legs.split(",") if n in LEGS]:
             if name == a.workload:
@@ -871,7 +911,7 @@ def main():
                 legs[name]["ms_per_step_minus_single_rank_path"] = legs[name]["ms_per_step"] - out["ms_per_step"]
         out["legs"] = legs
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         try:
             out["cpu_baseline"], ref = cpu_baseline(min(usable_cpus(), 64))
             if a.workload == "c2":
@@ -888,7 +928,7 @@ def main():
         # the last line of stdout
         flush_c_stdio()
         sys.stdout.flush()
-        line = compact_line(out, write_detail(out, a.detail))
+        line = compact_line(out, write_detail(out, a.detail) if a.full else None)
         text = json.dumps(line, separators=(",", ":"))
         if len(text) > LINE_LIMIT:  # never let an oversized line cost the driver its record again
             for key in ("legs", "comm"):

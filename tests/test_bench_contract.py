@@ -116,7 +116,7 @@ def test_compact_line_of_a_full_record_fits_the_driver():
 
 def test_committed_line_is_what_the_driver_reads():
     """profiles/r6_bench.json is the stdout line of `python bench.py` on an MI355X (tools/gpu_final_r6.sh), byte for byte what
-    the driver's `python bench.py --gpus 1 --steps 20 --warmup 5` prints last: it holds the contract, fits the driver's
+    `python bench.py --gpus 1 --steps 20 --warmup 5` printed last (what `--full` runs today): it holds the contract, fits the driver's
     8 KB, quotes counter traffic of this very build (sha over the kernel sources) and is the compact form of the full
     record written beside it (profiles/r6_bench_detail.json)."""
     with open(os.path.join(ROOT, "profiles", "r6_bench.json")) as f:
@@ -196,3 +196,35 @@ def test_line_survives_an_oversized_record():
     d = json.loads(text)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "roofline", "cpu_baseline", "parity", "config"):
         assert key in d
+
+
+def test_dump_outputs_writes_the_state_and_bounds_its_size(tmp_path, monkeypatch):
+    """--dump-outputs: the state [x | v | e] of the last timed step split into state_x / state_v / state_e, with t and dt,
+    float64; above the limit every array is cut to the same seeded sample, identical from run to run."""
+    import numpy as np
+    bench = _bench()
+
+    class FakeSim:
+        def __init__(self, S):
+            self.S, self.t, self.dt = S, 0.25, 1e-3
+
+        def state(self):
+            return self.S.copy()
+
+    dim, N, NE, L1D = 3, 1000, 64, 3
+    sz = {"dim": dim, "N": N, "NE": NE, "L1D": L1D}
+    S = np.random.default_rng(1).uniform(size=2 * dim * N + NE * L1D ** dim)
+    bench.dump_outputs(FakeSim(S), sz, str(tmp_path / "a"))
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in ("state_x", "state_v", "state_e", "t", "dt")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(np.concatenate([got["state_x"], got["state_v"], got["state_e"]]), S)
+    assert got["t"].tolist() == [0.25] and got["dt"].tolist() == [1e-3]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + S.nbytes // 4)
+    for run in ("b", "c"):
+        bench.dump_outputs(FakeSim(S), sz, str(tmp_path / run))
+    total = 0
+    for k in ("state_x", "state_v", "state_e"):
+        b, c = np.load(str(tmp_path / "b" / (k + ".npy"))), np.load(str(tmp_path / "c" / (k + ".npy")))
+        assert np.array_equal(b, c) and 0 < b.size < got[k].size and np.isin(b, got[k]).all()
+        total += b.nbytes
+    assert total <= S.nbytes // 4

@@ -79,7 +79,7 @@ def test_bench_gpus_n_over_the_cross_process_transport(nproc, pgrid, slab, monke
     if slab == 2:
         monkeypatch.setenv("LGH_COMM2", "0")
     steps, warmup, block = 3, 2, 8
-    d = _torchrun_bench(nproc, ["--transport", "shm", "--block", str(block), "--steps", str(steps), "--warmup", str(warmup)])
+    d = _torchrun_bench(nproc, ["--full", "--transport", "shm", "--block", str(block), "--steps", str(steps), "--warmup", str(warmup)])
     assert d["n_gpus"] == nproc and d["steps"] == steps and d["warmup"] == warmup and d["scaling"] == "weak"
     assert d["config"]["parallelism"] == "elements%dx%dx%d" % pgrid and d["config"]["zones_per_gpu"] == "%dx%dx%d" % (block, block, block)
     assert d["config"]["elements"] == nproc * block ** 3

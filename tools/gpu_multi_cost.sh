@@ -3,7 +3,7 @@ cd /root/repo
 export TMPDIR=/tmp
 O=gpurun_out/multi; mkdir -p $O
 for m in 0 1 0 1; do
-LGH_FORCE_MULTI=$m timeout 600 python bench.py --steps 20 --warmup 5 --no-legs --no-cpu-baseline > $O/b_$m.json 2> $O/b_$m.err; echo "m=$m rc=$?"
+LGH_FORCE_MULTI=$m timeout 600 python bench.py --full --steps 20 --warmup 5 --no-legs --no-cpu-baseline > $O/b_$m.json 2> $O/b_$m.err; echo "m=$m rc=$?"
 python - <<P
 import json
 d=json.loads([l for l in open("$O/b_$m.json") if l.startswith("{")][-1])
