@@ -13,6 +13,12 @@
  *    [c*N, (c+1)*N)), element-local dofs lexicographic; L2 dofs are e*L1D^dim + l
  *    (SURVEY A2-A4).  S = [x | v | e] with offsets {0, dim*N, 2*dim*N}
  *    (/root/reference/laghos_solver.cpp:166-169).
+ *  - dim = 1 (segments; README run 5) runs the reference's full-assembly path, to which
+ *    1D always switches (laghos.cpp:454-462), through the same entry points: S = [x | v | e]
+ *    with offsets {0, N, 2N}, stressJinvT[e*NQ+q], Jac0inv[e*NQ+q], L2 dofs e*L1D + l.  The
+ *    operators are those of the PA path except the energy solve: zone by zone with the
+ *    factored mass matrices Me(z) (lgh_l2_mass_solve_local), no CG.  One rank only.  Entry
+ *    points that exist for a 2D/3D kernel form (E-vector hooks, lockstep solve) refuse dim 1.
  *  - All work is enqueued on the context's HIP stream; calls are asynchronous
  *    unless they return a scalar to the host (documented per function).
  *  - Return value: 0 = LGH_OK, non-zero = error; lgh_last_error() gives the text.
@@ -42,7 +48,7 @@ typedef struct lgh_ctx lgh_ctx;
  * the MFEM spaces (laghos_assembly.cpp:123-143, :80-96; laghos_solver.hpp:72-89). */
 typedef struct lgh_config
 {
-   int dim, NE;            /* mesh dimension (2|3), local elements */
+   int dim, NE;            /* mesh dimension (1|2|3), local elements */
    int D1D, Q1D, L1D;      /* H1 dofs, quadrature points, L2 dofs per direction */
    int N;                  /* local scalar H1 nodes (H1c.GetVSize()) */
    const int *h1_map;      /* NE*D1D^dim: node of element-local lexicographic dof
@@ -133,6 +139,10 @@ int lgh_mass_mult_full(lgh_ctx *ctx, int space, const double *x, double *y);
  * communicator is attached.  Synchronous; *iters = GetNumIterations(). */
 int lgh_cg_solve(lgh_ctx *ctx, int space, const double *b, double *x, double rel_tol,
                  int max_iter, int *iters);
+/* 1D only (the FA energy solve, laghos_solver.cpp:203-215, :501-515): x = Me(z)^-1 b zone by zone (L2 vectors, device),
+ * with the Cholesky factors of the zone mass matrices formed at lgh_setup_rho0detj0 and again at lgh_mass_data_changed.
+ * Asynchronous.  LGH_ERR_UNSUPPORTED for dim 2/3 (they run the energy CG). */
+int lgh_l2_mass_solve_local(lgh_ctx *ctx, const double *b, double *x);
 
 /* ---- QUpdate::UpdateQuadratureData (laghos_solver.cpp:1354-1411): fused
  * E-restriction + reference-gradient + QKernel; updates stressJinvT and folds the

@@ -60,6 +60,7 @@ SYMBOLS = {
     "lgh_mass_mult": (_I, [_P, _I, _P, _P]),
     "lgh_mass_mult_full": (_I, [_P, _I, _P, _P]),
     "lgh_cg_solve": (_I, [_P, _I, _P, _P, _D, _I, c_int_p]),
+    "lgh_l2_mass_solve_local": (_I, [_P, _P, _P]),
     "lgh_qupdate": (_I, [_P, _P]),
     "lgh_solve_velocity": (_I, [_P, _P, _P, _P, _P, _P, _D, _I, c_int_p]),
     "lgh_solve_energy": (_I, [_P, _P, _P, _P, _P, _P, _D, _I, c_int_p]),

@@ -231,6 +231,10 @@ class Context:
         check(self.lib.lgh_cg_solve(self.h, space, _ptr(b), _ptr(x), rel_tol, max_iter, ctypes.byref(it)))
         return it.value
 
+    def l2_mass_solve_local(self, b, x):
+        """1D: x = Me(z)^-1 b zone by zone (the FA energy solve, lgh_l2_mass_solve_local)."""
+        check(self.lib.lgh_l2_mass_solve_local(self.h, _ptr(b), _ptr(x)))
+
     def qupdate(self, S):
         check(self.lib.lgh_qupdate(self.h, _ptr(S)))
 

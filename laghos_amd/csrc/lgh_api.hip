@@ -329,7 +329,7 @@ static int create_impl(const lgh_config *cfg, lgh_ctx *c, const int kid);
 int lgh_create(const lgh_config *cfg, lgh_ctx **out)
 {
    LGH_CHECK_ARG(cfg && out);
-   LGH_CHECK_ARG(cfg->dim == 2 || cfg->dim == 3);
+   LGH_CHECK_ARG(cfg->dim == 1 || cfg->dim == 2 || cfg->dim == 3);
    LGH_CHECK_ARG(cfg->NE > 0 && cfg->N > 0);
    LGH_CHECK_ARG(cfg->h1_map && cfg->B_h1 && cfg->G_h1 && cfg->B_l2 && cfg->weights && cfg->gamma);
    // MFEM_VERIFY(L1D==D1D-1) (laghos_assembly.cpp:533, :943)
@@ -339,7 +339,7 @@ int lgh_create(const lgh_config *cfg, lgh_ctx **out)
       return LGH_ERR_UNSUPPORTED;
    }
    const int kid = (cfg->dim << 8) | (cfg->D1D << 4) | cfg->Q1D;
-   if (!kernel_id_supported(kid))
+   if (!(cfg->dim == 1 ? kernel_id_supported_1d(kid) : kernel_id_supported(kid)))
    {
       set_error("Unknown kernel 0x%x", kid);
       return LGH_ERR_UNSUPPORTED;
@@ -353,7 +353,8 @@ int lgh_create(const lgh_config *cfg, lgh_ctx **out)
    LGH_HIP_CHECK(hipSetDevice(cfg->device));
    // argument errors a caller can trigger are found before anything is allocated
    LGH_CHECK_ARG(cfg->cfl > 0.0); // (the time-step estimate is a minimum over cfl / inv_dt >= 0, folded as such: lgh_qrows.hpp)
-   for (size_t i = 0, n = (size_t)cfg->NE * (cfg->dim == 2 ? cfg->D1D * cfg->D1D : cfg->D1D * cfg->D1D * cfg->D1D); i < n; i++)
+   const size_t nd = (cfg->dim == 1) ? cfg->D1D : (cfg->dim == 2) ? cfg->D1D * cfg->D1D : cfg->D1D * cfg->D1D * cfg->D1D;
+   for (size_t i = 0, n = (size_t)cfg->NE * nd; i < n; i++)
    {
       if (cfg->h1_map[i] < 0 || cfg->h1_map[i] >= cfg->N) { set_error("h1_map entry out of range"); return LGH_ERR_ARG; }
    }
@@ -365,13 +366,18 @@ int lgh_create(const lgh_config *cfg, lgh_ctx **out)
          if (cfg->ess[k][i] < 0 || cfg->ess[k][i] >= cfg->N) { set_error("essential dof out of range"); return LGH_ERR_ARG; }
       }
    }
+   if (cfg->dim == 1 && cfg->owner)
+   {
+      set_error("a 1D context runs on one rank: several ranks (an owner mask) are not supported in 1D");
+      return LGH_ERR_UNSUPPORTED;
+   }
 
    lgh_ctx *c = new lgh_ctx();
    memset((void *)c, 0, sizeof(lgh_ctx));
    new (&c->timers) Timers();
    c->device = cfg->device;
    // every failure below (HIP errors, out of memory) releases what was built so far
-   const int rc_create = create_impl(cfg, c, kid);
+   const int rc_create = (cfg->dim == 1) ? create_1d(cfg, c) : create_impl(cfg, c, kid);
    if (rc_create != LGH_OK)
    {
       lgh_destroy(c);
@@ -592,7 +598,7 @@ int lgh_destroy(lgh_ctx *c)
                    c->stressJinvT, c->Jac0inv, c->Jac0inv_soa, c->Jac0inv_e, c->rho0DetJ0w, c->massD, c->diagV, c->dinvV,
                    c->dt_est_dev, c->erhs_q, c->v_snap, c->dev_flags, c->ones_l2, c->massS, c->ones_ne, c->force_e_q, c->XE, c->YE, c->cg_r, c->cg_z, c->cg_d0, c->cg_d1, c->cg_y,
                    c->partials, c->tickets, c->cgs, c->scal, c->vcg_s, c->vcg_vec, c->vcg_partials,
-                   c->vcg_tickets};
+                   c->vcg_tickets, c->me_fac};
    for (void *p : ptrs) { if (p) { (void)hipFree(p); } }
    if (c->host_pinned) { (void)hipHostFree(c->host_pinned); }
    if (c->timers.ev[0]) { (void)hipEventDestroy(c->timers.ev[0]); }
@@ -652,6 +658,13 @@ static int stress_on_hand(lgh_ctx *c, const char *who)
    set_error("%s needs stressJinvT, which the last lgh_qupdate kept in registers (lgh_qupdate_store_stress(ctx, 0)): "
              "only F.1 and F^T v of the state's own velocity are on hand; store the stress (..., 1) and update again", who);
    return LGH_ERR_ARG;
+}
+// Entry points with no 1D form (the 2D/3D kernel forms, the lockstep solve, E-vector test hooks) refuse a 1D context.
+static int no_1d(const lgh_ctx *c, const char *who)
+{
+   if (c->dim != 1) { return LGH_OK; }
+   set_error("%s: not available for a 1D context (lgh_1d.hip has its own kernels)", who);
+   return LGH_ERR_UNSUPPORTED;
 }
 int lgh_qupdate_form(lgh_ctx *c, int *form)
 {
@@ -720,6 +733,7 @@ double *lgh_mass_D(lgh_ctx *c)
 int lgh_mass_data_form(lgh_ctx *c, int *form)
 {
    LGH_CHECK_ARG(c && form);
+   if (c->dim == 1) { *form = 0; return LGH_OK; } // (the 1D kernels read the stored table)
    const double *Dq, *Se;
    int dqs;
    int rc = mass_data(c, &Dq, &dqs, &Se);
@@ -732,6 +746,7 @@ int lgh_mass_data_changed(lgh_ctx *c)
    LGH_CHECK_ARG(c);
    c->mass_rank1 = -1;            // the compact form is looked for again at the next mass apply
    c->mass_gen++;
+   if (c->dim == 1) { return mass_changed_1d(c); } // (and the factors of the zone mass matrices of the energy solve)
    return mass_assemble_diag(c);  // operator and Jacobi preconditioner stay consistent (laghos_solver.cpp:266-270)
 }
 double *lgh_mass_diag(lgh_ctx *c) { return c->diagV; }
@@ -773,6 +788,7 @@ int lgh_setup_rho0detj0(lgh_ctx *c, const double *x0, const double *rho0_l2, con
    invalidate_fused(c);
    c->mass_rank1 = -1; // (new mass data)
    c->mass_gen++;
+   if (c->dim == 1) { return setup_1d(c, x0, rho0_l2, rho0_q, volume); } // (with the diagonal and the zone mass factors)
    int rc = setup_rho0detj0(c, x0, rho0_l2, rho0_q, volume);
    if (rc) { return rc; }
    return mass_assemble_diag(c);
@@ -784,6 +800,7 @@ int lgh_force_mult(lgh_ctx *c, const double *x_l2, double *y_h1)
    // L2R->Mult is the identity for the lexicographic L2 space (assembly.cpp:559-560)
    int rc = stress_on_hand(c, "lgh_force_mult"); // (a refusal is taken before the timing sample opens)
    if (rc) { return rc; }
+   if (c->dim == 1) { return force_mult_1d(c, x_l2, y_h1); }
    kt_begin(c, LGH_KERNEL_FORCE_MULT);
    rc = force_mult_E(c, c->stressJinvT, x_l2, c->YE);
    kt_end(c, LGH_KERNEL_FORCE_MULT);
@@ -798,6 +815,7 @@ int lgh_force_mult_transpose(lgh_ctx *c, const double *v_h1, double *y_l2)
    LGH_CHECK_ARG(c && v_h1 && y_l2);
    const int rc0 = stress_on_hand(c, "lgh_force_mult_transpose");
    if (rc0) { return rc0; }
+   if (c->dim == 1) { return force_mult_t_1d(c, v_h1, y_l2); }
    kt_begin(c, LGH_KERNEL_FORCE_MULT_T);
    const int rc = force_mult_t_L(c, c->stressJinvT, v_h1, y_l2);
    kt_end(c, LGH_KERNEL_FORCE_MULT_T);
@@ -819,11 +837,13 @@ int lgh_mass_eliminate_rhs(lgh_ctx *c, double *b)
 int lgh_mass_mult(lgh_ctx *c, int space, const double *x, double *y)
 {
    LGH_CHECK_ARG(c && x && y && (space == LGH_SPACE_H1 || space == LGH_SPACE_L2));
+   if (c->dim == 1) { return mass_apply_1d(c, space, x, y, true); }
    return space == LGH_SPACE_H1 ? mass_apply_h1(c, x, y, true) : mass_apply_l2(c, x, y);
 }
 int lgh_mass_mult_full(lgh_ctx *c, int space, const double *x, double *y)
 {
    LGH_CHECK_ARG(c && x && y && (space == LGH_SPACE_H1 || space == LGH_SPACE_L2));
+   if (c->dim == 1) { return mass_apply_1d(c, space, x, y, false); }
    return space == LGH_SPACE_H1 ? mass_apply_h1(c, x, y, false) : mass_apply_l2(c, x, y);
 }
 
@@ -831,7 +851,19 @@ int lgh_cg_solve(lgh_ctx *c, int space, const double *b, double *x, double rel_t
                  int *iters)
 {
    LGH_CHECK_ARG(c && b && x && (space == LGH_SPACE_H1 || space == LGH_SPACE_L2));
+   if (c->dim == 1) { return cg_1d(c, space, b, x, rel_tol, max_iter, iters, false); }
    return cg_solve(c, space, b, x, rel_tol, max_iter, iters, false);
+}
+
+int lgh_l2_mass_solve_local(lgh_ctx *c, const double *b, double *x)
+{
+   LGH_CHECK_ARG(c && b && x);
+   if (c->dim != 1)
+   {
+      set_error("lgh_l2_mass_solve_local: the zone-local energy solve belongs to the 1D (full-assembly) path; 2D/3D run the energy CG");
+      return LGH_ERR_UNSUPPORTED;
+   }
+   return l2_solve_local_1d(c, b, x);
 }
 
 int lgh_qupdate(lgh_ctx *c, const double *S)
@@ -840,7 +872,7 @@ int lgh_qupdate(lgh_ctx *c, const double *S)
    RoctxRange range("QUpdate-UpdateQuadratureData"); // laghos_solver.cpp:1358
    timer_start(c);
    kt_begin(c, LGH_KERNEL_QUPDATE);
-   int rc = qupdate(c, S);
+   int rc = (c->dim == 1) ? qupdate_1d(c, S) : qupdate(c, S);
    kt_end(c, LGH_KERNEL_QUPDATE);
    timer_stop(c, 3);
    c->timers.c[2] += c->NE;
@@ -890,6 +922,16 @@ int lgh_solve_velocity(lgh_ctx *c, const double *S, double *dS_dt, const double 
    const int dim = c->dim, N = c->N;
    double *dv = dS_dt + c->H1V;
    int rc;
+   if (dim == 1) // the FA branch (laghos_solver.cpp:400-439; lgh_1d.hip)
+   {
+      LGH_CHECK_ARG(!c->accel_src);
+      const double *ones = nullptr;
+      rc = one_vector(c, one_l2, &ones);
+      if (rc) { return rc; }
+      rc = stress_on_hand(c, "lgh_solve_velocity");
+      if (rc) { return rc; }
+      return solve_velocity_1d(c, ones, dv, rhs_h1, rel_tol, max_iter, h1_iters);
+   }
    // One rank, region timers off, no acceleration source: the E->L sum of F.1, the negation,
    // EliminateRHS, dv = 0 and the CG initialisation are one kernel (vcg_init_force_k), with
    // bit-identical results.  With the timers on the reference's regions are kept apart.
@@ -1081,6 +1123,12 @@ int lgh_solve_energy(lgh_ctx *c, const double *S, const double *v_h1, double *dS
    LGH_CHECK_ARG(c && S && v_h1 && dS_dt && e_rhs);
    (void)S;
    double *de = dS_dt + 2 * (size_t)c->H1V;
+   if (c->dim == 1) // the FA branch: zone-local solves with the factors of Me(z), no CG (laghos_solver.cpp:491-516)
+   {
+      const int rc1 = stress_on_hand(c, "lgh_solve_energy");
+      if (rc1) { return rc1; }
+      return solve_energy_1d(c, v_h1, de, e_rhs, e_source, l2_iters);
+   }
    timer_start(c);
    int rc = energy_rhs(c, v_h1, e_rhs); // :473
    timer_stop(c, 2);
@@ -1141,6 +1189,11 @@ int lgh_solve_energy_begin(lgh_ctx *c, const double *S, const double *v_h1, doub
    LGH_CHECK_ARG(c && S && v_h1 && dS_dt && e_rhs);
    c->e_args = {S, v_h1, dS_dt, e_rhs, e_source, rel_tol, max_iter};
    c->e_lockstep = 0;
+   if (c->dim == 1) // (no overlap in 1D: _end runs the zone-local solve, after the velocity solve as in the reference)
+   {
+      c->e_async = 2;
+      return LGH_OK;
+   }
    if (!energy_overlap_ok(c))
    {
       // Several ranks without a second channel (the default over real RCCL): the energy CG runs in LOCKSTEP with the velocity
@@ -1204,7 +1257,7 @@ int lgh_energy_lockstep_stats(lgh_ctx *c, long out[4])
 {
    LGH_CHECK_ARG(c && out);
    out[0] = c->ls_stats[0]; out[1] = c->ls_stats[1]; out[2] = c->ls_stats[2];
-   out[3] = (c->multi != 0 && !comm_second_channel(c) && vcg_available(c) && l2_lockstep_possible(c) && vcg_lockstep_ready(c)) ? 1 : 0;
+   out[3] = (c->dim != 1 && c->multi != 0 && !comm_second_channel(c) && vcg_available(c) && l2_lockstep_possible(c) && vcg_lockstep_ready(c)) ? 1 : 0;
    return LGH_OK;
 }
 int lgh_solve_energy_end(lgh_ctx *c, int *l2_iters)
@@ -1294,6 +1347,11 @@ int lgh_vec_dot(lgh_ctx *c, const double *x, const double *y, long n, double *re
 int lgh_set_velocity_source(lgh_ctx *c, const double *accel_h1)
 {
    LGH_CHECK_ARG(c);
+   if (accel_h1)
+   {
+      const int rc = no_1d(c, "lgh_set_velocity_source"); // (problem 7 has no 1D form)
+      if (rc) { return rc; }
+   }
    c->accel_src = accel_h1;
    return LGH_OK;
 }
@@ -1301,17 +1359,21 @@ int lgh_set_velocity_source(lgh_ctx *c, const double *accel_h1)
 int lgh_tg_source_2d(lgh_ctx *c, const double *S, double *e_source)
 {
    LGH_CHECK_ARG(c && S && e_source);
+   const int rc = no_1d(c, "lgh_tg_source_2d");
+   if (rc) { return rc; }
    return tg_source_2d(c, S, e_source);
 }
 
 int lgh_internal_energy(lgh_ctx *c, const double *e_l2, double *result)
 {
    LGH_CHECK_ARG(c && e_l2 && result);
+   if (c->dim == 1) { return energy_1d(c, 0, e_l2, result); }
    return interp_energy(c, 0, e_l2, result);
 }
 int lgh_kinetic_energy(lgh_ctx *c, const double *v_h1, double *result)
 {
    LGH_CHECK_ARG(c && v_h1 && result);
+   if (c->dim == 1) { return energy_1d(c, 1, v_h1, result); }
    return interp_energy(c, 1, v_h1, result);
 }
 
@@ -1404,12 +1466,13 @@ int lgh_table_symmetry(lgh_ctx *c, int *h1, int *l2)
 int lgh_l2_mass_form(lgh_ctx *c, int *form, int *compact)
 {
    LGH_CHECK_ARG(c && form && compact);
+   if (c->dim == 1) { *form = 0; *compact = 0; return LGH_OK; } // (l2_mass_1d_k: one zone per lane, the stored table)
    return l2_mass_form(c, form, compact);
 }
 int lgh_k1_form(lgh_ctx *c, int *form)
 {
    LGH_CHECK_ARG(c && form);
-   *form = vcg_k1_form(c);
+   *form = (c->dim == 1) ? -1 : vcg_k1_form(c);
    return LGH_OK;
 }
 
@@ -1417,6 +1480,8 @@ int lgh_test_vcg_k1(lgh_ctx *c, const double *r, const double *d_old, const doub
                     double *y_E, double den[3])
 {
    LGH_CHECK_ARG(c && r && (first || d_old) && rz && rz_prev && y_E && den);
+   const int rc = no_1d(c, "lgh_test_vcg_k1");
+   if (rc) { return rc; }
    return vcg_test_k1(c, r, d_old, rz, rz_prev, first, y_E, den);
 }
 int lgh_jac0inv_form(lgh_ctx *c, int *compact)
@@ -1428,32 +1493,44 @@ int lgh_jac0inv_form(lgh_ctx *c, int *compact)
 int lgh_vcg_layout_stats(lgh_ctx *c, long out[4])
 {
    LGH_CHECK_ARG(c && out);
+   const int rc = no_1d(c, "lgh_vcg_layout_stats");
+   if (rc) { return rc; }
    return vcg_layout_stats(c, out);
 }
 int lgh_test_vcg_merged_faces(lgh_ctx *c, unsigned char *mask, long *n_merged)
 {
    LGH_CHECK_ARG(c && mask && n_merged);
+   const int rc = no_1d(c, "lgh_test_vcg_merged_faces");
+   if (rc) { return rc; }
    return vcg_test_merged_faces(c, mask, n_merged);
 }
 int lgh_test_vcg_k2(lgh_ctx *c, int it, const double *y_E, double *r, double *d, double *x, const double den[3], const double rz[3],
                     const double rz_prev[3], const double alpha_prev[3], double rz_out[3], int *deferred_x)
 {
    LGH_CHECK_ARG(c && it >= 1 && y_E && r && d && x && den && rz && rz_prev && alpha_prev && rz_out && deferred_x);
+   const int rc = no_1d(c, "lgh_test_vcg_k2");
+   if (rc) { return rc; }
    return vcg_test_k2(c, it, y_E, r, d, x, den, rz, rz_prev, alpha_prev, rz_out, deferred_x);
 }
 int lgh_force_mult_E(lgh_ctx *c, const double *sJit, const double *x_E, double *y_E)
 {
    LGH_CHECK_ARG(c && sJit && x_E && y_E);
+   const int rc = no_1d(c, "lgh_force_mult_E");
+   if (rc) { return rc; }
    return force_mult_E(c, sJit, x_E, y_E);
 }
 int lgh_force_mult_transpose_E(lgh_ctx *c, const double *sJit, const double *v_E, double *y_E)
 {
    LGH_CHECK_ARG(c && sJit && v_E && y_E);
+   const int rc = no_1d(c, "lgh_force_mult_transpose_E");
+   if (rc) { return rc; }
    return force_mult_t_E(c, sJit, v_E, y_E);
 }
 int lgh_mass_apply_E(lgh_ctx *c, int space, const double *x_E, double *y_E)
 {
    LGH_CHECK_ARG(c && x_E && y_E);
+   const int rc = no_1d(c, "lgh_mass_apply_E");
+   if (rc) { return rc; }
    return mass_apply_E(c, space, x_E, y_E);
 }
 int lgh_test_eig(lgh_ctx *c, int dim, int n, const double *A, double *lambda, double *vec)

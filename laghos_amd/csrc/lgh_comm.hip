@@ -715,6 +715,11 @@ int lgh_comm_unique_id_shm(char id_out[128])
 int lgh_comm_init(lgh_ctx *c, int nranks, int rank, const char unique_id[128])
 {
    LGH_CHECK_ARG(c && nranks >= 1 && rank >= 0 && rank < nranks && unique_id);
+   if (c->dim == 1)
+   {
+      set_error("lgh_comm_init: a 1D context runs on one rank (several ranks are not supported in 1D)");
+      return LGH_ERR_UNSUPPORTED;
+   }
    if (memcmp(unique_id, "LGHSHM", 6) == 0) // cross-process loopback communicator (bench.py --transport shm, tests)
    {
       if (!c->comm) { c->comm = new Comm(); }

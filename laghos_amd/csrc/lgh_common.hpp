@@ -197,6 +197,7 @@ struct lgh_ctx
    int q_trace_n, q_trace_calls;
    void *order;          // lgh::MeshOrder (lgh_order.hip)
    unsigned long mass_gen; // counts changes of the mass data / Jacobi diagonal (the velocity solve keeps copies in its own numbering)
+   double *me_fac;       // 1D: NE * L1D^2, Cholesky factors of the zone mass matrices Me(z) of the energy solve (lgh_1d.hip)
 };
 
 namespace lgh
@@ -556,6 +557,25 @@ bool comm_second_channel(const lgh_ctx *c); // reductions may run on the context
 int exchange_words(lgh_ctx *c, const long long *src, int nwords);
 int comm_word_peers(lgh_ctx *c, int nwords, const long long **peers, int *n_peers); // (allocates the peer buffer on first use)
 int allreduce_dev(lgh_ctx *c, double *dev, int count, int op, bool packed = false); // packed: as halo_sum (sums that travel as one exchange with every peer only)
+
+// ---- lgh_1d.hip: the 1D path (the entry points send a context with dim == 1 there; the 2D/3D kernels never see one)
+bool kernel_id_supported_1d(int kid);
+int create_1d(const lgh_config *cfg, lgh_ctx *c);
+int setup_1d(lgh_ctx *c, const double *x0, const double *rho0_l2, const double *rho0_q, double *volume);
+int mass_changed_1d(lgh_ctx *c); // Jacobi diagonal and zone mass factors from the current mass data
+int force_mult_1d(lgh_ctx *c, const double *x_l2, double *y_h1);
+int force_mult_t_1d(lgh_ctx *c, const double *v_h1, double *y_l2);
+int mass_apply_1d(lgh_ctx *c, int space, const double *x, double *y, bool eliminate);
+int l2_solve_local_1d(lgh_ctx *c, const double *b, double *x);
+int cg_1d(lgh_ctx *c, int space, const double *b, double *x, double rel_tol, int max_iter, int *iters, bool x_is_zero);
+int qupdate_1d(lgh_ctx *c, const double *S);
+int solve_velocity_1d(lgh_ctx *c, const double *ones, double *dv, double *rhs, double rel_tol, int max_iter, int *h1_iters);
+int solve_energy_1d(lgh_ctx *c, const double *v_h1, double *de, double *e_rhs, const double *e_source, int *l2_iters);
+int density_1d(lgh_ctx *c, const double *x_h1, double *rho_l2);
+int energy_1d(lgh_ctx *c, int which, const double *vec, double *result);
+int sedov_density_error_1d(lgh_ctx *c, const double *x_h1, const double *rho_l2, const double par[21], double t,
+                           const double origin[3], int n1d, const double *weights, const double *B_h1, const double *G_h1,
+                           const double *B_l2, double *err2);
 
 // bracket one launch of kernel `id` with an event pair when sampling is on
 inline void kt_begin(lgh_ctx *c, int id)

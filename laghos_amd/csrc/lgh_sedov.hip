@@ -516,6 +516,7 @@ int lgh_sedov_eval(lgh_ctx *c, const double par[21], double t, long n, const dou
 int lgh_compute_density(lgh_ctx *c, const double *x_h1, double *rho_l2)
 {
    LGH_CHECK_ARG(c && x_h1 && rho_l2);
+   if (c->dim == 1) { return density_1d(c, x_h1, rho_l2); } // (lgh_1d.hip)
    const int grid = std::min(c->NE, 2048);
    DevBuf scratch;
    if (scratch.alloc((size_t)grid * c->NL * (c->NL + 1) * sizeof(double))) { set_error("lgh_compute_density: hipMalloc failed"); return LGH_ERR_HIP; }
@@ -525,7 +526,7 @@ int lgh_compute_density(lgh_ctx *c, const double *x_h1, double *rho_l2)
       hipLaunchKernelGGL(density_project_k<3>, dim3(grid), dim3(256), lds, c->stream, c->NE, c->N, c->D1D, c->Q1D, c->L1D,
                          c->h1map, c->B, c->G, c->Bl, c->W, x_h1, c->rho0DetJ0w, (double *)scratch.p, rho_l2);
    }
-   else
+   else if (c->dim == 2)
    {
       hipLaunchKernelGGL(density_project_k<2>, dim3(grid), dim3(256), lds, c->stream, c->NE, c->N, c->D1D, c->Q1D, c->L1D,
                          c->h1map, c->B, c->G, c->Bl, c->W, x_h1, c->rho0DetJ0w, (double *)scratch.p, rho_l2);
@@ -541,6 +542,7 @@ int lgh_sedov_density_error(lgh_ctx *c, const double *x_h1, const double *rho_l2
 {
    LGH_CHECK_ARG(c && x_h1 && rho_l2 && par && origin && weights && B_h1 && G_h1 && B_l2 && err2 && t > 0.0 &&
                  n1d >= 1 && n1d <= 64);
+   if (c->dim == 1) { return sedov_density_error_1d(c, x_h1, rho_l2, par, t, origin, n1d, weights, B_h1, G_h1, B_l2, err2); }
    const int D = c->D1D, L = c->L1D;
    // host tables of the error rule -> device: [w | B_h1 | G_h1 | B_l2]
    std::vector<double> tab;
@@ -565,7 +567,7 @@ int lgh_sedov_density_error(lgh_ctx *c, const double *x_h1, const double *rho_l2
       hipLaunchKernelGGL(sedov_density_error_k<3>, dim3(grid), dim3(256), lds, c->stream, c->NE, c->N, D, L, n1d, c->h1map,
                          dB, dG, dBl, dw, x_h1, rho_l2, s, k, origin[0], origin[1], origin[2], (double *)part.p);
    }
-   else
+   else if (c->dim == 2)
    {
       hipLaunchKernelGGL(sedov_density_error_k<2>, dim3(grid), dim3(256), lds, c->stream, c->NE, c->N, D, L, n1d, c->h1map,
                          dB, dG, dBl, dw, x_h1, rho_l2, s, k, origin[0], origin[1], 0.0, (double *)part.p);

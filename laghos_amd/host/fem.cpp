@@ -147,7 +147,12 @@ CartMesh CartMesh::Named(const std::string &name_in)
    const size_t dot = name.rfind(".mesh");
    if (dot != std::string::npos) { name = name.substr(0, dot); }
    CartMesh m;
-   if (name == "square01_quad")
+   if (name == "segment01") // two segments, boundary attribute 1 at both ends (data/segment01.mesh)
+   {
+      m.dim = 1;
+      m.brk[0] = {0.0, 0.5, 1.0};
+   }
+   else if (name == "square01_quad")
    {
       m.dim = 2;
       m.brk[0] = {0.0, 0.5, 1.0};
@@ -186,7 +191,7 @@ CartMesh CartMesh::Named(const std::string &name_in)
    else
    {
       throw std::runtime_error("mesh '" + name_in + "' is not one of the structured meshes this "
-                               "harness supports (square01_quad, cube01_hex, box01_hex, rectangle01_quad, "
+                               "harness supports (segment01, square01_quad, cube01_hex, box01_hex, rectangle01_quad, "
                                "square_gresho, rt2D)");
    }
    return m;
@@ -258,9 +263,23 @@ Partition::Partition(const CartMesh &mesh, int nranks_, int rank_)
 }
 
 // ---- discretisation ----------------------------------------------------------------------
+// What 1D supports, checked before anything else is built (the reference defines problems 1 and 2 only in 1D - the others
+// read x(1) of a one-component point, laghos.cpp:1101-1117, :1144-1201, :1218 - and this harness runs 1D on one rank).
+static int Dim1DChecked(const CartMesh &mesh, int problem, int nranks)
+{
+   if (mesh.dim != 1) { return mesh.dim; }
+   if (problem != 1 && problem != 2)
+   {
+      throw std::runtime_error("problem " + std::to_string(problem) +
+                               " is not defined in 1D: only problems 1 (Sedov) and 2 (Sod) are");
+   }
+   if (nranks > 1) { throw std::runtime_error("1D runs on one rank: several ranks are not supported in 1D"); }
+   return 1;
+}
+
 Discretization::Discretization(const CartMesh &mesh_, int order_v, int order_e, int problem_,
                                int nranks, int rank, int order_q, double blast)
-   : dim(mesh_.dim), problem(problem_), tab(order_v, order_e, order_q), mesh(mesh_),
+   : dim(Dim1DChecked(mesh_, problem_, nranks)), problem(problem_), tab(order_v, order_e, order_q), mesh(mesh_),
      part(mesh_, nranks, rank), blast_energy(blast)
 {
    const int p = order_v, D = tab.D1D, Q = tab.Q1D, L = tab.L1D;
@@ -325,7 +344,7 @@ Discretization::Discretization(const CartMesh &mesh_, int order_v, int order_e, 
    }
    // neighbours: ranks whose block touches this one (faces, edges, corners)
    int off[3] = {0, 0, 0};
-   const int lo3[3] = {-1, -1, dim == 3 ? -1 : 0}, hi3[3] = {1, 1, dim == 3 ? 1 : 0};
+   const int lo3[3] = {-1, dim >= 2 ? -1 : 0, dim == 3 ? -1 : 0}, hi3[3] = {1, dim >= 2 ? 1 : 0, dim == 3 ? 1 : 0};
    for (off[2] = lo3[2]; off[2] <= hi3[2]; off[2]++)
       for (off[1] = lo3[1]; off[1] <= hi3[1]; off[1]++)
          for (off[0] = lo3[0]; off[0] <= hi3[0]; off[0]++)
@@ -864,6 +883,7 @@ void Discretization::Renumber(const std::string &mode, int levels, unsigned seed
 {
    if (mode.empty() || mode == "none" || mode == "lexicographic") { return; }
    if (!node_perm.empty()) { throw std::runtime_error("Discretization::Renumber: already renumbered"); }
+   if (dim == 1) { throw std::runtime_error("-renumber " + mode + ": renumbering is for 2D/3D meshes"); }
    std::vector<int> np, ep;
    if (mode == "mfem")
    {

@@ -2,9 +2,10 @@
 //
 // Mirrors the command line, time loop and output format of the reference driver
 // (/root/reference/laghos.cpp:119-1092) for the subset this repository supports:
-// PA mode (-pa), dim 2/3, problems 0-7 on the structured meshes of data/,
+// PA mode (-pa), dim 2/3, problems 0-7 on the structured meshes of data/; in 1D (data/segment01.mesh, -dim 1) the FA path,
+// problems 1 and 2, to which -pa switches as in the reference (laghos.cpp:454-462);
 // -s 1, 2, 3, 4 (Euler, RK2, RK3 SSP, RK4) and 7 (RK2Avg).  Everything else the reference driver does
-// (visualisation, VisIt, -fa, AMR, METIS, Umpire, Caliper) is out of scope
+// (visualisation, VisIt, -fa in 2D/3D, AMR, METIS, Umpire, Caliper) is out of scope
 // (SURVEY §2).  Exposed both as the `laghos` executable and as C entry points
 // (laghos_sim_*) that bench.py drives through ctypes.
 #include <algorithm>
@@ -190,12 +191,13 @@ bool WriteFields(const std::string &basename, int ti, const Discretization &d, i
       std::ofstream f(name("mesh").c_str());
       if (!f) { return false; }
       f.precision(8);
-      f << "LGH mesh v1.0\n\n# structured " << (dim == 3 ? "hexahedral" : "quadrilateral")
+      f << "LGH mesh v1.0\n\n# structured " << (dim == 3 ? "hexahedral" : (dim == 2 ? "quadrilateral" : "segment"))
         << " zones; node ids of a zone in lexicographic order of its (order+1)^dim H1 nodes\n\ndimension\n" << dim
         << "\n\nelements\n" << d.NE << "\n";
+      const int geom = (dim == 3) ? 5 : (dim == 2 ? 3 : 1); // MFEM geometry ids: CUBE, SQUARE, SEGMENT
       for (int e = 0; e < d.NE; e++)
       {
-         f << 1 << " " << (dim == 3 ? 5 : 3);
+         f << 1 << " " << geom;
          for (int k = 0; k < d.ND; k++) { f << " " << d.h1map[(size_t)e * d.ND + k]; }
          f << "\n";
       }
@@ -278,11 +280,6 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
          return nullptr;
       }
    }
-   if (!o.p_assembly)
-   {
-      std::fprintf(stderr, "laghos: only the partial-assembly path (-pa) is implemented\n");
-      return nullptr;
-   }
    try
    {
       CartMesh mesh = (o.mesh_file.compare(0, 7, "default") == 0)
@@ -290,6 +287,22 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
                          : CartMesh::Named(o.mesh_file);
       for (int l = 0; l < o.rs_levels + o.rp_levels; l++) { mesh.UniformRefinement(); } // laghos.cpp:391, :483
       o.dim = mesh.dim;
+      if (o.dim == 1 && o.p_assembly) // laghos.cpp:454-462: 1D runs the FA path
+      {
+         o.p_assembly = false;
+         if (rank == 0 && !o.quiet) { std::cout << "Laghos does not support PA in 1D. Switching to FA." << std::endl; }
+      }
+      if (!o.p_assembly && o.dim != 1)
+      {
+         std::fprintf(stderr, "laghos: only the partial-assembly path (-pa) is implemented\n");
+         return nullptr;
+      }
+      const char *force_multi = std::getenv("LGH_FORCE_MULTI");
+      if (o.dim == 1 && force_multi && force_multi[0] == '1')
+      {
+         std::fprintf(stderr, "laghos: LGH_FORCE_MULTI=1 drives the multi-rank path, which 1D does not have\n");
+         return nullptr;
+      }
       s->disc.reset(new Discretization(mesh, o.order_v, o.order_e, o.problem, nranks, rank, o.order_q, o.blast_energy));
       s->disc->impose_visc = o.impose_visc;
       s->disc->Renumber(o.renumber, o.rs_levels + o.rp_levels, (unsigned)o.renumber_seed);

@@ -1,0 +1,121 @@
+"""1D on the host (no GPU): the segment mesh, the Sod and Sedov initial states, the refusals, and the driver's PA -> FA
+switch (reference laghos.cpp:428-462, :499-515, :597-616, :1094-1275; data/segment01.mesh)."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "laghos_amd", "laghos")
+
+
+def disc(rs, ok, ot, problem, E0=1.0, nranks=1):
+    from laghos_amd import host_lib
+    return host_lib.host_disc("segment01", rs, ok, ot, problem, blast_energy=E0, nranks=nranks)
+
+
+@pytest.mark.parametrize("rs,ok,ot", [(0, 1, 0), (1, 2, 1), (3, 3, 2), (2, 5, 4)])
+def test_segment01_discretization(rs, ok, ot):
+    from laghos_amd import host_lib
+    d = disc(rs, ok, ot, 2)
+    NE, D = 2 * 2 ** rs, ok + 1
+    N = NE * ok + 1
+    h1 = d["h1map"].reshape(NE, D)
+    # element e holds nodes e*ok .. e*ok + ok: the nodes in natural x order, vertices shared by neighbours
+    assert np.array_equal(h1, np.arange(NE)[:, None] * ok + np.arange(D)[None, :])
+    assert len(d["S0"]) == 2 * N + NE * (ot + 1)
+    assert list(d["ess"][0]) == [0, N - 1] and len(d["ess"][1]) == 0 and len(d["ess"][2]) == 0
+    tab = host_lib.host_tables(ok, ot)
+    assert np.array_equal(d["W"], tab["qwts"])
+    assert len(d["nbr_rank"]) == 0 and np.all(d["owner"] == 1.0)
+
+
+def test_sod_initial_state():
+    """Problem 2 at rs 5 (README run 5): 64 zones of Q2Q1, x at the Gauss-Lobatto points, v = 0, rho0 = 1 | 0.1,
+    gamma = 1.4, e = p / (rho (gamma - 1)) = 2.5 on both sides."""
+    from laghos_amd import host_lib
+    ok, ot = 2, 1
+    d = disc(5, ok, ot, 2)
+    NE, N, L = 64, 129, ot + 1
+    S = d["S0"]
+    gll = host_lib.host_tables(ok, ot)["gll"]
+    h = 1.0 / NE
+    x_ref = np.concatenate([e * h + h * gll[:-1] for e in range(NE)] + [[1.0]])
+    assert np.allclose(S[:N], x_ref, rtol=0, atol=1e-15)
+    assert np.all(S[N:2 * N] == 0.0)
+    rho = d["rho0_l2"].reshape(NE, L)
+    centres = (np.arange(NE) + 0.5) * h
+    want = np.where(centres < 0.5, 1.0, 0.1)
+    assert np.allclose(rho, want[:, None], rtol=1e-14, atol=0)
+    assert np.all(d["gamma"] == 1.4)
+    assert np.allclose(S[2 * N:], 2.5, rtol=1e-14, atol=0)
+    assert np.allclose(d["rho0_q"].reshape(NE, -1), want[:, None], rtol=0, atol=0)
+
+
+@pytest.mark.parametrize("rs,ok,ot,E0", [(0, 2, 1, 1.0), (3, 3, 2, 0.25), (2, 4, 3, 2.0)])
+def test_sedov_1d_initial_energy(rs, ok, ot, E0):
+    """Problem 1: the delta at the origin carries E0 / 2^dim = E0 / 2 (laghos.cpp:597-606), all of it in zone 0."""
+    from laghos_amd import host_lib
+    d = disc(rs, ok, ot, 1, E0=E0)
+    NE, N, L = 2 * 2 ** rs, 2 * 2 ** rs * ok + 1, ot + 1
+    e = d["S0"][2 * N:].reshape(NE, L)
+    assert np.all(e[1:] == 0.0)
+    assert np.all(d["S0"][N:2 * N] == 0.0) and np.allclose(d["rho0_l2"], 1.0, rtol=1e-14, atol=0)
+    tab = host_lib.host_tables(ok, ot)
+    h0 = d["S0"][ok] - d["S0"][0]
+    integral = h0 * np.sum(tab["qwts"] * (tab["Bl"] @ e[0]))  # rho0 = 1
+    assert abs(integral - E0 / 2) <= 1e-14 * E0
+
+
+def test_1d_refusals(capfd):
+    """Problems 0 and 3-7 are not defined in 1D, and 1D runs on one rank: both refused on the host, before any GPU call."""
+    for p in (0, 3, 4, 5, 6, 7):
+        with pytest.raises(RuntimeError):
+            disc(2, 2, 1, p)
+        assert f"problem {p} is not defined in 1D" in capfd.readouterr().err
+    with pytest.raises(RuntimeError):
+        disc(2, 2, 1, 2, nranks=2)
+    assert "several ranks are not supported in 1D" in capfd.readouterr().err
+
+
+def test_lgh_create_accepts_dim1():
+    """lgh_create takes dim 1 (it used to refuse it as a bad argument); without a GPU it stops at the device check."""
+    import torch
+    if torch.cuda.is_available():
+        return  # (the GPU tests create real 1D contexts)
+    from laghos_amd import _lib
+    L = _lib.load()
+    NE, D, Q = 2, 3, 4
+    h1 = np.array([0, 1, 2, 2, 3, 4], np.int32)
+    ones = np.ones(64)
+    cfg = _lib.LghConfig()
+    cfg.dim, cfg.NE, cfg.D1D, cfg.Q1D, cfg.L1D, cfg.N = 1, NE, D, Q, D - 1, 5
+    ip, dp = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)
+    cfg.h1_map = h1.ctypes.data_as(ip)
+    for f in ("B_h1", "G_h1", "B_l2", "weights", "gamma"):
+        setattr(cfg, f, ones.ctypes.data_as(dp))
+    cfg.cfl = 0.5
+    h = ctypes.c_void_p()
+    assert L.lgh_create(ctypes.byref(cfg), ctypes.byref(h)) != 0
+    err = L.lgh_last_error()
+    assert b"bad argument" not in err and b"HIP" in err, err
+    cfg.Q1D = 5  # no 1D kernel for (D1D, Q1D) = (3, 5)
+    assert L.lgh_create(ctypes.byref(cfg), ctypes.byref(h)) != 0
+    assert b"Unknown kernel 0x135" in L.lgh_last_error()
+
+
+def test_driver_switches_pa_to_fa_in_1d():
+    """-pa (the default) in 1D prints the reference's switch message; -fa stays refused in 2D with the same words."""
+    p = subprocess.run([EXE, "-p", "2", "-m", "data/segment01.mesh", "-rs", "1", "-ms", "1", "-pa"], capture_output=True,
+                       text=True, timeout=300, cwd=ROOT)
+    assert p.stdout.count("Laghos does not support PA in 1D. Switching to FA.") == 1, p.stdout + p.stderr
+    p = subprocess.run([EXE, "-p", "1", "-m", "data/square01_quad.mesh", "-rs", "1", "-ms", "1", "-fa"], capture_output=True,
+                       text=True, timeout=300, cwd=ROOT)
+    assert p.returncode != 0 and "laghos: only the partial-assembly path (-pa) is implemented" in p.stderr
+    p = subprocess.run([EXE, "-p", "2", "-m", "data/segment01.mesh", "-rs", "1", "-ms", "1", "-fa"], capture_output=True,
+                       text=True, timeout=300, cwd=ROOT)
+    assert "only the partial-assembly path" not in p.stderr and "Switching to FA" not in p.stdout
+    p = subprocess.run([EXE, "-p", "3", "-dim", "1", "-nx", "8", "-ms", "1"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode != 0 and "problem 3 is not defined in 1D" in p.stderr
