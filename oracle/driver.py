@@ -2,7 +2,8 @@
 
 Mirrors, in Python over oracle/_build/liblaghos_oracle.so:
   * LagrangianHydroOperator ctor/Mult/GetTimeStepEstimate/ResetTimeStepEstimate
-    (/root/reference/laghos_solver.cpp:104-294, :308-327, :527-540)
+    (/root/reference/laghos_solver.cpp:104-294, :308-327, :527-540): the PA branch for
+    dim >= 2, the full-assembly branch for dim == 1 (laghos_oracle.cpp, "FA branch")
   * RK4Solver (upstream MFEM) and RK2AvgSolver (laghos_solver.cpp:1447-1487)
   * the time loop with adaptive dt control (laghos.cpp:706-778) and the |e|
     report / --checks probe points (laghos.cpp:792-839, :903-919)
@@ -93,7 +94,7 @@ ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_double, ctypes.c_double, ctypes.c_int, 
 
 
 class Hydro:
-    """The oracle's LagrangianHydroOperator (PA branch, dim >= 2)."""
+    """The oracle's LagrangianHydroOperator (PA branch for dim >= 2, FA branch for dim == 1)."""
 
     def __init__(self, prob: Problem, cfl=0.5, cg_tol=1e-8, cg_max_iter=300, comm=None, native=False):
         self.p = prob
@@ -122,7 +123,7 @@ class Hydro:
             int(prob.use_viscosity()), int(prob.use_vorticity()), ctypes.c_double(cfl), prob.order_v))
         if comm is not None:
             self._install_comm(comm)
-        # Rho0DetJ0Vol + h0 (laghos_solver.cpp:223-262)
+        # Rho0DetJ0Vol + h0 (laghos_solver.cpp:223-262; dim 1: the FA set-up :203-221, :231-250 as well)
         x0 = np.ascontiguousarray(S[:prob.H1V])
         vol = L.lgo_setup_rho0detj0(self.h, _dp(x0), _dp(np.ascontiguousarray(rho_l2)),
                                     _dp(np.ascontiguousarray(rho0_q)))
@@ -133,7 +134,7 @@ class Hydro:
         self.volume = vol
         h0 = (vol / ne) ** (1.0 / prob.dim) / prob.order_v
         L.lgo_set_h0(self.h, ctypes.c_double(h0))
-        L.lgo_mass_assemble_diag(self.h)  # OperatorJacobiSmoother (laghos_solver.cpp:266-270)
+        L.lgo_mass_assemble_diag(self.h)  # OperatorJacobiSmoother (laghos_solver.cpp:266-270); dim 1: diag(Mv)
         self.source_type = prob.source_type()
         self._accel = np.ascontiguousarray(prob.accel_source()) if self.source_type == 2 else None
         self.qdata_is_current = False
@@ -258,6 +259,13 @@ class Hydro:
         self.L.lgo_mass_set_ess(self.h, comp)
         self.L.lgo_mass_mult(self.h, space, int(full), _dp(x), _dp(y))
         return y
+
+    def l2_solve_local(self, b):
+        """dim 1: x = Me_inv(e) b zone by zone, the FA energy solve (laghos_solver.cpp:501-515)."""
+        assert self.p.dim == 1
+        x = np.empty(self.p.L2V)
+        self.L.lgo_l2_solve_local(self.h, _dp(np.ascontiguousarray(b, dtype=np.float64)), _dp(x))
+        return x
 
     def cg(self, space, b, x=None, comp=-1, rel_tol=None, max_iter=None):
         x = np.zeros_like(b) if x is None else x

@@ -7,7 +7,7 @@ reference's golden |e| values:
   * 1-D tables: Gauss-Legendre rule on [0,1], Gauss-Lobatto nodes, Lagrange
     (H1) basis + derivative, Bernstein (L2) basis          (SURVEY A1-A3, A5;
     corroborated by /root/reference/amr/laghos_assembly.cpp:32-58)
-  * Cartesian tensor-product meshes equivalent to data/square01_quad.mesh,
+  * Cartesian tensor-product meshes equivalent to data/segment01.mesh, data/square01_quad.mesh,
     data/cube01_hex.mesh, data/box01_hex.mesh, data/rectangle01_quad.mesh after
     `-rs` uniform refinements (laghos.cpp:378-392; the mesh files are all
     axis-aligned structured grids with element axes = global axes)
@@ -85,6 +85,7 @@ def quad_points_1d(order_v, order_e, order_q=-1):
 # ----------------------------------------------------------------------------
 MESHES = {
     # name: per-axis break points of the coarse mesh file
+    "segment01": [[0.0, 0.5, 1.0]],
     "square01_quad": [[0.0, 0.5, 1.0], [0.0, 0.5, 1.0]],
     "cube01_hex": [[0.0, 0.5, 1.0], [0.0, 0.5, 1.0], [0.0, 0.5, 1.0]],
     "box01_hex": [[0.0, 1.0, 3.0, 5.0, 7.0], [0.0, 1.5, 3.0], [0.0, 1.5, 3.0]],
@@ -200,7 +201,11 @@ class Problem:
     def _build_h1map(self):
         dim, p, D = self.dim, self.order_v, self.D1D
         m = np.empty((self.NE, self.ND), dtype=np.int32)
-        if dim == 2:
+        if dim == 1:
+            e = np.arange(self.NE)
+            for dx in range(D):
+                m[:, dx] = e * p + dx
+        elif dim == 2:
             nx, ny = self.ne
             Nx = self.nn[0]
             ex, ey = np.meshgrid(np.arange(nx), np.arange(ny), indexing="xy")
@@ -277,7 +282,9 @@ class Problem:
             lo, hi = b[ei[:, a]], b[ei[:, a] + 1]
             per_axis.append(lo[:, None] + (hi - lo)[:, None] * ref1d[None, :])  # (NE, n)
         pts = np.empty((self.NE, n ** self.dim, self.dim))
-        if self.dim == 2:
+        if self.dim == 1:
+            pts[:, :, 0] = per_axis[0]
+        elif self.dim == 2:
             for j in range(n):
                 for i in range(n):
                     pts[:, i + n * j, 0] = per_axis[0][:, i]

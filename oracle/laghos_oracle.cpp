@@ -901,6 +901,11 @@ struct Ctx
    // timers (laghos_solver.hpp:39-56)
    double t_force, t_cgH1, t_cgL2, t_qdata;
    long H1iter, L2iter, quad_tstep;
+   // dim == 1: the full-assembly branch (see the FA section below)
+   std::vector<int> mv_off, mv_col;    // Mv: CSR by node, columns ascending
+   std::vector<double> mv_val;
+   std::vector<double> Fe;             // ForceIntegrator element matrices, Fe[(e*ND + i)*NL + l]
+   std::vector<double> Me_inv;         // DenseMatrixInverse of Me(e), row-major NL x NL per zone
 };
 
 double now()
@@ -1060,6 +1065,292 @@ double dot_plain(size_t n, const double *a, const double *b)
    return s;
 }
 
+// ---------------------------------------------------------------------------
+// dim == 1: the full-assembly (FA) branch.  The reference takes it for every
+// 1D run (laghos.cpp:454-462 switches -pa to -fa there); restated from:
+//   set-up           laghos_solver.cpp:203-221 (Me(e) by MassIntegrator, LU
+//                    inverse by DenseMatrixInverse; Mv by VectorMassIntegrator),
+//                    :231-262 (Jac0inv, rho0DetJ0w, volume, h0)
+//   quadrature data  laghos_solver.cpp:816-985 (batches of 3 zones)
+//   Force            ForceIntegrator, laghos_assembly.cpp:43-78, assembled
+//   SolveVelocity    laghos_solver.cpp:400-439 (Force 1, Neg, FormLinearSystem,
+//                    Jacobi PCG: lgo_cg with space 0)
+//   SolveEnergy      laghos_solver.cpp:491-516 (Force^T v, Me_inv(e) per zone)
+// Sparse products run row by row with ascending columns, as SparseMatrix::Mult.
+// ---------------------------------------------------------------------------
+
+// x at the quadrature points of zone e (1D: ND = D1D, NQ = Q1D, NL = L1D)
+inline double fa_interp(const std::vector<double> &T, int Q, int q, int n, const double *xe)
+{
+   double s = 0.0;
+   for (int d = 0; d < n; d++) { s += T[q + Q * d] * xe[d]; }
+   return s;
+}
+
+// LU factorisation with partial pivoting, then the inverse column by column
+// (DenseMatrixInverse::Factor + GetInverseMatrix: LUFactors).  A is n x n row-major.
+void lu_inverse(int n, const double *A, double *Ainv)
+{
+   std::vector<double> LU(A, A + n * n);
+   std::vector<int> piv(n);
+   for (int i = 0; i < n; i++)
+   {
+      int p = i;
+      double m = std::fabs(LU[i * n + i]);
+      for (int j = i + 1; j < n; j++)
+         if (std::fabs(LU[j * n + i]) > m) { m = std::fabs(LU[j * n + i]); p = j; }
+      piv[i] = p;
+      if (p != i)
+         for (int k = 0; k < n; k++) { std::swap(LU[i * n + k], LU[p * n + k]); }
+      const double d = 1.0 / LU[i * n + i];
+      for (int j = i + 1; j < n; j++)
+      {
+         LU[j * n + i] *= d;
+         for (int k = i + 1; k < n; k++) { LU[j * n + k] -= LU[j * n + i] * LU[i * n + k]; }
+      }
+   }
+   std::vector<double> col(n);
+   for (int c = 0; c < n; c++)
+   {
+      for (int i = 0; i < n; i++) { col[i] = (i == c) ? 1.0 : 0.0; }
+      for (int i = 0; i < n; i++) { std::swap(col[i], col[piv[i]]); }
+      for (int i = 0; i < n; i++)
+         for (int k = 0; k < i; k++) { col[i] -= LU[i * n + k] * col[k]; }
+      for (int i = n - 1; i >= 0; i--)
+      {
+         for (int k = i + 1; k < n; k++) { col[i] -= LU[i * n + k] * col[k]; }
+         col[i] /= LU[i * n + i];
+      }
+      for (int i = 0; i < n; i++) { Ainv[i * n + c] = col[i]; }
+   }
+}
+
+// laghos_solver.cpp:203-221, :231-250
+double fa_setup(Ctx &c, const double *x0, const double *rho0_l2, const double *rho0_q)
+{
+   const int NE = c.NE, D = c.D1D, Q = c.Q1D, L = c.L1D;
+   std::vector<double> Mv_e((size_t)NE * D * D, 0.0), Me(L * L);
+   c.Me_inv.assign((size_t)NE * L * L, 0.0);
+   double vol = 0.0;
+   for (int e = 0; e < NE; e++)
+   {
+      double xe[16], re[16];
+      for (int d = 0; d < D; d++) { xe[d] = x0[c.h1map[(size_t)e * D + d]]; }
+      for (int l = 0; l < L; l++) { re[l] = rho0_l2[(size_t)e * L + l]; }
+      std::fill(Me.begin(), Me.end(), 0.0);
+      double *mv = Mv_e.data() + (size_t)e * D * D;
+      for (int q = 0; q < Q; q++)
+      {
+         const size_t eq = (size_t)e * Q + q;
+         const double J = fa_interp(c.G, Q, q, D, xe);
+         c.Jac0inv[eq] = 1.0 / J;                                  // DenseMatrixInverse of the 1 x 1 Jacobian
+         const double rho0DetJ0 = J * fa_interp(c.Bl, Q, q, L, re); // Tr.Weight() * rho_vals(q)
+         c.rho0DetJ0w[eq] = rho0DetJ0 * c.W[q];
+         // MassIntegrator / VectorMassIntegrator: w = Tr.Weight() * ip.weight * Q(x)
+         const double w = J * c.W[q] * rho0_q[eq];
+         c.massD[eq] = w;
+         for (int i = 0; i < L; i++)
+            for (int j = 0; j < L; j++) { Me[i * L + j] += w * c.Bl[q + Q * i] * c.Bl[q + Q * j]; }
+         for (int i = 0; i < D; i++)
+            for (int j = 0; j < D; j++) { mv[i * D + j] += w * c.B[q + Q * i] * c.B[q + Q * j]; }
+      }
+      lu_inverse(L, Me.data(), c.Me_inv.data() + (size_t)e * L * L);
+      vol += xe[D - 1] - xe[0];                                    // GetElementVolume
+   }
+   // Mv.Assemble(): element matrices summed in ascending element order into CSR rows
+   const int N = c.N;
+   std::vector<std::vector<std::pair<int, double>>> rows(N);
+   for (int e = 0; e < NE; e++)
+      for (int i = 0; i < D; i++)
+         for (int j = 0; j < D; j++)
+         {
+            const int r = c.h1map[(size_t)e * D + i], col = c.h1map[(size_t)e * D + j];
+            const double v = Mv_e[((size_t)e * D + i) * D + j];
+            auto it = std::find_if(rows[r].begin(), rows[r].end(), [&](const std::pair<int, double> &p) { return p.first == col; });
+            if (it == rows[r].end()) { rows[r].push_back({col, v}); }
+            else { it->second += v; }
+         }
+   c.mv_off.assign((size_t)N + 1, 0);
+   c.mv_col.clear();
+   c.mv_val.clear();
+   for (int r = 0; r < N; r++)
+   {
+      std::sort(rows[r].begin(), rows[r].end(), [](const std::pair<int, double> &a, const std::pair<int, double> &b) { return a.first < b.first; });
+      for (auto &p : rows[r]) { c.mv_col.push_back(p.first); c.mv_val.push_back(p.second); }
+      c.mv_off[(size_t)r + 1] = (int)c.mv_col.size();
+   }
+   return vol;
+}
+
+// Jacobi diagonal: the diagonal of the assembled Mv.  (The FA solve's HypreSmoother
+// reads the diagonal of the eliminated matrix, 1 on the essential rows; the residual
+// is 0 there, so either gives the same iterates.)
+void fa_diag(Ctx &c)
+{
+   for (int r = 0; r < c.N; r++)
+   {
+      c.diagV[r] = 0.0;
+      for (int k = c.mv_off[r]; k < c.mv_off[(size_t)r + 1]; k++)
+         if (c.mv_col[k] == r) { c.diagV[r] = c.mv_val[k]; }
+   }
+}
+
+void fa_mv_mult(const Ctx &c, const double *x, double *y)
+{
+   for (int r = 0; r < c.N; r++)
+   {
+      double s = 0.0;
+      for (int k = c.mv_off[r]; k < c.mv_off[(size_t)r + 1]; k++) { s += c.mv_val[k] * x[c.mv_col[k]]; }
+      y[r] = s;
+   }
+}
+
+// y_e = Me(e) x_e, Me(e) formed again from the mass data (the L2 mass operator of the tests)
+void fa_me_mult(const Ctx &c, const double *x, double *y)
+{
+   const int NE = c.NE, Q = c.Q1D, L = c.L1D;
+   for (int e = 0; e < NE; e++)
+   {
+      for (int i = 0; i < L; i++)
+      {
+         double s = 0.0;
+         for (int j = 0; j < L; j++)
+         {
+            double m = 0.0;
+            for (int q = 0; q < Q; q++) { m += c.massD[(size_t)e * Q + q] * c.Bl[q + Q * i] * c.Bl[q + Q * j]; }
+            s += m * x[(size_t)e * L + j];
+         }
+         y[(size_t)e * L + i] = s;
+      }
+   }
+}
+
+void fa_me_inv_mult(const Ctx &c, const double *b, double *x)
+{
+   const int L = c.L1D;
+   for (int e = 0; e < c.NE; e++)
+   {
+      const double *Mi = c.Me_inv.data() + (size_t)e * L * L;
+      for (int i = 0; i < L; i++)
+      {
+         double s = 0.0;
+         for (int j = 0; j < L; j++) { s += Mi[i * L + j] * b[(size_t)e * L + j]; }
+         x[(size_t)e * L + i] = s;
+      }
+   }
+}
+
+// laghos_solver.cpp:816-985, then the ForceIntegrator element matrices (AssembleForceMatrix)
+void fa_qupdate(Ctx &c, const double *S)
+{
+   const int NE = c.NE, D = c.D1D, Q = c.Q1D, L = c.L1D, N = c.N;
+   const double *x = S, *v = S + N, *en = S + 2 * (size_t)N;
+   const int nbatch = 3;
+   std::vector<double> J((size_t)nbatch * Q), rho(J.size()), E(J.size()), dvq(J.size());
+   for (int z0 = 0; z0 < NE; z0 += nbatch)
+   {
+      const int nz = std::min(nbatch, NE - z0);
+      double min_detJ = std::numeric_limits<double>::infinity();
+      for (int z = 0; z < nz; z++)
+      {
+         const int e = z0 + z;
+         double xe[16], ve[16], ee[16];
+         for (int d = 0; d < D; d++) { xe[d] = x[c.h1map[(size_t)e * D + d]]; ve[d] = v[c.h1map[(size_t)e * D + d]]; }
+         for (int l = 0; l < L; l++) { ee[l] = en[(size_t)e * L + l]; }
+         for (int q = 0; q < Q; q++)
+         {
+            const int i = z * Q + q;
+            J[i] = fa_interp(c.G, Q, q, D, xe);
+            dvq[i] = fa_interp(c.G, Q, q, D, ve);
+            min_detJ = std::fmin(min_detJ, J[i]);
+            rho[i] = c.rho0DetJ0w[(size_t)e * Q + q] / J[i] / c.W[q];
+            E[i] = std::fmax(0.0, fa_interp(c.Bl, Q, q, L, ee));
+         }
+      }
+      for (int z = 0; z < nz; z++)
+      {
+         const int e = z0 + z;
+         const double gamma = c.gamma[e];
+         for (int q = 0; q < Q; q++)
+         {
+            const int i = z * Q + q;
+            const size_t eq = (size_t)e * Q + q;
+            const double detJ = J[i], Jinv = 1.0 / J[i], r = rho[i];
+            const double p = (gamma - 1.0) * r * E[i];                   // ComputeMaterialProperties
+            const double sound_speed = std::sqrt(gamma * (gamma - 1.0) * E[i]);
+            double stress = -p, visc_coeff = 0.0;
+            if (c.visc)
+            {
+               const double sgrad_v = dvq[i] * Jinv;                      // GetVectorGradient; Symmetrize: itself
+               const double eig_val = sgrad_v, eig_vec = 1.0;             // dim == 1
+               const double Jpi = detJ * c.Jac0inv[eq];
+               const double ph_dir = Jpi * eig_vec;
+               const double h = c.h0 * std::fabs(ph_dir) / std::fabs(eig_vec);
+               const double mu = eig_val;
+               visc_coeff = 2.0 * r * h * h * std::fabs(mu);
+               const double eps = 1e-12;
+               visc_coeff += 0.5 * r * h * sound_speed * 1.0 * (1.0 - smooth_step_01(mu - 2.0 * eps, eps));
+               stress += visc_coeff * sgrad_v;
+            }
+            const double h_min = std::fabs(detJ) / (double)c.order_v;     // CalcSingularvalue(0) of 1 x 1
+            const double inv_dt = sound_speed / h_min + 2.5 * visc_coeff / r / h_min / h_min;
+            if (min_detJ < 0.0) { c.dt_est = 0.0; }
+            else if (inv_dt > 0.0) { c.dt_est = std::fmin(c.dt_est, c.cfl * (1.0 / inv_dt)); }
+            double sJ = stress * Jinv;                                    // MultABt(stress, Jinv)
+            sJ *= c.W[q] * detJ;
+            c.stressJinvT[eq] = sJ;
+         }
+      }
+   }
+}
+
+// ForceIntegrator::AssembleElementMatrix2 (laghos_assembly.cpp:43-78), 1D:
+// elmat(i, l) += (stressJinvT * dshape(i)) * shape(l)
+void fa_force_assemble(Ctx &c)
+{
+   const int NE = c.NE, D = c.D1D, Q = c.Q1D, L = c.L1D;
+   c.Fe.assign((size_t)NE * D * L, 0.0);
+   for (int e = 0; e < NE; e++)
+      for (int q = 0; q < Q; q++)
+      {
+         const double sJ = c.stressJinvT[(size_t)e * Q + q];
+         for (int i = 0; i < D; i++)
+         {
+            const double lf = sJ * c.G[q + Q * i];
+            for (int l = 0; l < L; l++) { c.Fe[((size_t)e * D + i) * L + l] += lf * c.Bl[q + Q * l]; }
+         }
+      }
+}
+
+// Force.Mult: row n of the assembled matrix, columns (e, l) ascending
+void fa_force_mult(const Ctx &c, const double *xl, double *y)
+{
+   const int D = c.D1D, L = c.L1D;
+   for (int n = 0; n < c.N; n++)
+   {
+      double s = 0.0;
+      for (int k = c.t_off[n]; k < c.t_off[n + 1]; k++)
+      {
+         const int p = c.t_idx[k], e = p / D, i = p - e * D;
+         for (int l = 0; l < L; l++) { s += c.Fe[((size_t)e * D + i) * L + l] * xl[(size_t)e * L + l]; }
+      }
+      y[n] = s;
+   }
+}
+
+// Force.MultTranspose: column (e, l) takes its rows in ascending node order
+void fa_force_mult_t(const Ctx &c, const double *v, double *y)
+{
+   const int D = c.D1D, L = c.L1D;
+   for (int e = 0; e < c.NE; e++)
+      for (int l = 0; l < L; l++)
+      {
+         double s = 0.0;
+         for (int i = 0; i < D; i++) { s += c.Fe[((size_t)e * D + i) * L + l] * v[c.h1map[(size_t)e * D + i]]; }
+         y[(size_t)e * L + l] = s;
+      }
+}
+
 } // namespace
 
 extern "C"
@@ -1091,9 +1382,9 @@ void *lgo_create(int dim, int NE, int D1D, int Q1D, int L1D, int N, const int *h
 {
    Ctx *c = new Ctx;
    c->dim = dim; c->NE = NE; c->D1D = D1D; c->Q1D = Q1D; c->L1D = L1D; c->N = N;
-   c->ND = dim == 2 ? D1D * D1D : D1D * D1D * D1D;
-   c->NQ = dim == 2 ? Q1D * Q1D : Q1D * Q1D * Q1D;
-   c->NL = dim == 2 ? L1D * L1D : L1D * L1D * L1D;
+   c->ND = dim == 1 ? D1D : dim == 2 ? D1D * D1D : D1D * D1D * D1D;
+   c->NQ = dim == 1 ? Q1D : dim == 2 ? Q1D * Q1D : Q1D * Q1D * Q1D;
+   c->NL = dim == 1 ? L1D : dim == 2 ? L1D * L1D : L1D * L1D * L1D;
    c->H1V = dim * N;
    c->L2V = NE * c->NL;
    c->h1map.assign(h1map, h1map + (size_t)NE * c->ND);
@@ -1189,6 +1480,8 @@ void lgo_qkernel(void *h, const double *q_dx, const double *q_e, const double *q
    if (c->dim == 2) { QKernel<2>(c->NE, c->NQ, c->visc, c->vort, c->h0, (double)c->order_v, c->cfl, inf, c->gamma.data(), c->W.data(), q_dx, c->rho0DetJ0w.data(), q_e, q_dv, c->Jac0inv.data(), q_dt, sJit); }
    else { QKernel<3>(c->NE, c->NQ, c->visc, c->vort, c->h0, (double)c->order_v, c->cfl, inf, c->gamma.data(), c->W.data(), q_dx, c->rho0DetJ0w.data(), q_e, q_dv, c->Jac0inv.data(), q_dt, sJit); }
 }
+// dim == 1: x = Me_inv(e) b zone by zone (the FA energy solve, laghos_solver.cpp:501-515)
+void lgo_l2_solve_local(void *h, const double *b, double *x) { fa_me_inv_mult(*(Ctx *)h, b, x); }
 // small-matrix probes for tests (vs numpy)
 void lgo_eig3(const double *A, double *lam, double *vec) { sm::CalcEigenvalues<3>(A, lam, vec); }
 void lgo_eig2(const double *A, double *lam, double *vec) { sm::CalcEigenvalues<2>(A, lam, vec); }
@@ -1201,6 +1494,7 @@ double lgo_sv2(const double *A, int i) { return sm::CalcSingularvalue<2>(A, i); 
 void lgo_force_mult(void *h, const double *x, double *y)
 {
    Ctx *c = (Ctx *)h;
+   if (c->dim == 1) { fa_force_assemble(*c); fa_force_mult(*c, x, y); return; } // Force.Mult (FA)
    // L2R->Mult is the identity copy for lexicographic L2
    force_mult_E(*c, c->stressJinvT.data(), x, c->YE.data());
    h1_scatter_add(*c, c->dim, c->YE.data(), y);
@@ -1210,6 +1504,7 @@ void lgo_force_mult(void *h, const double *x, double *y)
 void lgo_force_mult_transpose(void *h, const double *v, double *y)
 {
    Ctx *c = (Ctx *)h;
+   if (c->dim == 1) { fa_force_assemble(*c); fa_force_mult_t(*c, v, y); return; } // Force.MultTranspose (FA)
    h1_gather(*c, c->dim, v, c->YE.data());
    force_mult_t_E(*c, c->stressJinvT.data(), c->YE.data(), y);
 }
@@ -1226,6 +1521,17 @@ void lgo_mass_eliminate_rhs(void *h, double *b)
 void lgo_mass_mult(void *h, int space, int full, const double *x, double *y)
 {
    Ctx *c = (Ctx *)h;
+   if (c->dim == 1) // FA: the assembled Mv, and Me(e) zone by zone
+   {
+      if (space == 0)
+      {
+         fa_mv_mult(*c, x, y);
+         if (!full && c->cur_ess >= 0)
+            for (int i : c->ess[c->cur_ess]) { y[i] = 0.0; }
+      }
+      else { fa_me_mult(*c, x, y); }
+      return;
+   }
    if (space == 0)
    {
       h1_gather(*c, 1, x, c->XE.data());
@@ -1241,6 +1547,7 @@ void lgo_mass_mult(void *h, int space, int full, const double *x, double *y)
 void lgo_mass_assemble_diag(void *h)
 {
    Ctx *c = (Ctx *)h;
+   if (c->dim == 1) { fa_diag(*c); return; }
    if (c->dim == 2) { mass_diag_dispatch<2>(c->D1D, c->Q1D, c->NE, c->B.data(), c->massD.data(), c->YE.data()); }
    else { mass_diag_dispatch<3>(c->D1D, c->Q1D, c->NE, c->B.data(), c->massD.data(), c->YE.data()); }
    h1_scatter_add(*c, 1, c->YE.data(), c->diagV.data());
@@ -1254,6 +1561,7 @@ void lgo_mass_assemble_diag(void *h)
 double lgo_setup_rho0detj0(void *h, const double *x0, const double *rho0_l2, const double *rho0_q)
 {
    Ctx *c = (Ctx *)h;
+   if (c->dim == 1) { return fa_setup(*c, x0, rho0_l2, rho0_q); }
    const int dim = c->dim, NQ = c->NQ, NE = c->NE;
    h1_gather(*c, dim, x0, c->e_vec.data());
    if (dim == 2) { interp_dispatch<2>(c->D1D, c->Q1D, NE, dim, c->B.data(), c->G.data(), c->e_vec.data(), nullptr, c->q_dx.data()); }
@@ -1309,6 +1617,13 @@ void lgo_qupdate(void *h, const double *S)
    Ctx *c = (Ctx *)h;
    const double t0 = now();
    const int dim = c->dim, NE = c->NE;
+   if (dim == 1)
+   {
+      fa_qupdate(*c, S);
+      c->t_qdata += now() - t0;
+      c->quad_tstep += NE;
+      return;
+   }
    const double *x = S, *v = S + c->H1V, *e = S + 2 * (size_t)c->H1V;
    h1_gather(*c, dim, x, c->e_vec.data());
    if (dim == 2) { interp_dispatch<2>(c->D1D, c->Q1D, NE, dim, c->B.data(), c->G.data(), c->e_vec.data(), nullptr, c->q_dx.data()); }
@@ -1488,6 +1803,14 @@ void lgo_solve_energy(void *h, const double *v, double *dS, double cg_tol, int c
    c->t_force += now() - t0;
    if (e_source)
       for (int i = 0; i < L2V; i++) { e_rhs[i] += e_source[i]; } // :477
+   if (c->dim == 1) // FA: Me_inv(e).Mult zone by zone, L2iter += 1 per zone (:501-515)
+   {
+      t0 = now();
+      fa_me_inv_mult(*c, e_rhs.data(), de);
+      c->t_cgL2 += now() - t0;
+      c->L2iter += c->NE;
+      return;
+   }
    lgo_cg(h, 1, e_rhs.data(), de, cg_tol, cg_max_iter); // :481
 }
 
@@ -1508,7 +1831,10 @@ void lgo_hydro_mult(void *h, const double *S, double *dS, double cg_tol, int cg_
 double lgo_internal_energy(void *h, const double *e)
 {
    Ctx *c = (Ctx *)h;
-   if (c->dim == 2) { interp_dispatch<2>(c->L1D, c->Q1D, c->NE, 1, c->Bl.data(), nullptr, e, c->q_e.data(), nullptr); }
+   if (c->dim == 1)
+      for (int el = 0; el < c->NE; el++)
+         for (int q = 0; q < c->Q1D; q++) { c->q_e[(size_t)el * c->Q1D + q] = fa_interp(c->Bl, c->Q1D, q, c->L1D, e + (size_t)el * c->L1D); }
+   else if (c->dim == 2) { interp_dispatch<2>(c->L1D, c->Q1D, c->NE, 1, c->Bl.data(), nullptr, e, c->q_e.data(), nullptr); }
    else { interp_dispatch<3>(c->L1D, c->Q1D, c->NE, 1, c->Bl.data(), nullptr, e, c->q_e.data(), nullptr); }
    double s = 0.0;
    for (size_t i = 0; i < (size_t)c->NE * c->NQ; i++) { s += c->q_e[i] * c->rho0DetJ0w[i]; }
@@ -1520,7 +1846,10 @@ double lgo_kinetic_energy(void *h, const double *v)
    const int dim = c->dim;
    std::vector<double> qv((size_t)c->NE * c->NQ * dim);
    h1_gather(*c, dim, v, c->e_vec.data());
-   if (dim == 2) { interp_dispatch<2>(c->D1D, c->Q1D, c->NE, dim, c->B.data(), c->G.data(), c->e_vec.data(), qv.data(), nullptr); }
+   if (dim == 1)
+      for (int el = 0; el < c->NE; el++)
+         for (int q = 0; q < c->Q1D; q++) { qv[(size_t)el * c->Q1D + q] = fa_interp(c->B, c->Q1D, q, c->D1D, c->e_vec.data() + (size_t)el * c->D1D); }
+   else if (dim == 2) { interp_dispatch<2>(c->D1D, c->Q1D, c->NE, dim, c->B.data(), c->G.data(), c->e_vec.data(), qv.data(), nullptr); }
    else { interp_dispatch<3>(c->D1D, c->Q1D, c->NE, dim, c->B.data(), c->G.data(), c->e_vec.data(), qv.data(), nullptr); }
    double s = 0.0;
    for (size_t i = 0; i < (size_t)c->NE * c->NQ; i++)

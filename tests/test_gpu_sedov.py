@@ -49,7 +49,7 @@ def test_exact_solution_many_radii_vs_oracle(small_ctx):
     from laghos_amd import context as C
     from oracle.sedov_error import SedovSol
     rng = np.random.default_rng(5)
-    for dim, gamma, E, t in [(3, 1.4, 0.25, 0.6), (2, 1.4, 0.25, 0.8)]:
+    for dim, gamma, E, t in [(3, 1.4, 0.25, 0.6), (2, 1.4, 0.25, 0.8), (1, 1.4, 0.5, 0.2)]:
         sol = SedovSol(dim, gamma, 1.0, E)
         sol.set_time(t)
         r_h = rng.uniform(0, 1.2 * sol.r2, 200000)

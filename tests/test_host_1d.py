@@ -119,3 +119,42 @@ def test_driver_switches_pa_to_fa_in_1d():
     assert "only the partial-assembly path" not in p.stderr and "Switching to FA" not in p.stdout
     p = subprocess.run([EXE, "-p", "3", "-dim", "1", "-nx", "8", "-ms", "1"], capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode != 0 and "problem 3 is not defined in 1D" in p.stderr
+
+
+@pytest.mark.parametrize("problem", [1, 2])
+@pytest.mark.parametrize("rs,ok,ot", [(0, 1, 0), (1, 2, 1), (3, 3, 2), (2, 4, 3), (5, 5, 4)])
+def test_segment01_discretization_vs_oracle(problem, rs, ok, ot):
+    """The host's 1D discretisation against the oracle's Problem (oracle/fem.py, written independently from the
+    reference): initial state, rho0 (Bernstein dofs and at the quadrature points), gamma, numbering, essential dofs."""
+    from oracle.fem import Problem
+    d = disc(rs, ok, ot, problem)
+    p = Problem(mesh="segment01", rs=rs, order_v=ok, order_e=ot, problem=problem)
+    S, rho_l2, gamma, rho0_q = p.initial_state()
+    assert p.dim == 1 and p.NE == 2 * 2 ** rs and p.N == p.NE * ok + 1
+    assert np.array_equal(d["h1map"].reshape(p.NE, p.ND), p.h1map)
+    assert np.array_equal(d["ess"][0], p.ess[0]) and len(p.ess) == 1
+    assert d["S0"].shape == S.shape
+    assert np.max(np.abs(d["S0"] - S)) <= 1e-14 * np.max(np.abs(S))
+    assert np.max(np.abs(d["rho0_l2"] - rho_l2)) <= 1e-14
+    assert np.array_equal(d["rho0_q"], rho0_q)
+    assert np.array_equal(d["gamma"], gamma)
+    assert np.max(np.abs(d["W"] - p.W)) <= 1e-15
+
+
+@pytest.mark.parametrize("nx", [3, 7, 257])
+def test_cartesian_breaks_vs_segment01(nx):
+    """The oracle's `-dim 1 -nx n` mesh (breaks = linspace(0, 1, n + 1)) is segment01 refined when n = 2^(rs+1), and a
+    valid 1D problem of any size otherwise: numbering, ends, node coordinates."""
+    from oracle.fem import Problem
+    ok = 2
+    p = Problem(breaks=[np.linspace(0.0, 1.0, nx + 1)], order_v=ok, order_e=1, problem=2)
+    assert p.NE == nx and p.N == nx * ok + 1
+    assert np.array_equal(p.h1map, np.arange(nx)[:, None] * ok + np.arange(ok + 1)[None, :])
+    assert list(p.ess[0]) == [0, p.N - 1]
+    x = p.initial_state()[0][:p.N]
+    assert np.all(np.diff(x) > 0) and x[0] == 0.0 and x[-1] == 1.0
+    if nx == 257:
+        return
+    q = Problem(mesh="segment01", rs=3, order_v=ok, order_e=1, problem=2)
+    r = Problem(breaks=[np.linspace(0.0, 1.0, 17)], order_v=ok, order_e=1, problem=2)
+    assert np.max(np.abs(q.initial_state()[0] - r.initial_state()[0])) <= 1e-15
