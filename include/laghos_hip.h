@@ -288,6 +288,24 @@ int lgh_sedov_density_error(lgh_ctx *ctx, const double *x_h1, const double *rho_
                             const double origin[3], int n1d, const double *weights, const double *B_h1,
                             const double *G_h1, const double *B_l2, double *err2);
 
+/* ---- visualisation sampling (stands in for VisItDataCollection::Save, laghos.cpp:691-701, :845-871; the driver's
+ * `-paraview` dumps): x, v, e, the density rho_l2 (lgh_compute_density; may be NULL) and the pressure of the equation of
+ * state of QUpdateBody (laghos_solver.cpp:1069-1168), p = (gamma_z - 1) rho max(e, 0), on a lattice of R1 = R + 1 points
+ * per direction in every zone (2 <= R1 <= 9).  With NP = NE * R1^dim the point index is pt = e * R1^dim + (rx + R1 * (ry +
+ * R1 * rz)), e the CALLER's zone index (the one h1_map uses).  Outputs are device arrays, structure of arrays:
+ * x_out[c * NP + pt], v_out[c * NP + pt] (c < dim), e_out[pt], rho_out[pt], p_out[pt]; each may be NULL and is then
+ * skipped (the others keep their bits).  B_h1_lat [r + R1 * d] / B_l2_lat [r + R1 * l] are HOST tables of the 1-D H1 / L2
+ * bases at the lattice abscissae r / R - lgh_config.B_h1 / B_l2 with Q1D -> R1; they are read during the call, nothing is
+ * kept of them.  rho_out or p_out without rho_l2, or an R1 out of range: LGH_ERR_ARG; a lattice table of more than 81 entries
+ * (R1 * D1D) or a zone that needs more than 64 KB of LDS (D1D = 9 on R1 = 9 points in 3D): LGH_ERR_UNSUPPORTED.  No kernel is
+ * launched in either case.
+ * Asynchronous on the context's stream; reads S, rho_l2 and the context's constant data, writes its outputs only: the
+ * quadrature data, its generation counter and the fused force products are untouched.  All dimensions (1D included). */
+int lgh_sample_fields(lgh_ctx *ctx, const double *S, const double *rho_l2 /* or NULL */,
+                      int R1, const double *B_h1_lat /* host, R1*D1D, [r + R1*d] */,
+                      const double *B_l2_lat /* host, R1*L1D, [r + R1*l] */,
+                      double *x_out, double *v_out, double *e_out, double *rho_out, double *p_out);
+
 /* ---- timing data (TimingData, laghos_solver.hpp:39-56): seconds measured with
  * HIP events around the same regions as the reference stopwatches.
  * t[0..3] = cgH1, cgL2, force, qdata; c[0..2] = H1iter, L2iter, quad_tstep */
@@ -307,6 +325,7 @@ int lgh_enable_timers(lgh_ctx *ctx, int on);
 #define LGH_KERNEL_MASS_CG_L2 5
 #define LGH_KERNEL_HALO 6         /* one shared-node / scalar exchange over RCCL: pack, grouped send/recv, combine */
 #define LGH_KERNEL_ALLREDUCE 7    /* one ncclAllReduce of device scalars */
+#define LGH_KERNEL_SAMPLE 8       /* lgh_sample_fields */
 int lgh_ktime_begin(lgh_ctx *ctx, int which, int max_samples);
 int lgh_ktime_end(lgh_ctx *ctx, int *launches, double *mean_seconds);
 /* Whether lgh_create found the 1-D H1 / L2 tables mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (any nodal or

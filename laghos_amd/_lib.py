@@ -81,6 +81,7 @@ SYMBOLS = {
     "lgh_sedov_eval": (_I, [_P, c_dbl_p, _D, _L, _P, _P, _P, _P]),
     "lgh_compute_density": (_I, [_P, _P, _P]),
     "lgh_sedov_density_error": (_I, [_P, _P, _P, c_dbl_p, _D, c_dbl_p, _I, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
+    "lgh_sample_fields": (_I, [_P, _P, _P, _I, c_dbl_p, c_dbl_p, _P, _P, _P, _P, _P]),
     "lgh_get_timers": (_I, [_P, c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
     "lgh_reset_timers": (_I, [_P]),
     "lgh_enable_timers": (_I, [_P, _I]),

@@ -362,6 +362,17 @@ class Context:
                                                ctypes.byref(out)))
         return out.value
 
+    def sample_fields(self, S, rho_l2, B_h1_lat, B_l2_lat, x=None, v=None, e=None, rho=None, p=None):
+        """lgh_sample_fields: the fields of S (and the density dofs rho_l2, or None) on the lattice whose host tables are
+        B_h1_lat (R1, D1D) and B_l2_lat (R1, L1D), indexed [r, d]; x, v: device tensors of dim * NE * R1^dim, e, rho, p:
+        NE * R1^dim, each may be None (skipped).  Asynchronous."""
+        Bh = _np_f64(np.asarray(B_h1_lat).T.reshape(-1))   # -> [r + R1*d]
+        Bl = _np_f64(np.asarray(B_l2_lat).T.reshape(-1))
+        R1 = int(np.asarray(B_h1_lat).shape[0])
+        opt = lambda t: _ptr(t) if t is not None else None
+        check(self.lib.lgh_sample_fields(self.h, _ptr(S), opt(rho_l2), R1, _dbl(Bh), _dbl(Bl), opt(x), opt(v), opt(e), opt(rho),
+                                         opt(p)))
+
     def solve_energy_begin(self, S, v, dS, e_rhs, rel_tol, max_iter, e_source=None):
         check(self.lib.lgh_solve_energy_begin(self.h, _ptr(S), _ptr(v), _ptr(dS), _ptr(e_rhs),
                                               _ptr(e_source) if e_source is not None else None,

@@ -137,6 +137,15 @@ Tables::Tables(int ov, int oe, int oq) : order_v(ov), order_e(oe), D1D(ov + 1), 
    BernsteinTable(oe, qpts, Bl);
 }
 
+void LatticeTables(int order_v, int order_e, int R, std::vector<double> &B_h1_lat, std::vector<double> &B_l2_lat)
+{
+   std::vector<double> gll, pts((size_t)R + 1), G;
+   for (int r = 0; r <= R; r++) { pts[r] = (double)r / (double)R; } // (0 and 1 exactly: the end rows are unit vectors)
+   GaussLobatto(order_v + 1, gll);
+   LagrangeTables(gll, pts, B_h1_lat, G);
+   BernsteinTable(order_e, pts, B_l2_lat);
+}
+
 // ---- mesh ---------------------------------------------------------------------------
 CartMesh CartMesh::Named(const std::string &name_in)
 {

@@ -36,6 +36,11 @@ struct Tables
    Tables(int order_v, int order_e, int order_q = -1);
 };
 
+// The same two bases at the lattice abscissae r/R, r = 0..R, of the visualisation sampling (lgh_sample_fields; R1 = R + 1
+// points per direction): B_h1_lat[r + R1*d] (Gauss-Lobatto Lagrange, order_v), B_l2_lat[r + R1*l] (Bernstein, order_e) -
+// Tables::B / Bl with Q1D -> R1.
+void LatticeTables(int order_v, int order_e, int R, std::vector<double> &B_h1_lat, std::vector<double> &B_l2_lat);
+
 // ---- mesh ---------------------------------------------------------------------------
 // Tensor-product mesh given by per-axis break points; element e = ex + nx*(ey + ny*ez).
 struct CartMesh

@@ -5,10 +5,12 @@
 // PA mode (-pa), dim 2/3, problems 0-7 on the structured meshes of data/; in 1D (data/segment01.mesh, -dim 1) the FA path,
 // problems 1 and 2, to which -pa switches as in the reference (laghos.cpp:454-462);
 // -s 1, 2, 3, 4 (Euler, RK2, RK3 SSP, RK4) and 7 (RK2Avg).  Everything else the reference driver does
-// (visualisation, VisIt, -fa in 2D/3D, AMR, METIS, Umpire, Caliper) is out of scope
-// (SURVEY §2).  Exposed both as the `laghos` executable and as C entry points
+// (GLVis sockets, VisIt / MFEM data collections, -fa in 2D/3D, AMR, METIS, Umpire, Caliper) is out of scope
+// (SURVEY §2); `-paraview` writes VTK files ParaView and VisIt open directly (vtk_output.hpp).
+// Exposed both as the `laghos` executable and as C entry points
 // (laghos_sim_*) that bench.py drives through ctypes.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -23,6 +25,7 @@
 
 #include "laghos_solver.hpp"
 #include "sedov_exact.hpp"
+#include "vtk_output.hpp"
 
 using namespace laghos;
 
@@ -48,6 +51,11 @@ struct Options
    bool check_exact_sedov = false; // -err (laghos.cpp:262)
    bool gfprint = false;           // -print (laghos.cpp:283-285)
    std::string basename = "results/Laghos"; // -k (laghos.cpp:286-287)
+   // -paraview: VTK dumps of density, velocity, specific internal energy (the reference's VisIt fields, laghos.cpp:691-701,
+   // :845-871) and pressure at cycle 0 and every -vs steps, under <basename>_paraview/ with the collection <basename>.pvd
+   bool paraview = false;
+   bool vis_refine_set = false;
+   int vis_refine = 0;             // -vr: lattice cells per zone and direction (default: order_v), 1..8
    int dev = 0;
    // multi-rank (set by the launcher, not the reference CLI)
    int nranks = 1, rank = 0;
@@ -102,6 +110,15 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
       if (a == "-no-fom" || a == "--no-fom") { o.fom = false; continue; }
       if (a == "-q" || a == "--quiet") { o.quiet = true; continue; }
       if (a == "-print" || a == "--print") { o.gfprint = true; continue; }
+      if (a == "-paraview" || a == "--paraview") { o.paraview = true; continue; }
+      if (a == "-no-paraview" || a == "--no-paraview") { o.paraview = false; continue; }
+      if (a == "-vr" || a == "--vis-refine")
+      {
+         if (!(v = need(i))) { return false; }
+         o.vis_refine = std::atoi(v);
+         o.vis_refine_set = true;
+         continue;
+      }
       if (a == "-store-stress" || a == "--store-stress") { o.store_stress = true; continue; }
       if (a == "-no-store-stress" || a == "--no-store-stress") { o.store_stress = false; continue; }
       if (a == "-renumber" || a == "--renumber") { if (!(v = need(i))) { return false; } o.renumber = v; continue; }
@@ -109,6 +126,12 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
       if (a == "-d" || a == "--device") { if (!need(i)) { return false; } continue; } // always the HIP path
       if (a == "-no-vis" || a == "--no-visualization" || a == "-no-visit" || a == "-no-print") { continue; }
       err = "unsupported option: " + a;
+      return false;
+   }
+   if (!o.vis_refine_set) { o.vis_refine = o.order_v; }
+   if ((o.vis_refine_set || o.paraview) && (o.vis_refine < 1 || o.vis_refine > 8))
+   {
+      err = "-vr / --vis-refine must be between 1 and 8, got " + std::to_string(o.vis_refine);
       return false;
    }
    return true;
@@ -244,7 +267,60 @@ struct laghos_sim
    int checks = 0;
    bool checks_ok = true;
    std::string error;
+   // -paraview: the dumps so far (the .pvd is rewritten after each), scratch, and where the time of a dump goes
+   std::vector<double> pv_times;
+   std::vector<int> pv_cycles;
+   Vector pv_rho, pv_dev;
+   std::vector<double> pv_host;
+   double pv_seconds[3] = {0, 0, 0}; // density + sampling (GPU), device-to-host copy, file write
 };
+
+// One `-paraview` dump of the state at cycle `cycle` (laghos.cpp:691-701, :845-871): density, lattice values on the GPU, one
+// copy to the host, <basename>_paraview/cycle_<cycle>[.<rank>].vtu; rank 0 adds the .pvtu of a multi-rank cycle and
+// rewrites <basename>.pvd.  rho: the density of this state where the caller (`-print`) has projected it already.
+static bool DumpParaview(laghos_sim *s, int cycle, const Vector *rho = nullptr)
+{
+   using clk = std::chrono::steady_clock;
+   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+   const Options &o = s->opt;
+   auto &hydro = *s->hydro;
+   const int dim = s->disc->dim, R = o.vis_refine;
+   const long NP = hydro.SamplePoints(R);
+   const clk::time_point t0 = clk::now();
+   if (!rho)
+   {
+      hydro.ComputeDensity(s->S, s->pv_rho); // rho_gf is refreshed before the output (laghos.cpp:827-830)
+      rho = &s->pv_rho;
+   }
+   hydro.SampleFields(s->S, *rho, R, s->pv_dev);
+   hydro.Sync();
+   const clk::time_point t1 = clk::now();
+   s->pv_dev.ToHost(s->pv_host);
+   const clk::time_point t2 = clk::now();
+   const double *h = s->pv_host.data();
+   const std::string dir = o.basename + "_paraview";
+   const size_t slash = o.basename.find_last_of('/');
+   const std::string rel_dir = (slash == std::string::npos ? o.basename : o.basename.substr(slash + 1)) + "_paraview";
+   bool ok = WriteVtu(dir, dim, s->disc->NE, R + 1, h, h + dim * NP, h + 2 * dim * NP, h + (2 * dim + 1) * NP,
+                      h + (2 * dim + 2) * NP, cycle, s->t, o.rank, o.nranks);
+   s->pv_times.push_back(s->t);
+   s->pv_cycles.push_back(cycle);
+   if (ok && o.rank == 0)
+   {
+      if (o.nranks > 1) { ok = WritePvtu(dir, cycle, s->t, o.nranks); }
+      ok = ok && WritePvd(o.basename + ".pvd", rel_dir, s->pv_times, s->pv_cycles, o.nranks);
+   }
+   const clk::time_point t3 = clk::now();
+   s->pv_seconds[0] += secs(t0, t1);
+   s->pv_seconds[1] += secs(t1, t2);
+   s->pv_seconds[2] += secs(t2, t3);
+   if (!ok)
+   {
+      s->error = "cannot write the -paraview files under " + dir;
+      std::fprintf(stderr, "%s\n", s->error.c_str());
+   }
+   return ok;
+}
 
 extern "C"
 {
@@ -352,6 +428,7 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
    s->hydro->ResetTimeStepEstimate();                                                // :707
    s->t = 0.0;
    s->dt = s->hydro->GetTimeStepEstimate(s->S);                                      // :708
+   if (o.paraview && !DumpParaview(s.get(), 0)) { return nullptr; }                   // :691-701
    return s.release();
 }
 
@@ -411,10 +488,10 @@ int laghos_sim_step(laghos_sim *s)
                       << ",\t|e| = " << std::setprecision(10) << std::scientific << sqrt_norm;
             std::cout << std::fixed << std::endl;
          }
+         Vector rho;
          if (o.gfprint) // laghos.cpp:873-900
          {
             std::vector<double> Sh, rhoh;
-            Vector rho;
             hydro.ComputeDensity(s->S, rho); // laghos.cpp:827-830 (rho_gf is refreshed before the output)
             hydro.Sync();
             s->S.ToHost(Sh);
@@ -426,6 +503,7 @@ int laghos_sim_step(laghos_sim *s)
                return -1;
             }
          }
+         if (o.paraview && !DumpParaview(s, s->ti, o.gfprint ? &rho : nullptr)) { return -1; } // laghos.cpp:845-871 (one projection for both)
       }
       if (o.check)
       {
@@ -529,6 +607,29 @@ int laghos_host_tables(int order_v, int order_e, double *qpts, double *qwts, dou
    std::memcpy(Bl, t.Bl.data(), t.Bl.size() * sizeof(double));
    return t.Q1D;
 }
+// host-only: the 1-D bases at the lattice abscissae r/R of the visualisation sampling, B_h1_lat[r + (R+1)*d] ((R+1)*(order_v+1)),
+// B_l2_lat[r + (R+1)*l] ((R+1)*(order_e+1))
+int laghos_host_lattice_tables(int order_v, int order_e, int R, double *B_h1_lat, double *B_l2_lat)
+{
+   if (order_v < 1 || order_e < 0 || R < 1) { return -1; }
+   std::vector<double> Bh, Bl;
+   LatticeTables(order_v, order_e, R, Bh, Bl);
+   std::memcpy(B_h1_lat, Bh.data(), Bh.size() * sizeof(double));
+   std::memcpy(B_l2_lat, Bl.data(), Bl.size() * sizeof(double));
+   return 0;
+}
+// host-only: the VTK writers of the `-paraview` dumps (vtk_output.hpp); 0 = written.  The arrays are host arrays in the
+// layout of lgh_sample_fields; the piece goes to <dir>/cycle_<6 digits>[.<rank>].vtu
+int laghos_host_write_vtu(const char *dir, int dim, int NE, int R1, const double *x, const double *v, const double *e,
+                          const double *rho, const double *p, int cycle, double time, int rank, int nranks)
+{
+   return WriteVtu(dir, dim, NE, R1, x, v, e, rho, p, cycle, time, rank, nranks) ? 0 : -1;
+}
+int laghos_host_write_pvtu(const char *dir, int cycle, double time, int nranks) { return WritePvtu(dir, cycle, time, nranks) ? 0 : -1; }
+int laghos_host_write_pvd(const char *pvd_path, const char *rel_dir, int n, const double *times, const int *cycles, int nranks)
+{
+   return WritePvd(pvd_path, rel_dir, std::vector<double>(times, times + n), std::vector<int>(cycles, cycles + n), nranks) ? 0 : -1;
+}
 // Builds the discretisation of one rank and returns sizes; arrays are copied out
 // by laghos_host_disc_get.  kind: 0 h1map, 1 S0, 2 rho0_l2, 3 gamma, 4 rho0_q,
 // 5 ess[0], 6 ess[1], 7 ess[2], 8 owner, 9 W, 10 nbr_rank, 11.. nbr_nodes[k-11]
@@ -539,12 +640,14 @@ struct laghos_host_disc
 };
 // renumber: NULL / "none", "mfem" or "random" (Discretization::Renumber; kinds 100 / 101 of laghos_host_disc_get then
 // return node_perm / elem_perm)
-laghos_host_disc *laghos_host_disc_create_renumbered(const char *mesh, int rs, int order_v, int order_e, int problem,
-                                                     double blast_energy, int nranks, int rank, const char *renumber, int seed)
+static laghos_host_disc *HostDiscCreate(const char *mesh, const int *zones, int rs, int order_v, int order_e, int problem,
+                                        double blast_energy, int nranks, int rank, const char *renumber, int seed)
 {
    try
    {
-      CartMesh m = CartMesh::Named(mesh);
+      // zones: a Cartesian grid of zones[0] x zones[1] x zones[2] unit-box zones in zones[3] dimensions (the driver's
+      // "default" mesh) instead of a named one
+      CartMesh m = zones ? CartMesh::Cartesian(zones[3], zones[0], zones[1], zones[2], 1.0, 1.0, 1.0) : CartMesh::Named(mesh);
       for (int l = 0; l < rs; l++) { m.UniformRefinement(); }
       std::unique_ptr<laghos_host_disc> h(new laghos_host_disc());
       h->d.reset(new Discretization(m, order_v, order_e, problem, nranks, rank, -1, blast_energy));
@@ -557,6 +660,18 @@ laghos_host_disc *laghos_host_disc_create_renumbered(const char *mesh, int rs, i
       std::fprintf(stderr, "laghos_host_disc_create: %s\n", e.what());
       return nullptr;
    }
+}
+laghos_host_disc *laghos_host_disc_create_renumbered(const char *mesh, int rs, int order_v, int order_e, int problem,
+                                                     double blast_energy, int nranks, int rank, const char *renumber, int seed)
+{
+   return HostDiscCreate(mesh, nullptr, rs, order_v, order_e, problem, blast_energy, nranks, rank, renumber, seed);
+}
+// the same on a Cartesian grid of nx x ny x nz zones of the unit box (`-m default -dim .. -nx .. -ny .. -nz ..`)
+laghos_host_disc *laghos_host_disc_create_cartesian(int dim, int nx, int ny, int nz, int rs, int order_v, int order_e, int problem,
+                                                    double blast_energy, int nranks, int rank, const char *renumber, int seed)
+{
+   const int zones[4] = {nx, ny, nz, dim};
+   return HostDiscCreate(nullptr, zones, rs, order_v, order_e, problem, blast_energy, nranks, rank, renumber, seed);
 }
 laghos_host_disc *laghos_host_disc_create(const char *mesh, int rs, int order_v, int order_e, int problem,
                                           double blast_energy, int nranks, int rank)
@@ -621,6 +736,11 @@ int laghos_main(int argc, const char *const *argv)
    std::cout << std::endl;
    std::cout << "Energy  diff: " << std::scientific << std::setprecision(2)
              << std::fabs(s->energy_init - energy_final) << std::endl;
+   if (o.paraview && !o.quiet)
+   {
+      std::cout << "ParaView dumps: " << s->pv_cycles.size() << " (sample " << s->pv_seconds[0] << " s, copy " << s->pv_seconds[1]
+                << " s, write " << s->pv_seconds[2] << " s) -> " << o.basename << ".pvd" << std::endl;
+   }
    int ret = 0;
    if (o.check_exact_sedov)
    {

@@ -237,6 +237,24 @@ double LagrangianHydroOperator::SedovDensityError(const Vector &S, const Vector 
    return std::sqrt(err2);
 }
 
+long LagrangianHydroOperator::SamplePoints(int R) const
+{
+   long np = NE;
+   for (int a = 0; a < dim; a++) { np *= R + 1; }
+   return np;
+}
+
+void LagrangianHydroOperator::SampleFields(const Vector &S, const Vector &rho, int R, Vector &out) const
+{
+   const long NP = SamplePoints(R);
+   if (out.Size() != (2 * dim + 3) * NP) { out.SetSize((2 * dim + 3) * NP); }
+   std::vector<double> Bh, Bl;
+   LatticeTables(disc.tab.order_v, disc.tab.order_e, R, Bh, Bl);
+   double *o = out.Write();
+   LGH_VERIFY(lgh_sample_fields(ctx, S.Read(), rho.Read(), R + 1, Bh.data(), Bl.data(), o, o + dim * NP, o + 2 * dim * NP,
+                                o + (2 * dim + 1) * NP, o + (2 * dim + 2) * NP));
+}
+
 double LagrangianHydroOperator::AllReduce(double v, int op) const
 {
    if (disc.part.nranks > 1) { LGH_VERIFY(lgh_allreduce(ctx, &v, op)); }

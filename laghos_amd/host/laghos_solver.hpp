@@ -85,6 +85,12 @@ public:
    // error rule of order err_order (laghos.cpp:1007-1086); all-reduced
    double SedovDensityError(const Vector &S, const Vector &rho, const double par[21], double t,
                             const double origin[3], int err_order) const;
+   // The fields of S and the density rho on the lattice of R + 1 points per direction in every zone (lgh_sample_fields;
+   // stands in for the grid-function evaluation behind the reference's data collections, laghos.cpp:691-701, :845-871):
+   // out = [x | v | e | rho | p] in blocks of dim, dim, 1, 1, 1 times NE (R+1)^dim values, zones in the caller's order.
+   // Asynchronous on the context's stream; the quadrature data is not touched.
+   void SampleFields(const Vector &S, const Vector &rho, int R, Vector &out) const;
+   long SamplePoints(int R) const; // NE (R+1)^dim
    void PrintTimingData(bool IamRoot, int steps, bool fom) const;
    const TimingData &Timing() const;
    void ResetTiming();

@@ -1,0 +1,190 @@
+// vtk_output.cpp — VTK XML writers of the `-paraview` dumps (vtk_output.hpp).
+#include "vtk_output.hpp"
+
+#include <cstdint>
+#include <cstdio>
+#include <fstream>
+#include <iomanip>
+#include <sstream>
+#include <sys/stat.h>
+
+namespace laghos
+{
+
+void MakeDirs(const std::string &dir)
+{
+   for (size_t p = 1; p <= dir.size(); p++)
+   {
+      if (p == dir.size() || dir[p] == '/') { (void)::mkdir(dir.substr(0, p).c_str(), 0777); }
+   }
+}
+
+static std::string CycleTag(int cycle)
+{
+   char buf[32];
+   std::snprintf(buf, sizeof(buf), "cycle_%06d", cycle);
+   return buf;
+}
+std::string VtuName(int cycle, int nranks, int rank)
+{
+   std::string s = CycleTag(cycle);
+   if (nranks > 1) { s += "." + std::to_string(rank); }
+   return s + ".vtu";
+}
+std::string PvtuName(int cycle) { return CycleTag(cycle) + ".pvtu"; }
+
+namespace
+{
+
+// the arrays of the appended block, in file order: a DataArray element in the header, UInt64 byte count + data behind it
+struct Appended
+{
+   struct Block { const void *data; uint64_t bytes; };
+   std::vector<Block> blocks;
+   uint64_t offset = 0;
+   std::string Array(const char *type, const char *name, int ncomp, const void *data, uint64_t bytes, const char *extra = "")
+   {
+      std::ostringstream os;
+      os << "<DataArray type=\"" << type << "\" Name=\"" << name << "\"";
+      if (ncomp > 0) { os << " NumberOfComponents=\"" << ncomp << "\""; }
+      os << extra << " format=\"appended\" offset=\"" << offset << "\"/>\n";
+      blocks.push_back({data, bytes});
+      offset += sizeof(uint64_t) + bytes;
+      return os.str();
+   }
+   void Write(std::ostream &f) const
+   {
+      f << "<AppendedData encoding=\"raw\">\n_";
+      for (const Block &b : blocks)
+      {
+         f.write(reinterpret_cast<const char *>(&b.bytes), sizeof(uint64_t));
+         f.write(reinterpret_cast<const char *>(b.data), (std::streamsize)b.bytes);
+      }
+      f << "\n</AppendedData>\n";
+   }
+};
+
+// c-th component of point pt of a dim-component structure of arrays, zero above dim
+std::vector<double> Interleave3(const double *soa, int dim, size_t NP)
+{
+   std::vector<double> a(3 * NP, 0.0);
+   for (int c = 0; c < dim; c++)
+   {
+      for (size_t i = 0; i < NP; i++) { a[3 * i + c] = soa[c * NP + i]; }
+   }
+   return a;
+}
+
+const char *kPointArrays[4][2] = {{"density", "1"}, {"velocity", "3"}, {"specific_internal_energy", "1"}, {"pressure", "1"}};
+
+} // namespace
+
+bool WriteVtu(const std::string &dir, int dim, int NE, int R1, const double *x, const double *v, const double *e,
+              const double *rho, const double *p, int cycle, double time, int rank, int nranks)
+{
+   if (dim < 1 || dim > 3 || NE < 0 || R1 < 2 || !x || !v || !e || !rho || !p) { return false; }
+   const int R = R1 - 1;
+   size_t NPZ = 1, NCZ = 1;
+   for (int a = 0; a < dim; a++) { NPZ *= R1; NCZ *= R; }
+   const size_t NP = (size_t)NE * NPZ, NC = (size_t)NE * NCZ;
+   const int nv = 1 << dim; // corners of a cell
+   const std::vector<double> pts = Interleave3(x, dim, NP), vel = Interleave3(v, dim, NP);
+   // R^dim linear cells per zone on the zone's own lattice points, corners in VTK's order (VTK_LINE 3, VTK_QUAD 9,
+   // VTK_HEXAHEDRON 12: counter-clockwise in the bottom plane, then the top plane)
+   static const int corner[8][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {0, 1, 0}, {0, 0, 1}, {1, 0, 1}, {1, 1, 1}, {0, 1, 1}};
+   std::vector<int64_t> conn(NC * nv), offs(NC);
+   std::vector<uint8_t> types(NC, (uint8_t)(dim == 3 ? 12 : (dim == 2 ? 9 : 3)));
+   std::vector<int32_t> zone(NC), rnk(NC, (int32_t)rank);
+   const int Ry = dim > 1 ? R : 1, Rz = dim > 2 ? R : 1;
+   size_t cell = 0;
+   for (int z = 0; z < NE; z++)
+   {
+      for (int cz = 0; cz < Rz; cz++)
+         for (int cy = 0; cy < Ry; cy++)
+            for (int cx = 0; cx < R; cx++, cell++)
+            {
+               for (int k = 0; k < nv; k++)
+               {
+                  const int rx = cx + corner[k][0], ry = cy + corner[k][1], rz = cz + corner[k][2];
+                  conn[cell * nv + k] = (int64_t)((size_t)z * NPZ + rx + (size_t)R1 * (ry + (size_t)R1 * rz));
+               }
+               offs[cell] = (int64_t)((cell + 1) * nv);
+               zone[cell] = z;
+            }
+   }
+   const int32_t cyc = cycle;
+   Appended ap;
+   std::ostringstream h;
+   h << "<?xml version=\"1.0\"?>\n<VTKFile type=\"UnstructuredGrid\" version=\"1.0\" byte_order=\"LittleEndian\" "
+        "header_type=\"UInt64\">\n<UnstructuredGrid>\n<FieldData>\n";
+   h << ap.Array("Float64", "TIME", 0, &time, sizeof(double), " NumberOfTuples=\"1\"");
+   h << ap.Array("Int32", "CYCLE", 0, &cyc, sizeof(int32_t), " NumberOfTuples=\"1\"");
+   h << "</FieldData>\n<Piece NumberOfPoints=\"" << NP << "\" NumberOfCells=\"" << NC << "\">\n<Points>\n";
+   h << ap.Array("Float64", "Points", 3, pts.data(), pts.size() * sizeof(double));
+   h << "</Points>\n<Cells>\n";
+   h << ap.Array("Int64", "connectivity", 0, conn.data(), conn.size() * sizeof(int64_t));
+   h << ap.Array("Int64", "offsets", 0, offs.data(), offs.size() * sizeof(int64_t));
+   h << ap.Array("UInt8", "types", 0, types.data(), types.size());
+   h << "</Cells>\n<PointData Scalars=\"density\" Vectors=\"velocity\">\n";
+   h << ap.Array("Float64", "density", 1, rho, NP * sizeof(double));
+   h << ap.Array("Float64", "velocity", 3, vel.data(), vel.size() * sizeof(double));
+   h << ap.Array("Float64", "specific_internal_energy", 1, e, NP * sizeof(double));
+   h << ap.Array("Float64", "pressure", 1, p, NP * sizeof(double));
+   h << "</PointData>\n<CellData>\n";
+   h << ap.Array("Int32", "zone", 1, zone.data(), zone.size() * sizeof(int32_t));
+   h << ap.Array("Int32", "rank", 1, rnk.data(), rnk.size() * sizeof(int32_t));
+   h << "</CellData>\n</Piece>\n</UnstructuredGrid>\n";
+   MakeDirs(dir);
+   std::ofstream f((dir + "/" + VtuName(cycle, nranks, rank)).c_str(), std::ios::binary);
+   if (!f) { return false; }
+   f << h.str();
+   ap.Write(f);
+   f << "</VTKFile>\n";
+   f.close();
+   return !f.fail();
+}
+
+bool WritePvtu(const std::string &dir, int cycle, double time, int nranks)
+{
+   MakeDirs(dir);
+   std::ofstream f((dir + "/" + PvtuName(cycle)).c_str());
+   if (!f) { return false; }
+   f << std::setprecision(17);
+   f << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PUnstructuredGrid\" version=\"1.0\" byte_order=\"LittleEndian\" "
+        "header_type=\"UInt64\">\n<PUnstructuredGrid GhostLevel=\"0\">\n";
+   f << "<!-- cycle " << cycle << ", time " << time << " -->\n";
+   f << "<PPoints>\n<PDataArray type=\"Float64\" Name=\"Points\" NumberOfComponents=\"3\"/>\n</PPoints>\n";
+   f << "<PPointData Scalars=\"density\" Vectors=\"velocity\">\n";
+   for (auto &a : kPointArrays)
+   {
+      f << "<PDataArray type=\"Float64\" Name=\"" << a[0] << "\" NumberOfComponents=\"" << a[1] << "\"/>\n";
+   }
+   f << "</PPointData>\n<PCellData>\n<PDataArray type=\"Int32\" Name=\"zone\" NumberOfComponents=\"1\"/>\n"
+        "<PDataArray type=\"Int32\" Name=\"rank\" NumberOfComponents=\"1\"/>\n</PCellData>\n";
+   for (int r = 0; r < nranks; r++) { f << "<Piece Source=\"" << VtuName(cycle, nranks, r) << "\"/>\n"; }
+   f << "</PUnstructuredGrid>\n</VTKFile>\n";
+   f.close();
+   return !f.fail();
+}
+
+bool WritePvd(const std::string &pvd_path, const std::string &rel_dir, const std::vector<double> &times,
+              const std::vector<int> &cycles, int nranks)
+{
+   if (times.size() != cycles.size()) { return false; }
+   const size_t slash = pvd_path.find_last_of('/');
+   if (slash != std::string::npos) { MakeDirs(pvd_path.substr(0, slash)); }
+   std::ofstream f(pvd_path.c_str());
+   if (!f) { return false; }
+   f << std::setprecision(17);
+   f << "<?xml version=\"1.0\"?>\n<VTKFile type=\"Collection\" version=\"0.1\" byte_order=\"LittleEndian\">\n<Collection>\n";
+   for (size_t i = 0; i < times.size(); i++)
+   {
+      f << "<DataSet timestep=\"" << times[i] << "\" group=\"\" part=\"0\" file=\"" << rel_dir << "/"
+        << (nranks > 1 ? PvtuName(cycles[i]) : VtuName(cycles[i], 1, 0)) << "\"/>\n";
+   }
+   f << "</Collection>\n</VTKFile>\n";
+   f.close();
+   return !f.fail();
+}
+
+} // namespace laghos

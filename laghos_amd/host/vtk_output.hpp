@@ -1,0 +1,32 @@
+// vtk_output.hpp — ParaView/VisIt output of the `-paraview` dumps: VTK XML files of linear cells over the lattice values
+// lgh_sample_fields produces (stands in for the reference's VisItDataCollection, /root/reference/laghos.cpp:691-701,
+// :845-871; the layout follows what MFEM's ParaViewDataCollection does with its levels of detail).  Host only, no GPU
+// code, no MFEM: a high-order zone becomes R^dim linear cells on its (R+1)^dim lattice points, points duplicated zone
+// by zone so that the discontinuous fields are exact.  DESIGN.md §7b.
+#pragma once
+#include <string>
+#include <vector>
+
+namespace laghos
+{
+
+// mkdir -p
+void MakeDirs(const std::string &dir);
+
+// "cycle_<6 digits>.vtu", with ".<rank>" in front of the extension on several ranks
+std::string VtuName(int cycle, int nranks, int rank);
+std::string PvtuName(int cycle);
+
+// One UnstructuredGrid piece <dir>/VtuName(): NP = NE * R1^dim points, structure of arrays as lgh_sample_fields writes
+// them (x[c * NP + pt], v[c * NP + pt], e[pt], rho[pt], p[pt]; pt = e * R1^dim + rx + R1 * (ry + R1 * rz)).
+// PointData density, velocity, specific_internal_energy, pressure (Float64); CellData zone (the caller's zone id) and
+// rank (Int32); FieldData TIME, CYCLE.  Little endian, UInt64 headers, every array in one raw appended block.
+bool WriteVtu(const std::string &dir, int dim, int NE, int R1, const double *x, const double *v, const double *e,
+              const double *rho, const double *p, int cycle, double time, int rank, int nranks);
+// <dir>/PvtuName(): the pieces of all ranks of one cycle
+bool WritePvtu(const std::string &dir, int cycle, double time, int nranks);
+// The collection <pvd_path>: one DataSet per dump so far, file = <rel_dir>/<piece or .pvtu>
+bool WritePvd(const std::string &pvd_path, const std::string &rel_dir, const std::vector<double> &times,
+              const std::vector<int> &cycles, int nranks);
+
+} // namespace laghos

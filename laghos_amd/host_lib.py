@@ -57,10 +57,20 @@ def load():
         L.laghos_host_partition.argtypes = [I, I, I, I, I, ctypes.POINTER(I)]
         L.laghos_host_tables.restype = I
         L.laghos_host_tables.argtypes = [I, I, P, P, P, P, P, P]
+        L.laghos_host_lattice_tables.restype = I
+        L.laghos_host_lattice_tables.argtypes = [I, I, I, P, P]
+        L.laghos_host_write_vtu.restype = I
+        L.laghos_host_write_vtu.argtypes = [ctypes.c_char_p, I, I, I, P, P, P, P, P, I, D, I, I]
+        L.laghos_host_write_pvtu.restype = I
+        L.laghos_host_write_pvtu.argtypes = [ctypes.c_char_p, I, D, I]
+        L.laghos_host_write_pvd.restype = I
+        L.laghos_host_write_pvd.argtypes = [ctypes.c_char_p, ctypes.c_char_p, I, P, P, I]
         L.laghos_host_disc_create.restype = P
         L.laghos_host_disc_create.argtypes = [ctypes.c_char_p, I, I, I, I, D, I, I]
         L.laghos_host_disc_create_renumbered.restype = P
         L.laghos_host_disc_create_renumbered.argtypes = [ctypes.c_char_p, I, I, I, I, D, I, I, ctypes.c_char_p, I]
+        L.laghos_host_disc_create_cartesian.restype = P
+        L.laghos_host_disc_create_cartesian.argtypes = [I, I, I, I, I, I, I, I, D, I, I, ctypes.c_char_p, I]
         L.laghos_host_disc_destroy.argtypes = [P]
         L.laghos_host_disc_size.restype = Lg
         L.laghos_host_disc_size.argtypes = [P, I]
@@ -170,12 +180,62 @@ def host_tables(order_v, order_e):
     return dict(qpts=qp, qwts=qw, gll=gll, B=B.reshape(D, Q).T, G=G.reshape(D, Q).T, Bl=Bl.reshape(Ld, Q).T)
 
 
-def host_disc(mesh, rs, order_v, order_e, problem, blast_energy=1.0, nranks=1, rank=0, renumber=None, seed=1):
-    """Arrays of the C++ Discretization for one rank (host only, no GPU); renumber = "mfem" / "random": after
-    Discretization::Renumber (`-renumber`), with node_perm / elem_perm in the result."""
+def host_lattice_tables(order_v, order_e, R):
+    """The 1-D bases at the lattice abscissae r/R, r = 0..R, of the visualisation sampling (Context.sample_fields):
+    (B_h1_lat (R+1, order_v+1), B_l2_lat (R+1, order_e+1)), indexed [r, d]."""
     L = load()
-    h = L.laghos_host_disc_create_renumbered(mesh.encode(), rs, order_v, order_e, problem, blast_energy, nranks, rank,
-                                             renumber.encode() if renumber else None, seed)
+    R1, D, Ld = R + 1, order_v + 1, order_e + 1
+    Bh, Bl = np.empty(R1 * D), np.empty(R1 * Ld)
+    if L.laghos_host_lattice_tables(order_v, order_e, R, Bh.ctypes.data, Bl.ctypes.data) != 0:
+        raise ValueError(f"host_lattice_tables({order_v}, {order_e}, {R})")
+    return Bh.reshape(D, R1).T, Bl.reshape(Ld, R1).T
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def host_write_vtu(directory, dim, NE, R1, x, v, e, rho, p, cycle, time, rank=0, nranks=1):
+    """One `-paraview` piece from sampled host arrays in the layout of lgh_sample_fields (x, v: dim * NE * R1^dim, the others
+    NE * R1^dim); returns the path written, <directory>/cycle_<6 digits>[.<rank>].vtu."""
+    L = load()
+    arrs = [_f64(a) for a in (x, v, e, rho, p)]
+    NP = NE * R1 ** dim
+    assert [a.size for a in arrs] == [dim * NP, dim * NP, NP, NP, NP]
+    if L.laghos_host_write_vtu(str(directory).encode(), dim, NE, R1, *[a.ctypes.data for a in arrs], cycle, time, rank, nranks) != 0:
+        raise RuntimeError(f"cannot write a .vtu under {directory}")
+    tag = f"cycle_{cycle:06d}" + (f".{rank}" if nranks > 1 else "")
+    return os.path.join(str(directory), tag + ".vtu")
+
+
+def host_write_pvtu(directory, cycle, time, nranks):
+    """<directory>/cycle_<6 digits>.pvtu naming the pieces of all ranks; returns its path."""
+    if load().laghos_host_write_pvtu(str(directory).encode(), cycle, time, nranks) != 0:
+        raise RuntimeError(f"cannot write a .pvtu under {directory}")
+    return os.path.join(str(directory), f"cycle_{cycle:06d}.pvtu")
+
+
+def host_write_pvd(path, rel_dir, times, cycles, nranks=1):
+    """The collection `path`: one DataSet per (time, cycle), file = <rel_dir>/cycle_<6 digits>.vtu (.pvtu on several ranks)."""
+    t, c = _f64(times), np.ascontiguousarray(cycles, dtype=np.int32)
+    assert t.size == c.size
+    if load().laghos_host_write_pvd(str(path).encode(), str(rel_dir).encode(), int(t.size), t.ctypes.data, c.ctypes.data, nranks) != 0:
+        raise RuntimeError(f"cannot write {path}")
+
+
+def host_disc(mesh, rs, order_v, order_e, problem, blast_energy=1.0, nranks=1, rank=0, renumber=None, seed=1, zones=None):
+    """Arrays of the C++ Discretization for one rank (host only, no GPU); renumber = "mfem" / "random": after
+    Discretization::Renumber (`-renumber`), with node_perm / elem_perm in the result.  zones = (nx,), (nx, ny) or
+    (nx, ny, nz): a Cartesian grid of that many zones of the unit box (the driver's default mesh) instead of `mesh`."""
+    L = load()
+    ren = renumber.encode() if renumber else None
+    if zones is not None:
+        n = list(zones) + [1] * (3 - len(zones))
+        h = L.laghos_host_disc_create_cartesian(len(zones), n[0], n[1], n[2], rs, order_v, order_e, problem, blast_energy,
+                                                nranks, rank, ren, seed)
+    else:
+        h = L.laghos_host_disc_create_renumbered(mesh.encode(), rs, order_v, order_e, problem, blast_energy, nranks, rank,
+                                                 ren, seed)
     if not h:
         raise RuntimeError("laghos_host_disc_create failed")
 
