@@ -244,6 +244,20 @@ int lgh_vec_axpby_pair(lgh_ctx *ctx, double *z1, double a1, const double *x1, do
 int lgh_vec_axpby(lgh_ctx *ctx, double *z, double a, const double *x, double b,
                   const double *y, long n);                                /* z = a x + b y */
 int lgh_vec_dot(lgh_ctx *ctx, const double *x, const double *y, long n, double *result); /* sync */
+/* The state fingerprint of include/lgh_fingerprint.h over the n doubles at x (device), taken as their bit patterns at
+ * positions offset .. offset + n - 1: out[0] = sum, out[1] = xor of the mixed words (mod 2^64).  Integer arithmetic only:
+ * the two words do not depend on the launch shape, and the fingerprint of a concatenation is the word-wise combination
+ * (add, xor) of the fingerprints of its parts at their offsets.  Synchronous, like lgh_vec_dot.  Reads x, writes nothing of
+ * the caller's: the quadrature data, its generation counter and the fused force products are untouched.  All dimensions.
+ * n == 0 gives {0, 0} without a launch; n < 0, or x == NULL with n > 0: LGH_ERR_ARG.  x may be any 8-byte aligned address
+ * (a slice that starts at an odd element is read with a scalar head). */
+int lgh_vec_fingerprint(lgh_ctx *ctx, const double *x, long n, unsigned long long offset, unsigned long long out[2]);
+/* The launch lgh_vec_fingerprint makes for (x, n), for tests that want sizes beyond one pass of the grid: out[0] = workgroups
+ * (0: no launch), out[1] = threads of a workgroup, out[2] = 1 when a scalar head is taken (x not 16-byte aligned), out[3] =
+ * words one pass of the largest grid takes. */
+int lgh_vec_fingerprint_shape(lgh_ctx *ctx, const double *x, long n, long out[4]);
+/* The same function over n 64-bit words in HOST memory (no GPU, no context): what the checkpoint code computes. */
+int lgh_fingerprint_host(const void *words, long n, unsigned long long offset, unsigned long long out[2]);
 
 /* ---- energies (laghos_solver.cpp:640-697); synchronous, all-reduced */
 /* Acceleration source of SolveVelocity (source_type == 2, problem 7; laghos_solver.cpp:340-347,
@@ -326,6 +340,7 @@ int lgh_enable_timers(lgh_ctx *ctx, int on);
 #define LGH_KERNEL_HALO 6         /* one shared-node / scalar exchange over RCCL: pack, grouped send/recv, combine */
 #define LGH_KERNEL_ALLREDUCE 7    /* one ncclAllReduce of device scalars */
 #define LGH_KERNEL_SAMPLE 8       /* lgh_sample_fields */
+#define LGH_KERNEL_FINGERPRINT 9  /* lgh_vec_fingerprint */
 int lgh_ktime_begin(lgh_ctx *ctx, int which, int max_samples);
 int lgh_ktime_end(lgh_ctx *ctx, int *launches, double *mean_seconds);
 /* Whether lgh_create found the 1-D H1 / L2 tables mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (any nodal or

@@ -73,6 +73,9 @@ SYMBOLS = {
     "lgh_vec_axpby": (_I, [_P, _P, _D, _P, _D, _P, _L]),
     "lgh_vec_axpby_pair": (_I, [_P, _P, _D, _P, _D, _P, _D, _P, _D, _P, _L]),
     "lgh_vec_dot": (_I, [_P, _P, _P, _L, c_dbl_p]),
+    "lgh_vec_fingerprint": (_I, [_P, _P, _L, ctypes.c_ulonglong, ctypes.POINTER(ctypes.c_ulonglong)]),
+    "lgh_vec_fingerprint_shape": (_I, [_P, _P, _L, ctypes.POINTER(ctypes.c_long)]),
+    "lgh_fingerprint_host": (_I, [_P, _L, ctypes.c_ulonglong, ctypes.POINTER(ctypes.c_ulonglong)]),
     "lgh_internal_energy": (_I, [_P, _P, c_dbl_p]),
     "lgh_kinetic_energy": (_I, [_P, _P, c_dbl_p]),
     "lgh_sedov_setup": (_I, [_I, _D, _D, _D, _D, c_dbl_p]),

@@ -397,6 +397,19 @@ class Context:
         check(self.lib.lgh_vec_dot(self.h, _ptr(x), _ptr(y), x.numel(), ctypes.byref(v)))
         return v.value
 
+    def fingerprint(self, t, offset=0):
+        """lgh_vec_fingerprint: the two 64-bit words (sum, xor) of the state fingerprint (include/lgh_fingerprint.h) of the
+        device tensor t, its first element at position `offset`.  Synchronous; reads t only."""
+        out = (ctypes.c_ulonglong * 2)()
+        check(self.lib.lgh_vec_fingerprint(self.h, _ptr(t), t.numel(), int(offset), out))
+        return int(out[0]), int(out[1])
+
+    def fingerprint_shape(self, t):
+        """(workgroups, threads, scalar head, words per pass of the largest grid) of the launch fingerprint(t) makes"""
+        out = (ctypes.c_long * 4)()
+        check(self.lib.lgh_vec_fingerprint_shape(self.h, _ptr(t), t.numel(), out))
+        return tuple(out)
+
     def internal_energy(self, e):
         v = ctypes.c_double()
         check(self.lib.lgh_internal_energy(self.h, _ptr(e), ctypes.byref(v)))

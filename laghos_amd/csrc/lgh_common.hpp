@@ -198,6 +198,7 @@ struct lgh_ctx
    void *order;          // lgh::MeshOrder (lgh_order.hip)
    unsigned long mass_gen; // counts changes of the mass data / Jacobi diagonal (the velocity solve keeps copies in its own numbering)
    double *me_fac;       // 1D: NE * L1D^2, Cholesky factors of the zone mass matrices Me(z) of the energy solve (lgh_1d.hip)
+   unsigned long long *fp_dev; // lgh_vec_fingerprint (lgh_fingerprint.hip): the two words of the result and the workgroups' partial words, allocated on first use
 };
 
 namespace lgh

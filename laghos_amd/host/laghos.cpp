@@ -10,6 +10,7 @@
 // Exposed both as the `laghos` executable and as C entry points
 // (laghos_sim_*) that bench.py drives through ctypes.
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -26,6 +27,7 @@
 #include "laghos_solver.hpp"
 #include "sedov_exact.hpp"
 #include "vtk_output.hpp"
+#include "checkpoint.hpp"
 
 using namespace laghos;
 
@@ -68,6 +70,11 @@ struct Options
    // reference option: the reference has no choice in the matter.
    std::string renumber = "none";
    int renumber_seed = 1;
+   // checkpoint / restart (checkpoint.hpp; the reference has none)
+   int ckpt_steps = 0;             // -ckpt N: a checkpoint after every accepted step with ti % N == 0 and after the last one (0: none)
+   int ckpt_keep = 2;              // -ckpt-keep K: pieces of this run kept per rank (0: all)
+   std::string restart;            // -restart PATH: a checkpoint stem, or "latest" (<basename>_restart/latest)
+   bool fingerprint = false;       // -fp: rank 0 prints the state fingerprint after the last step and per checkpoint
 };
 
 bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
@@ -96,6 +103,28 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
       OPT_INT("-cgm", "--cg-max-steps", cg_max_iter) OPT_INT("-ms", "--max-steps", max_tsteps)
       OPT_INT("-vs", "--visualization-steps", vis_steps) OPT_INT("-dev", "--dev", dev)
       OPT_INT("-renumber-seed", "--renumber-seed", renumber_seed)
+      if (a == "-ckpt" || a == "--checkpoint-steps")
+      {
+         if (!(v = need(i))) { return false; }
+         o.ckpt_steps = std::atoi(v);
+         if (o.ckpt_steps < 1) { err = "-ckpt / --checkpoint-steps must be at least 1, got " + std::string(v); return false; }
+         continue;
+      }
+      if (a == "-ckpt-keep" || a == "--checkpoint-keep")
+      {
+         if (!(v = need(i))) { return false; }
+         o.ckpt_keep = std::atoi(v);
+         if (o.ckpt_keep < 0) { err = "-ckpt-keep / --checkpoint-keep must be 0 (keep all) or more, got " + std::string(v); return false; }
+         continue;
+      }
+      if (a == "-restart" || a == "--restart")
+      {
+         if (!(v = need(i))) { return false; }
+         o.restart = v;
+         if (o.restart.empty()) { err = "-restart needs a checkpoint stem or the word latest"; return false; }
+         continue;
+      }
+      if (a == "-fp" || a == "--fingerprint") { o.fingerprint = true; continue; }
 #undef OPT_INT
 #undef OPT_DBL
       if (a == "-pa" || a == "--partial-assembly") { o.p_assembly = true; continue; }
@@ -273,6 +302,14 @@ struct laghos_sim
    Vector pv_rho, pv_dev;
    std::vector<double> pv_host;
    double pv_seconds[3] = {0, 0, 0}; // density + sampling (GPU), device-to-host copy, file write
+   // -ckpt / -restart: the fingerprint of the set-up arrays, the pieces this run wrote (oldest first; -ckpt-keep removes from
+   // this list only), scratch, and where the time of a checkpoint goes
+   unsigned long long setup_fp[2] = {0, 0};
+   std::vector<std::string> ckpt_mine;
+   std::vector<double> ckpt_host;
+   int ckpt_count = 0;
+   double ckpt_seconds[3] = {0, 0, 0}; // fingerprint (GPU), device-to-host copy, host fingerprint + file write
+   int steps_at_start = 0;             // RK steps the checkpoint of a restart had taken: timing / FOM cover the restarted segment
 };
 
 // One `-paraview` dump of the state at cycle `cycle` (laghos.cpp:691-701, :845-871): density, lattice values on the GPU, one
@@ -320,6 +357,126 @@ static bool DumpParaview(laghos_sim *s, int cycle, const Vector *rho = nullptr)
       std::fprintf(stderr, "%s\n", s->error.c_str());
    }
    return ok;
+}
+
+static std::string Hex32(const unsigned long long fp[2])
+{
+   char buf[40];
+   std::snprintf(buf, sizeof(buf), "%016llX%016llX", fp[0], fp[1]);
+   return buf;
+}
+
+static bool SimFail(laghos_sim *s, const std::string &msg)
+{
+   s->error = msg;
+   std::fprintf(stderr, "laghos: %s\n", msg.c_str());
+   return false;
+}
+
+// The fingerprint of this rank's state (own, lgh_vec_fingerprint at offset 0) and of the whole run (all): on one rank the
+// same two words; on several ranks the two words of every rank are gathered (lgh_allreduce sums of 32-bit halves, every
+// rank contributing its own slots: exact in doubles) and `all` is the host fingerprint of the 2 * nranks words in rank
+// order.  Collective on several ranks.
+static bool StateFingerprint(laghos_sim *s, unsigned long long own[2], unsigned long long all[2])
+{
+   const Options &o = s->opt;
+   auto &hydro = *s->hydro;
+   if (lgh_vec_fingerprint(hydro.Context(), s->S.Read(), s->S.Size(), 0ULL, own) != 0)
+   {
+      return SimFail(s, std::string("lgh_vec_fingerprint: ") + lgh_last_error());
+   }
+   all[0] = own[0];
+   all[1] = own[1];
+   if (o.nranks > 1)
+   {
+      std::vector<unsigned long long> w(2 * (size_t)o.nranks, 0ULL);
+      for (int r = 0; r < o.nranks; r++)
+      {
+         for (int k = 0; k < 2; k++)
+         {
+            for (int half = 0; half < 2; half++)
+            {
+               const double mine = (r == o.rank) ? (double)((own[k] >> (32 * half)) & 0xFFFFFFFFULL) : 0.0;
+               w[2 * (size_t)r + k] |= (unsigned long long)hydro.AllReduce(mine, 0) << (32 * half);
+            }
+         }
+      }
+      all[0] = all[1] = 0ULL;
+      FingerprintWords(w.data(), (long)w.size(), 0ULL, all);
+   }
+   return true;
+}
+
+// One checkpoint of the state after accepted step ti_now: fingerprint on the device, one copy to the host, the host fingerprint of the copy (the two must agree), then
+// the file of this rank, CheckpointPiece(stem).  On several ranks an all-reduce follows: every rank learns whether all
+// pieces are complete.  Collective.
+static bool WriteCheckpointPiece(laghos_sim *s, const std::string &stem, int ti_now, std::string *piece_out)
+{
+   using clk = std::chrono::steady_clock;
+   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+   const Options &o = s->opt;
+   const Discretization &d = *s->disc;
+   auto &hydro = *s->hydro;
+   const clk::time_point t0 = clk::now();
+   unsigned long long own[2], all[2];
+   if (!StateFingerprint(s, own, all)) { return false; }
+   const clk::time_point t1 = clk::now();
+   s->S.ToHost(s->ckpt_host);
+   const clk::time_point t2 = clk::now();
+   unsigned long long hfp[2] = {0ULL, 0ULL};
+   FingerprintWords(s->ckpt_host.data(), (long)s->ckpt_host.size(), 0ULL, hfp);
+   bool ok = true;
+   std::string err;
+   if (hfp[0] != own[0] || hfp[1] != own[1])
+   {
+      ok = false;
+      err = "checkpoint: the state gives " + Hex32(own) + " on the device and " + Hex32(hfp) + " after the copy to the host: not written";
+   }
+   const std::string piece = CheckpointPiece(stem, o.nranks, o.rank);
+   if (ok)
+   {
+      CheckpointHeader h;
+      h.dim = d.dim; h.problem = o.problem; h.order_v = o.order_v; h.order_e = o.order_e; h.Q1D = d.tab.Q1D;
+      h.NE = d.NE; h.global_NE = d.global_NE; h.N = d.N;
+      h.nranks = o.nranks; h.rank = o.rank;
+      for (int a = 0; a < 3; a++) { h.pgrid[a] = d.part.pgrid[a]; }
+      h.ode_solver = o.ode_solver_type; h.cfl = o.cfl; h.cg_tol = o.cg_tol; h.cg_max_iter = o.cg_max_iter;
+      h.t = s->t; h.dt = s->dt; h.ti = ti_now; h.steps = s->steps; h.repeats = s->repeats;
+      h.energy_init = s->energy_init; h.checks = s->checks; h.checks_ok = s->checks_ok ? 1 : 0;
+      h.setup_fp[0] = s->setup_fp[0]; h.setup_fp[1] = s->setup_fp[1];
+      std::vector<long long> cyc(s->pv_cycles.begin(), s->pv_cycles.end());
+      ok = WriteCheckpoint(piece, h, s->ckpt_host.data(), (long)s->ckpt_host.size(), s->pv_times.data(), cyc.data(), (long)cyc.size(), err) == CKPT_OK;
+   }
+   const clk::time_point t3 = clk::now();
+   s->ckpt_seconds[0] += secs(t0, t1);
+   s->ckpt_seconds[1] += secs(t1, t2);
+   s->ckpt_seconds[2] += secs(t2, t3);
+   const double complete = hydro.AllReduce(ok ? 1.0 : 0.0, 0);
+   if (!ok) { return SimFail(s, err); }
+   if (o.nranks > 1 && complete != (double)o.nranks) { return SimFail(s, "checkpoint " + stem + ": another rank could not write its piece"); }
+   s->ckpt_count++;
+   if (o.fingerprint && o.rank == 0) { std::cout << "State fingerprint: " << Hex32(all) << " (cycle " << ti_now << ")" << std::endl; }
+   if (piece_out) { *piece_out = piece; }
+   return true;
+}
+
+// The `-ckpt` checkpoint after accepted step ti_now: the pieces, then <basename>_restart/latest (rank 0, once all pieces are
+// complete), then -ckpt-keep: each rank removes its own older pieces beyond the K newest, from the list of what this run wrote.
+static bool PeriodicCheckpoint(laghos_sim *s, int ti_now)
+{
+   const Options &o = s->opt;
+   const std::string dir = CheckpointDir(o.basename), name = CheckpointName(ti_now);
+   std::string piece;
+   if (!WriteCheckpointPiece(s, dir + "/" + name, ti_now, &piece)) { return false; }
+   if (o.rank == 0 && !WriteLatest(dir, name)) { return SimFail(s, "cannot write " + dir + "/latest"); }
+   s->ckpt_mine.erase(std::remove(s->ckpt_mine.begin(), s->ckpt_mine.end(), piece), s->ckpt_mine.end()); // (written again: listed once)
+   s->ckpt_mine.push_back(piece);
+   while (o.ckpt_keep > 0 && (int)s->ckpt_mine.size() > o.ckpt_keep)
+   {
+      (void)std::remove(s->ckpt_mine.front().c_str());
+      s->ckpt_mine.erase(s->ckpt_mine.begin());
+   }
+   return true;
 }
 
 extern "C"
@@ -398,6 +555,55 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
    }
    std::vector<double> S0, rho0_l2, gamma, rho0_q;
    d.InitialState(S0, rho0_l2, gamma, rho0_q);
+   // -restart: read and verify the file, compare it with what THIS command line sets up (setup_fp: mesh, refinement, orders,
+   // problem, -E0, numbering and partition all end up in these arrays) - host work, before any GPU call
+   const bool restarting = !o.restart.empty();
+   Checkpoint ck;
+   std::string ck_piece;
+   if (restarting || o.ckpt_steps > 0) { SetupFingerprint(S0, rho0_l2, gamma, rho0_q, d.h1map, s->setup_fp); }
+   if (restarting)
+   {
+      std::string stem = o.restart, err;
+      if (stem == "latest")
+      {
+         std::string name;
+         const std::string dir = CheckpointDir(o.basename);
+         if (!ReadLatest(dir, name))
+         {
+            std::fprintf(stderr, "laghos: -restart latest: cannot read %s/latest\n", dir.c_str());
+            return nullptr;
+         }
+         stem = dir + "/" + name;
+      }
+      ck_piece = CheckpointPiece(stem, nranks, rank);
+      if (ReadCheckpoint(ck_piece, ck, err) != CKPT_OK)
+      {
+         std::fprintf(stderr, "laghos: -restart: %s\n", err.c_str());
+         return nullptr;
+      }
+      const CheckpointHeader &h = ck.h;
+      std::string why;
+      if (h.nranks != nranks || h.rank != rank)
+      {
+         why = "it is the piece of rank " + std::to_string(h.rank) + " of " + std::to_string(h.nranks) + ", this is rank " + std::to_string(rank) + " of " +
+               std::to_string(nranks) + " (a restart onto another rank count is not supported)";
+      }
+      else if (h.pgrid[0] != d.part.pgrid[0] || h.pgrid[1] != d.part.pgrid[1] || h.pgrid[2] != d.part.pgrid[2]) { why = "it was written on another process grid"; }
+      else if (h.setup_fp[0] != s->setup_fp[0] || h.setup_fp[1] != s->setup_fp[1])
+      {
+         why = "setup_fp: its run was set up differently (mesh, refinement, orders, problem, -E0, numbering or partition): the file has " + Hex32(h.setup_fp) +
+               ", this command line gives " + Hex32(s->setup_fp);
+      }
+      else if (h.state_words != (long)S0.size() || h.dim != d.dim || h.NE != d.NE || h.N != d.N || h.global_NE != d.global_NE)
+      {
+         why = "sizes: its state has " + std::to_string(h.state_words) + " words, this run's " + std::to_string(S0.size());
+      }
+      if (!why.empty())
+      {
+         std::fprintf(stderr, "laghos: -restart: checkpoint %s refused: %s\n", ck_piece.c_str(), why.c_str());
+         return nullptr;
+      }
+   }
    s->hydro.reset(new hydrodynamics::LagrangianHydroOperator(d, S0, rho0_l2, gamma, rho0_q, o.cfl, o.cg_tol,
                                                              o.cg_max_iter, o.dev, nccl_id));
    switch (o.ode_solver_type)
@@ -420,6 +626,56 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
       const char *senv = std::getenv("LGH_STORE_STRESS");
       const bool keep_in_registers = o.ode_solver_type != 7 && d.dim == 3 && !o.store_stress && !(senv && senv[0] == '1');
       if (keep_in_registers) { LGH_VERIFY(lgh_qupdate_store_stress(s->hydro->Context(), 0)); }
+   }
+   if (restarting)
+   {
+      // the set-up data came from S0 as in every run; the state now comes from the file and must have arrived in HBM intact
+      const CheckpointHeader &h = ck.h;
+      s->S.FromHost(ck.S);
+      s->S_old.SetSize(s->S.Size());
+      s->ode->Init(*s->hydro);
+      unsigned long long dfp[2];
+      if (lgh_vec_fingerprint(s->hydro->Context(), s->S.Read(), s->S.Size(), 0ULL, dfp) != 0 || dfp[0] != h.state_fp[0] || dfp[1] != h.state_fp[1])
+      {
+         std::fprintf(stderr, "laghos: -restart: checkpoint %s: the state on the device gives %s, state_fp is %s\n", ck_piece.c_str(),
+                      Hex32(dfp).c_str(), Hex32(h.state_fp).c_str());
+         return nullptr;
+      }
+      // the quadrature data current for S, as the end of step ti left it in the uninterrupted run (the estimate itself is not
+      // needed: dt comes from the file)
+      s->hydro->ResetTimeStepEstimate();
+      (void)s->hydro->GetTimeStepEstimate(s->S);
+      s->t = h.t; s->dt = h.dt; s->ti = h.ti + 1; s->steps = h.steps; s->repeats = h.repeats;
+      s->steps_at_start = h.steps;
+      s->energy_init = h.energy_init; s->checks = h.checks; s->checks_ok = h.checks_ok != 0;
+      s->pv_times = ck.pv_times;
+      s->pv_cycles.assign(ck.pv_cycles.begin(), ck.pv_cycles.end());
+      if (nranks > 1) // pieces of different checkpoints?
+      {
+         const double ti_min = s->hydro->AllReduce((double)h.ti, 1), ti_max = -s->hydro->AllReduce(-(double)h.ti, 1);
+         const double t_min = s->hydro->AllReduce(h.t, 1), t_max = -s->hydro->AllReduce(-h.t, 1);
+         if (ti_min != ti_max || t_min != t_max)
+         {
+            std::fprintf(stderr, "laghos: -restart: checkpoint %s refused: the ranks read pieces of different checkpoints (cycles %d .. %d)\n",
+                         ck_piece.c_str(), (int)ti_min, (int)ti_max);
+            return nullptr;
+         }
+      }
+      if (rank == 0)
+      {
+         if (h.ode_solver != o.ode_solver_type) { std::cout << "Restart: -s was " << h.ode_solver << " in the checkpoint, continuing with " << o.ode_solver_type << std::endl; }
+         if (h.cfl != o.cfl) { std::cout << "Restart: -cfl was " << h.cfl << " in the checkpoint, continuing with " << o.cfl << std::endl; }
+         if (h.cg_tol != o.cg_tol) { std::cout << "Restart: -cgt was " << h.cg_tol << " in the checkpoint, continuing with " << o.cg_tol << std::endl; }
+         if (h.cg_max_iter != o.cg_max_iter) { std::cout << "Restart: -cgm was " << h.cg_max_iter << " in the checkpoint, continuing with " << o.cg_max_iter << std::endl; }
+      }
+      if (root)
+      {
+         std::cout << "Restarting from " << ck_piece << ": cycle " << h.ti << ", t = " << std::setprecision(17) << s->t << ", dt = " << s->dt
+                   << std::setprecision(6) << std::endl;
+      }
+      // a checkpoint written after the last step: nothing is left to do
+      if (s->t >= o.t_final || (o.max_tsteps >= 0 && s->steps > o.max_tsteps)) { s->last_step = true; }
+      return s.release();
    }
    s->S.FromHost(S0);
    s->S_old.SetSize(s->S.Size());
@@ -473,6 +729,9 @@ int laghos_sim_step(laghos_sim *s)
          s->repeats++;
          if (root) { std::cout << "Repeating step " << s->ti << std::endl; }
          if (s->steps < o.max_tsteps) { s->last_step = false; }
+         // The run ends here when its last step was a repeated one (the loop of laghos.cpp:742-778 has no step left to take):
+         // the state is that of the last accepted step again, with the shortened dt - the checkpoint "after the last step"
+         if (s->last_step && o.ckpt_steps > 0 && s->ti > 1 && !PeriodicCheckpoint(s, s->ti - 1)) { return -1; }
          continue;
       }
       else if (dt_est > 1.25 * s->dt) { s->dt *= 1.02; }
@@ -510,6 +769,7 @@ int laghos_sim_step(laghos_sim *s)
          const double e_norm = hydro.ENorm(s->S);
          s->checks_ok = CheckNorm(o.dim, o.problem, s->ti, e_norm, s->checks) && s->checks_ok;
       }
+      if (o.ckpt_steps > 0 && (s->last_step || (s->ti % o.ckpt_steps) == 0) && !PeriodicCheckpoint(s, s->ti)) { return -1; }
       s->ti++;
       return 1;
    }
@@ -543,6 +803,28 @@ double laghos_sim_time(laghos_sim *s) { return s->t; }
 double laghos_sim_dt(laghos_sim *s) { return s->dt; }
 int laghos_sim_steps(laghos_sim *s) { return s->steps; }   // RK steps taken incl. repeated ones
 int laghos_sim_ti(laghos_sim *s) { return s->ti - 1; }     // accepted steps
+int laghos_sim_repeats(laghos_sim *s) { return s->repeats; } // repeated steps so far
+void laghos_sim_checks(laghos_sim *s, int *out) { out[0] = s->checks; out[1] = s->checks_ok ? 1 : 0; } // -chk: cycles compared, all passed
+// The state fingerprint `-fp` prints: out[0] = sum, out[1] = xor word (include/lgh_fingerprint.h).  One rank: lgh_vec_fingerprint
+// of S at offset 0; several ranks: the rank-ordered combination (collective).  0 = ok.
+int laghos_sim_fingerprint(laghos_sim *s, unsigned long long *out)
+{
+   unsigned long long own[2];
+   return StateFingerprint(s, own, out) ? 0 : -1;
+}
+// A checkpoint of the sim as it stands between two steps, to the stem given (rank r of several writes <stem>.<r>; collective).
+// No `latest`, no -ckpt-keep.  0 = written; laghos_sim_error() has the message otherwise.
+int laghos_sim_write_checkpoint(laghos_sim *s, const char *stem)
+{
+   if (!s || !stem || !*stem) { return -1; }
+   if (s->setup_fp[0] == 0 && s->setup_fp[1] == 0)
+   {
+      std::vector<double> S0, rho0_l2, gamma, rho0_q;
+      s->disc->InitialState(S0, rho0_l2, gamma, rho0_q);
+      SetupFingerprint(S0, rho0_l2, gamma, rho0_q, s->disc->h1map, s->setup_fp);
+   }
+   return WriteCheckpointPiece(s, stem, s->ti - 1, nullptr) ? 0 : -1;
+}
 double laghos_sim_enorm(laghos_sim *s) { return s->hydro->ENorm(s->S); }
 double laghos_sim_energy(laghos_sim *s) { return s->hydro->InternalEnergy(s->S) + s->hydro->KineticEnergy(s->S); }
 void laghos_sim_sync(laghos_sim *s) { s->hydro->Sync(); }
@@ -629,6 +911,60 @@ int laghos_host_write_pvtu(const char *dir, int cycle, double time, int nranks) 
 int laghos_host_write_pvd(const char *pvd_path, const char *rel_dir, int n, const double *times, const int *cycles, int nranks)
 {
    return WritePvd(pvd_path, rel_dir, std::vector<double>(times, times + n), std::vector<int>(cycles, cycles + n), nranks) ? 0 : -1;
+}
+// host-only: the checkpoint writer and reader (checkpoint.hpp); 0 = done, else a CheckpointError with its message in msg.
+//   ints[24]: dim problem order_v order_e Q1D | NE global_NE N | nranks rank pgrid[3] | ode_solver cg_max_iter | ti steps repeats |
+//             checks checks_ok | header_bytes state_words paraview_dumps (the last three: set by the reader, ignored by the writer)
+//   dbls[5]:  cfl cg_tol t dt energy_init;   fps[4]: setup_fp[2] state_fp[2] (state_fp: set by the reader, the writer computes it)
+static void CkptPack(const CheckpointHeader &h, long *ints, double *dbls, unsigned long long *fps)
+{
+   const long v[24] = {h.dim, h.problem, h.order_v, h.order_e, h.Q1D, h.NE, h.global_NE, h.N, h.nranks, h.rank, h.pgrid[0], h.pgrid[1], h.pgrid[2],
+                       h.ode_solver, h.cg_max_iter, h.ti, h.steps, h.repeats, h.checks, h.checks_ok, h.header_bytes, h.state_words, h.pv_dumps, 0};
+   std::copy(v, v + 24, ints);
+   dbls[0] = h.cfl; dbls[1] = h.cg_tol; dbls[2] = h.t; dbls[3] = h.dt; dbls[4] = h.energy_init;
+   fps[0] = h.setup_fp[0]; fps[1] = h.setup_fp[1]; fps[2] = h.state_fp[0]; fps[3] = h.state_fp[1];
+}
+static void CkptMsg(const std::string &err, char *msg, int msg_len)
+{
+   if (msg && msg_len > 0) { std::snprintf(msg, (size_t)msg_len, "%s", err.c_str()); }
+}
+int laghos_host_write_checkpoint(const char *path, const long *ints, const double *dbls, const unsigned long long *setup_fp, const double *S, long nS,
+                                 const double *pv_times, const long long *pv_cycles, long npv, char *msg, int msg_len)
+{
+   CheckpointHeader h;
+   h.dim = (int)ints[0]; h.problem = (int)ints[1]; h.order_v = (int)ints[2]; h.order_e = (int)ints[3]; h.Q1D = (int)ints[4];
+   h.NE = ints[5]; h.global_NE = ints[6]; h.N = ints[7];
+   h.nranks = (int)ints[8]; h.rank = (int)ints[9];
+   for (int a = 0; a < 3; a++) { h.pgrid[a] = (int)ints[10 + a]; }
+   h.ode_solver = (int)ints[13]; h.cg_max_iter = (int)ints[14]; h.ti = (int)ints[15]; h.steps = (int)ints[16]; h.repeats = (int)ints[17];
+   h.checks = (int)ints[18]; h.checks_ok = (int)ints[19];
+   h.cfl = dbls[0]; h.cg_tol = dbls[1]; h.t = dbls[2]; h.dt = dbls[3]; h.energy_init = dbls[4];
+   h.setup_fp[0] = setup_fp[0]; h.setup_fp[1] = setup_fp[1];
+   std::string err;
+   const int rc = WriteCheckpoint(path, h, S, nS, pv_times, pv_cycles, npv, err);
+   CkptMsg(err, msg, msg_len);
+   return rc;
+}
+// S (capS doubles), pv_times / pv_cycles (cap_pv entries) and the header arrays are written only when every check has passed
+int laghos_host_read_checkpoint(const char *path, long *ints, double *dbls, unsigned long long *fps, double *S, long capS, double *pv_times,
+                                long long *pv_cycles, long cap_pv, char *msg, int msg_len)
+{
+   Checkpoint c;
+   std::string err;
+   int rc = ReadCheckpoint(path, c, err);
+   if (rc == CKPT_OK && ((long)c.S.size() > capS || (long)c.pv_times.size() > cap_pv))
+   {
+      rc = CKPT_ERR_CAPACITY;
+      err = std::string("checkpoint ") + path + ": capacity: " + std::to_string(c.S.size()) + " state words and " + std::to_string(c.pv_times.size()) +
+            " dumps do not fit the caller's arrays";
+   }
+   CkptMsg(err, msg, msg_len);
+   if (rc != CKPT_OK) { return rc; }
+   CkptPack(c.h, ints, dbls, fps);
+   std::copy(c.S.begin(), c.S.end(), S);
+   std::copy(c.pv_times.begin(), c.pv_times.end(), pv_times);
+   std::copy(c.pv_cycles.begin(), c.pv_cycles.end(), pv_cycles);
+   return CKPT_OK;
 }
 // Builds the discretisation of one rank and returns sizes; arrays are copied out
 // by laghos_host_disc_get.  kind: 0 h1map, 1 S0, 2 rho0_l2, 3 gamma, 4 rho0_q,
@@ -730,7 +1066,13 @@ int laghos_main(int argc, const char *const *argv)
    int rc;
    while ((rc = laghos_sim_step(s)) == 1) {}
    if (rc < 0) { laghos_sim_destroy(s); return 1; }
-   int steps = s->steps * s->ode->Stages(); // laghos.cpp:928-935
+   if (o.fingerprint)
+   {
+      unsigned long long fp[2];
+      if (laghos_sim_fingerprint(s, fp) != 0) { laghos_sim_destroy(s); return 1; }
+      std::cout << "State fingerprint: " << Hex32(fp) << " (cycle " << s->ti - 1 << ")" << std::endl;
+   }
+   int steps = (s->steps - s->steps_at_start) * s->ode->Stages(); // laghos.cpp:928-935 (a restart: the steps of this segment, as the timers)
    s->hydro->PrintTimingData(true, steps, o.fom);
    const double energy_final = laghos_sim_energy(s);
    std::cout << std::endl;
@@ -740,6 +1082,11 @@ int laghos_main(int argc, const char *const *argv)
    {
       std::cout << "ParaView dumps: " << s->pv_cycles.size() << " (sample " << s->pv_seconds[0] << " s, copy " << s->pv_seconds[1]
                 << " s, write " << s->pv_seconds[2] << " s) -> " << o.basename << ".pvd" << std::endl;
+   }
+   if (o.ckpt_steps > 0 && !o.quiet)
+   {
+      std::cout << "Checkpoints: " << s->ckpt_count << " (fingerprint " << s->ckpt_seconds[0] << " s, copy " << s->ckpt_seconds[1] << " s, write "
+                << s->ckpt_seconds[2] << " s) -> " << CheckpointDir(o.basename) << std::endl;
    }
    int ret = 0;
    if (o.check_exact_sedov)

@@ -65,6 +65,20 @@ def load():
         L.laghos_host_write_pvtu.argtypes = [ctypes.c_char_p, I, D, I]
         L.laghos_host_write_pvd.restype = I
         L.laghos_host_write_pvd.argtypes = [ctypes.c_char_p, ctypes.c_char_p, I, P, P, I]
+        ULL = ctypes.c_ulonglong
+        L.laghos_sim_repeats.restype = I
+        L.laghos_sim_repeats.argtypes = [P]
+        L.laghos_sim_checks.argtypes = [P, ctypes.POINTER(I)]
+        L.laghos_sim_error.restype = ctypes.c_char_p
+        L.laghos_sim_error.argtypes = [P]
+        L.laghos_sim_fingerprint.restype = I
+        L.laghos_sim_fingerprint.argtypes = [P, ctypes.POINTER(ULL)]
+        L.laghos_sim_write_checkpoint.restype = I
+        L.laghos_sim_write_checkpoint.argtypes = [P, ctypes.c_char_p]
+        L.laghos_host_write_checkpoint.restype = I
+        L.laghos_host_write_checkpoint.argtypes = [ctypes.c_char_p, P, P, P, P, Lg, P, P, Lg, ctypes.c_char_p, I]
+        L.laghos_host_read_checkpoint.restype = I
+        L.laghos_host_read_checkpoint.argtypes = [ctypes.c_char_p, P, P, P, P, Lg, P, P, Lg, ctypes.c_char_p, I]
         L.laghos_host_disc_create.restype = P
         L.laghos_host_disc_create.argtypes = [ctypes.c_char_p, I, I, I, I, D, I, I]
         L.laghos_host_disc_create_renumbered.restype = P
@@ -158,6 +172,32 @@ class Sim:
         self.L.laghos_sim_get_state(self.h, out.ctypes.data)
         return out
 
+    @property
+    def repeats(self):
+        """repeated steps so far"""
+        return self.L.laghos_sim_repeats(self.h)
+
+    def checks(self):
+        """`-chk`: (cycles compared so far, all of them passed)"""
+        c = (ctypes.c_int * 2)()
+        self.L.laghos_sim_checks(self.h, c)
+        return c[0], bool(c[1])
+
+    def fingerprint(self):
+        """The state fingerprint `-fp` prints, as (sum word, xor word): on one rank lgh_vec_fingerprint of S at offset 0,
+        on several ranks the rank-ordered combination (every rank calls it)."""
+        out = (ctypes.c_ulonglong * 2)()
+        if self.L.laghos_sim_fingerprint(self.h, out) != 0:
+            raise RuntimeError(self.L.laghos_sim_error(self.h).decode())
+        return int(out[0]), int(out[1])
+
+    def checkpoint(self, stem):
+        """A checkpoint of the sim as it stands between two steps: the file `stem` (`stem.<rank>` on several ranks, every
+        rank calls it), which `-restart stem` reads.  Returns the path of this rank's piece."""
+        if self.L.laghos_sim_write_checkpoint(self.h, str(stem).encode()) != 0:
+            raise RuntimeError(self.L.laghos_sim_error(self.h).decode())
+        return str(stem)
+
 
 def host_partition(dim, nx, ny, nz, nranks):
     """Process grid laghos::Partition picks for an nx x ny x nz zone grid (None: not evenly divisible)."""
@@ -221,6 +261,66 @@ def host_write_pvd(path, rel_dir, times, cycles, nranks=1):
     assert t.size == c.size
     if load().laghos_host_write_pvd(str(path).encode(), str(rel_dir).encode(), int(t.size), t.ctypes.data, c.ctypes.data, nranks) != 0:
         raise RuntimeError(f"cannot write {path}")
+
+
+CKPT_INT_KEYS = ("dim", "problem", "order_v", "order_e", "Q1D", "NE", "global_NE", "N", "nranks", "rank", "pgrid0", "pgrid1", "pgrid2",
+                 "ode_solver", "cg_max_iter", "ti", "steps", "repeats", "checks", "checks_ok", "header_bytes", "state_words",
+                 "paraview_dumps")
+CKPT_DBL_KEYS = ("cfl", "cg_tol", "t", "dt", "energy_init")
+
+
+class CheckpointError(RuntimeError):
+    """A checkpoint that was refused: .code is the CheckpointError of checkpoint.hpp, the text names the file and the check."""
+
+    def __init__(self, code, msg):
+        super().__init__(msg)
+        self.code = code
+
+
+def fingerprint_host(words, offset=0):
+    """lgh_fingerprint_host (exported by the HIP library, needs no GPU): (sum word, xor word) of the 64-bit words of a
+    contiguous float64 / int64 / uint64 array, the first at position `offset`."""
+    from . import _lib as hip_lib
+    a = np.ascontiguousarray(words)
+    assert a.dtype.itemsize == 8, a.dtype
+    out = (ctypes.c_ulonglong * 2)()
+    hip_lib.check(hip_lib.load().lgh_fingerprint_host(ctypes.c_void_p(a.ctypes.data) if a.size else None, int(a.size), int(offset), out))
+    return int(out[0]), int(out[1])
+
+
+def host_write_checkpoint(path, header, S, pv_times=(), pv_cycles=()):
+    """checkpoint.hpp WriteCheckpoint through the host probe: header = dict of CKPT_INT_KEYS / CKPT_DBL_KEYS (missing keys 0)
+    and "setup_fp" = (word, word); S float64, pv_times float64, pv_cycles int64."""
+    L = load()
+    ints = np.array([int(header.get(k, 0)) for k in CKPT_INT_KEYS] + [0], dtype=np.int64)
+    dbls = np.array([float(header.get(k, 0.0)) for k in CKPT_DBL_KEYS], dtype=np.float64)
+    fp = np.array(header.get("setup_fp", (0, 0)), dtype=np.uint64)
+    S, t = _f64(S), _f64(pv_times)
+    c = np.ascontiguousarray(pv_cycles, dtype=np.int64)
+    assert t.size == c.size
+    msg = ctypes.create_string_buffer(1024)
+    rc = L.laghos_host_write_checkpoint(str(path).encode(), ints.ctypes.data, dbls.ctypes.data, fp.ctypes.data, S.ctypes.data, int(S.size),
+                                        t.ctypes.data, c.ctypes.data, int(t.size), msg, len(msg))
+    if rc != 0:
+        raise CheckpointError(rc, msg.value.decode())
+
+
+def host_read_checkpoint(path, S, pv_times, pv_cycles):
+    """checkpoint.hpp ReadCheckpoint through the host probe, into the caller's arrays (float64, float64, int64; at least as
+    large as the file's), which stay untouched when the file is refused (CheckpointError).  Returns the header as a dict."""
+    L = load()
+    assert S.dtype == np.float64 and pv_times.dtype == np.float64 and pv_cycles.dtype == np.int64
+    assert S.flags.c_contiguous and pv_times.flags.c_contiguous and pv_cycles.flags.c_contiguous
+    ints, dbls, fps = np.zeros(24, np.int64), np.zeros(5, np.float64), np.zeros(4, np.uint64)
+    msg = ctypes.create_string_buffer(1024)
+    rc = L.laghos_host_read_checkpoint(str(path).encode(), ints.ctypes.data, dbls.ctypes.data, fps.ctypes.data, S.ctypes.data, int(S.size),
+                                       pv_times.ctypes.data, pv_cycles.ctypes.data, int(min(pv_times.size, pv_cycles.size)), msg, len(msg))
+    if rc != 0:
+        raise CheckpointError(rc, msg.value.decode())
+    h = dict(zip(CKPT_INT_KEYS, (int(v) for v in ints)))
+    h.update(zip(CKPT_DBL_KEYS, (float(v) for v in dbls)))
+    h["setup_fp"], h["state_fp"] = (int(fps[0]), int(fps[1])), (int(fps[2]), int(fps[3]))
+    return h
 
 
 def host_disc(mesh, rs, order_v, order_e, problem, blast_energy=1.0, nranks=1, rank=0, renumber=None, seed=1, zones=None):
