@@ -262,7 +262,15 @@ def test_smallmat_device():
     g.ctx.test_singular(3, g.ctx.to_dev(np.transpose(J, (0, 2, 1)).reshape(-1)), sv)
     g.ctx.sync()
     s = np.linalg.svd(J, compute_uv=False)
-    assert np.max(np.abs(sv.cpu().numpy() - s[:, 2]) / s[:, 0]) < 1e-10
+    # the family rule of test_gpu_smallmat_edges.py: max(1e-14, 4 e_oracle) s_max, e_oracle the oracle's worst error over
+    # s_max on these same matrices (both routines form J^T J: the error grows with the condition number, and the worst
+    # conditioned of 20 000 Gaussian matrices sets it)
+    from smallmat_cases import oracle_sv
+    e_oracle = np.max(np.abs(oracle_sv(3, J) - s[:, 2]) / s[:, 0])
+    e_device = np.max(np.abs(sv.cpu().numpy() - s[:, 2]) / s[:, 0])
+    print(f"singular value: device {e_device:.2e} oracle {e_oracle:.2e}")
+    assert e_device <= max(1e-14, 4 * e_oracle)
+    assert max(1e-14, 4 * e_oracle) < 1e-10  # (never weaker than the bar this assertion replaced)
     g.close()
 
 
