@@ -459,6 +459,23 @@ int lgh_test_vcg_merged_faces(lgh_ctx *ctx, unsigned char *mask, long *n_merged)
 int lgh_test_vcg_k2(lgh_ctx *ctx, int it, const double *y_E, double *r, double *d, double *x, const double den[3],
                     const double rz[3], const double rz_prev[3], const double alpha_prev[3], double rz_out[3],
                     int *deferred_x);
+/* The exact integer accumulators every (d, A d) and (r, z) of the lockstep velocity solve goes through (lgh_vcg.hpp), on
+ * their own: the probe's kernels call the solve's own device functions.  Host arrays in, host arrays out; synchronous;
+ * single rank.  E is the scale of the window, or - scale != NULL - exact_scale(*scale) taken on the device.
+ *   mode 0, split: one thread per addend v[i] (n of them): exact_add into zeroed accumulators; w_out[4 i + j] = limb j,
+ *           i_out[i] = 1 accepted / 0 refused (accumulators untouched).
+ *   mode 1, value: d_out[i] = exact_value of the limb words w_in[4 i .. 4 i + 3] under E (scale must be NULL).
+ *   mode 2, grid: n addends per component (v[k n + i], k < 3) over G workgroups of 256 threads as the tail of the slab K1
+ *           adds them (per-thread exact_add, wave_sum_i64, LDS, one atomic per word into shard blockIdx % 4, atomic or
+ *           into the flag word) into a cleared set; a second launch folds the set: w_out = its 56 raw words,
+ *           d_out[k] = exact_den, d_out[3 + k] = exact_fold, d_out[6 + k] = exact_fold_lanes (one full wavefront, word l
+ *           in lane l).  exact_den gets *scale, or a value whose exact_scale is E.
+ *   mode 3, wave: w_out[64 b + l] = what lane l of wavefront b gets from wave_sum_i64 of w_in[64 b .. 64 b + 63]
+ *           (n a multiple of 64).
+ *   mode 4, scale: i_out[i] = exact_scale(v[i]).
+ * Arguments a mode does not use may be NULL / 0. */
+int lgh_test_exact_sum(lgh_ctx *ctx, int mode, long n, int G, int E, const double *scale, const double *v,
+                       const long long *w_in, long long *w_out, double *d_out, int *i_out);
 /* halo pieces without the RCCL transport (tests emulate the exchange between
  * several contexts on one GPU): rank bookkeeping, pack into / combine from caller
  * buffers of 3*total doubles laid out as the send / receive buffers are. */

@@ -284,6 +284,50 @@ class Context:
                                        _dbl(al), _dbl(out), ctypes.byref(form)))
         return out, bool(form.value)
 
+    def _exact_sum(self, mode, n, G=0, E=0, scale=None, v=None, w_in=None, w_out=None, d_out=None, i_out=None):
+        llp, sc = ctypes.POINTER(ctypes.c_longlong), None if scale is None else np.array([scale], dtype=np.float64)
+        check(self.lib.lgh_test_exact_sum(
+            self.h, mode, n, int(G), int(E), None if sc is None else _dbl(sc), None if v is None else _dbl(v),
+            None if w_in is None else w_in.ctypes.data_as(llp), None if w_out is None else w_out.ctypes.data_as(llp),
+            None if d_out is None else _dbl(d_out), None if i_out is None else i_out.ctypes.data_as(_lib.c_int_p)))
+
+    def test_exact_split(self, v, E=0, scale=None):
+        """exact_add of every v[i] into zeroed accumulators (lgh_test_exact_sum, mode 0): (limbs int64 [n, 4], accepted bool [n])."""
+        v = _np_f64(v)
+        limbs, ok = np.zeros((v.size, 4), dtype=np.int64), np.zeros(v.size, dtype=np.int32)
+        self._exact_sum(0, v.size, E=E, scale=scale, v=v, w_out=limbs, i_out=ok)
+        return limbs, ok != 0
+
+    def test_exact_value(self, limbs, E):
+        """exact_value of every row of limbs [n, 4] under E (mode 1): float64 [n]."""
+        limbs = np.ascontiguousarray(limbs, dtype=np.int64).reshape(-1, 4)
+        out = np.zeros(limbs.shape[0])
+        self._exact_sum(1, limbs.shape[0], E=E, w_in=limbs, d_out=out)
+        return out
+
+    def test_exact_grid(self, v, G, E=0, scale=None):
+        """v [3, n] over G workgroups into a cleared set, then the three folds (mode 2):
+        (the set's raw words int64 [56], folds float64 [3 (exact_den, exact_fold, exact_fold_lanes), 3 components])."""
+        v = _np_f64(v)
+        assert v.ndim == 2 and v.shape[0] == 3
+        words, folds = np.zeros(56, dtype=np.int64), np.zeros(9)
+        self._exact_sum(2, v.shape[1], G=G, E=E, scale=scale, v=v, w_out=words, d_out=folds)
+        return words, folds.reshape(3, 3)
+
+    def test_wave_sum(self, words):
+        """wave_sum_i64 of every 64 words (mode 3): what each of the 64 lanes gets, int64, same shape."""
+        words = np.ascontiguousarray(words, dtype=np.int64)
+        out = np.zeros_like(words)
+        self._exact_sum(3, words.size, w_in=words, w_out=out)
+        return out
+
+    def test_exact_scale(self, rz):
+        """exact_scale of every rz[i] (mode 4): int32 [n]."""
+        rz = _np_f64(rz)
+        out = np.zeros(rz.size, dtype=np.int32)
+        self._exact_sum(4, rz.size, v=rz, i_out=out)
+        return out
+
     def mass_data_form(self):
         """'rank1' when the mass kernels read D[q, e] = W[q] s_e (one double per element), 'stored' otherwise."""
         f = ctypes.c_int(-1)

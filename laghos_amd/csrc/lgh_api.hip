@@ -1512,6 +1512,17 @@ int lgh_test_vcg_k2(lgh_ctx *c, int it, const double *y_E, double *r, double *d,
    if (rc) { return rc; }
    return vcg_test_k2(c, it, y_E, r, d, x, den, rz, rz_prev, alpha_prev, rz_out, deferred_x);
 }
+int lgh_test_exact_sum(lgh_ctx *c, int mode, long n, int G, int E, const double *scale, const double *v, const long long *w_in,
+                       long long *w_out, double *d_out, int *i_out)
+{
+   LGH_CHECK_ARG(c && mode >= 0 && mode <= 4 && n >= 1 && n <= (1L << 24) && E >= -1000 && E <= 1000);
+   LGH_CHECK_ARG(mode != 0 || (v && w_out && i_out));
+   LGH_CHECK_ARG(mode != 1 || (w_in && d_out && !scale));
+   LGH_CHECK_ARG(mode != 2 || (v && w_out && d_out && G >= 1 && G <= 1024));
+   LGH_CHECK_ARG(mode != 3 || (w_in && w_out && n % 64 == 0));
+   LGH_CHECK_ARG(mode != 4 || (v && i_out));
+   return vcg_test_exact_sum(c, mode, n, G, E, scale, v, w_in, w_out, d_out, i_out);
+}
 int lgh_force_mult_E(lgh_ctx *c, const double *sJit, const double *x_E, double *y_E)
 {
    LGH_CHECK_ARG(c && sJit && x_E && y_E);

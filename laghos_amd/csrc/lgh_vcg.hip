@@ -2887,6 +2887,161 @@ __global__ void vcg_test_put_rz_k(long long *set, double v0, double v1, double v
       if (!ok) { set[kLimbShards * kVC * kLimbs] = 1; }
    }
 }
+// Test hook (lgh_test_exact_sum): the exact accumulators of lgh_vcg.hpp on their own.  The kernels below call
+// exact_scale / exact_add / wave_sum_i64 / exact_value / exact_den / exact_fold / exact_fold_lanes themselves - what a
+// test sees through them is what K1 and K2 compute with.
+__global__ void __launch_bounds__(256)
+vcg_test_exact_split_k(const double *__restrict__ v, const long n, int E, const double *__restrict__ scale, long long *__restrict__ limbs, int *__restrict__ ok)
+{
+   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+   if (i >= n) { return; }
+   if (scale) { E = exact_scale(*scale); }
+   long long acc[kLimbs] = {0, 0, 0, 0};
+   ok[i] = exact_add(acc, v[i], E) ? 1 : 0;
+   for (int j = 0; j < kLimbs; j++) { limbs[kLimbs * i + j] = acc[j]; }
+}
+__global__ void __launch_bounds__(256)
+vcg_test_exact_value_k(const long long *__restrict__ limbs, const long n, const int E, double *__restrict__ out)
+{
+   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+   if (i >= n) { return; }
+   long long l4[kLimbs];
+   for (int j = 0; j < kLimbs; j++) { l4[j] = limbs[kLimbs * i + j]; }
+   out[i] = exact_value(l4, E);
+}
+__global__ void __launch_bounds__(256)
+vcg_test_exact_scale_k(const double *__restrict__ rz, const long n, int *__restrict__ E)
+{
+   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+   if (i < n) { E[i] = exact_scale(rz[i]); }
+}
+// one wavefront per 64 words; every lane's result is returned
+__global__ void __launch_bounds__(64)
+vcg_test_wave_sum_k(const long long *__restrict__ in, long long *__restrict__ out)
+{
+   const long i = (long)blockIdx.x * 64 + threadIdx.x;
+   out[i] = wave_sum_i64(in[i]);
+}
+// n addends per component (component k: v[k n + i]) over the workgroups of the grid, then what the tail of the slab K1
+// does with a lane's accumulators: wave_sum_i64, LDS, one atomic per word into the workgroup's shard, the flag word
+__global__ void __launch_bounds__(256)
+vcg_test_exact_grid_k(const double *__restrict__ v, const long n, int E, const double *__restrict__ scale, long long *__restrict__ set)
+{
+   constexpr int NW = 4;
+   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+   if (scale) { E = exact_scale(*scale); }
+   long long acc[kVC][kLimbs];
+   for (int k = 0; k < kVC; k++) { for (int j = 0; j < kLimbs; j++) { acc[k][j] = 0; } }
+   bool acc_bad = false;
+   for (long i = (long)blockIdx.x * 256 + tid; i < n; i += 256L * gridDim.x)
+   {
+      for (int k = 0; k < kVC; k++) { acc_bad = !exact_add(acc[k], v[(long)k * n + i], E) || acc_bad; }
+   }
+   __shared__ long long redi[NW][kVC * kLimbs];
+   __shared__ int redbad[NW];
+#pragma unroll
+   for (int k = 0; k < kVC; k++)
+   {
+#pragma unroll
+      for (int j = 0; j < kLimbs; j++)
+      {
+         const long long tot = wave_sum_i64(acc[k][j]);
+         if (lane == 0) { redi[wid][kLimbs * k + j] = tot; }
+      }
+   }
+   const bool anybad = __any(acc_bad);
+   if (lane == 0) { redbad[wid] = anybad ? 1 : 0; }
+   __syncthreads();
+   if (tid < kVC * kLimbs)
+   {
+      long long sum = 0;
+      for (int w = 0; w < NW; w++) { sum += redi[w][tid]; }
+      if (sum != 0) { (void)__hip_atomic_fetch_add(&set[(blockIdx.x % kLimbShards) * (kVC * kLimbs) + tid], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+   }
+   if (tid == kVC * kLimbs)
+   {
+      int bad = 0;
+      for (int w = 0; w < NW; w++) { bad |= redbad[w]; }
+      if (bad) { (void)__hip_atomic_fetch_or(&set[kLimbShards * kVC * kLimbs], 1LL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+   }
+}
+// the three folds of a set by one full wavefront: out[k] = exact_den, out[3 + k] = exact_fold, out[6 + k] = exact_fold_lanes
+__global__ void __launch_bounds__(64)
+vcg_test_exact_fold_k(const long long *__restrict__ set, int E, const double *__restrict__ scale, double rz, double *__restrict__ out)
+{
+   const int lane = threadIdx.x;
+   if (scale) { E = exact_scale(*scale); rz = *scale; }
+   const long long w = (lane <= kLimbShards * kVC * kLimbs) ? set[lane] : 0LL; // lane l holds word l
+   for (int k = 0; k < kVC; k++)
+   {
+      const double a = exact_den(set, k, rz), b = exact_fold(set, k, E), f = exact_fold_lanes(w, k, E);
+      if (lane == 0) { out[k] = a; out[3 + k] = b; out[6 + k] = f; }
+   }
+}
+int vcg_test_exact_sum(lgh_ctx *c, int mode, long n, int G, int E, const double *scale, const double *v, const long long *w_in,
+                       long long *w_out, double *d_out, int *i_out)
+{
+   struct Dev { void *p = nullptr; ~Dev() { (void)hipFree(p); } } dv, dw, dd, di, ds;
+   auto up = [&](Dev &b, const void *src, size_t bytes) -> hipError_t {
+      hipError_t e = hipMalloc(&b.p, bytes);
+      if (e == hipSuccess) { e = src ? hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) : hipMemsetAsync(b.p, 0, bytes, c->stream); }
+      return e;
+   };
+   if (scale) { LGH_HIP_CHECK(up(ds, scale, sizeof(double))); }
+   const double *dscale = (const double *)ds.p;
+   const unsigned nb = (unsigned)((n + 255) / 256);
+   const size_t un = (size_t)n;
+   switch (mode)
+   {
+      case 0: // split
+         LGH_HIP_CHECK(up(dv, v, un * sizeof(double)));
+         LGH_HIP_CHECK(up(dw, nullptr, kLimbs * un * sizeof(long long)));
+         LGH_HIP_CHECK(up(di, nullptr, un * sizeof(int)));
+         hipLaunchKernelGGL(vcg_test_exact_split_k, dim3(nb), dim3(256), 0, c->stream, (const double *)dv.p, n, E, dscale, (long long *)dw.p, (int *)di.p);
+         LGH_HIP_CHECK(hipGetLastError());
+         LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
+         LGH_HIP_CHECK(hipMemcpy(w_out, dw.p, kLimbs * un * sizeof(long long), hipMemcpyDeviceToHost));
+         LGH_HIP_CHECK(hipMemcpy(i_out, di.p, un * sizeof(int), hipMemcpyDeviceToHost));
+         return LGH_OK;
+      case 1: // value
+         LGH_HIP_CHECK(up(dw, w_in, kLimbs * un * sizeof(long long)));
+         LGH_HIP_CHECK(up(dd, nullptr, un * sizeof(double)));
+         hipLaunchKernelGGL(vcg_test_exact_value_k, dim3(nb), dim3(256), 0, c->stream, (const long long *)dw.p, n, E, (double *)dd.p);
+         LGH_HIP_CHECK(hipGetLastError());
+         LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
+         LGH_HIP_CHECK(hipMemcpy(d_out, dd.p, un * sizeof(double), hipMemcpyDeviceToHost));
+         return LGH_OK;
+      case 2: // grid
+         LGH_HIP_CHECK(up(dv, v, kVC * un * sizeof(double)));
+         LGH_HIP_CHECK(up(dw, nullptr, kLimbWords * sizeof(long long))); // a cleared set
+         LGH_HIP_CHECK(up(dd, nullptr, 9 * sizeof(double)));
+         hipLaunchKernelGGL(vcg_test_exact_grid_k, dim3((unsigned)G), dim3(256), 0, c->stream, (const double *)dv.p, n, E, dscale, (long long *)dw.p);
+         LGH_HIP_CHECK(hipGetLastError());
+         hipLaunchKernelGGL(vcg_test_exact_fold_k, dim3(1), dim3(64), 0, c->stream, (const long long *)dw.p, E, dscale, ldexp(0.75, E - 12), (double *)dd.p);
+         LGH_HIP_CHECK(hipGetLastError());
+         LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
+         LGH_HIP_CHECK(hipMemcpy(w_out, dw.p, kLimbWords * sizeof(long long), hipMemcpyDeviceToHost));
+         LGH_HIP_CHECK(hipMemcpy(d_out, dd.p, 9 * sizeof(double), hipMemcpyDeviceToHost));
+         return LGH_OK;
+      case 3: // wave
+         LGH_HIP_CHECK(up(dv, w_in, un * sizeof(long long)));
+         LGH_HIP_CHECK(up(dw, nullptr, un * sizeof(long long)));
+         hipLaunchKernelGGL(vcg_test_wave_sum_k, dim3((unsigned)(n / 64)), dim3(64), 0, c->stream, (const long long *)dv.p, (long long *)dw.p);
+         LGH_HIP_CHECK(hipGetLastError());
+         LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
+         LGH_HIP_CHECK(hipMemcpy(w_out, dw.p, un * sizeof(long long), hipMemcpyDeviceToHost));
+         return LGH_OK;
+      default: // 4: scale
+         LGH_HIP_CHECK(up(dv, v, un * sizeof(double)));
+         LGH_HIP_CHECK(up(di, nullptr, un * sizeof(int)));
+         hipLaunchKernelGGL(vcg_test_exact_scale_k, dim3(nb), dim3(256), 0, c->stream, (const double *)dv.p, n, (int *)di.p);
+         LGH_HIP_CHECK(hipGetLastError());
+         LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
+         LGH_HIP_CHECK(hipMemcpy(i_out, di.p, un * sizeof(int), hipMemcpyDeviceToHost));
+         return LGH_OK;
+   }
+}
+
 // Test hooks and the merged layout: the hooks speak the element-local E-vector ([e][d] per component) on both sides.
 // Out of K1: every entry from its place in the plane; the right-hand member of a merged pair reads 0.0 and the sum K1
 // formed is reported in the left-hand zone's entry (lgh_test_vcg_merged_faces tells the caller which entries those are).

@@ -254,10 +254,16 @@ struct VcgArgs
 // sets dynamically.  Integer addition is associative: every addend v, known to lie in (-2^(E-1), 2^(E-1)), is split
 // into kLimbs signed pieces of 32 bits - limb j weighs 2^(E - 32 (j + 1)) - which are added into 64-bit integer
 // accumulators (registers, LDS, finally fire-and-forget device atomics: no ticket, no fold, nobody is "last").
-// The window of 128 bits below 2^E loses at most 2^(E-128) per addend; up to 2^31 addends fit the accumulators.
+// The window of 128 bits below 2^E loses less than 2^(E-128) per addend (the bits below it are dropped, towards zero);
+// up to 2^31 addends fit the accumulators.
 // E comes from a quantity every workgroup of the producing and of the consuming kernel reads alike (rz of the
 // iteration: (d, A d) <= lambda_max(D^-1 M) (r, z) <= 64 (r, z) for the Jacobi-preconditioned mass matrix), a
 // non-finite or out-of-window addend sets a sticky flag that turns the sum into NaN.
+// A scale no solve should see: rz < 0 gives the window of |rz|; rz = 0 gives E = 12; for rz = inf or NaN the C library
+// leaves frexp's exponent open, the device instruction (v_frexp_exp_i32_f64) returns 0: E = 12 as well.  Each is a valid
+// window - a set added and folded under it is the exact sum of its addends where they fit and NaN where one does not,
+// never a finite number that is not the sum (in the solve a non-finite rz makes beta and with it every addend NaN).
+// tests/test_gpu_exact_sum.py pins all of this through lgh_test_exact_sum.
 constexpr int kLimbs = 4;      // 64-bit accumulators per sum
 constexpr int kLimbShards = 4; // copies of the accumulators (workgroup b adds to shard b % kLimbShards): ~64 atomics per word and launch
 constexpr int kLimbWords = kLimbShards * kVC * kLimbs + 8; // the accumulators, then the flag word (padded)
@@ -268,20 +274,25 @@ __device__ __forceinline__ int exact_scale(const double rz) // E for sums bounde
    (void)frexp(rz, &e); // rz = m 2^e, m in [0.5, 1)
    return e + 12;
 }
-// returns false when v does not fit the window (|v| >= 2^(E-1), NaN, inf); acc is then left alone
+// returns false when v does not fit the window (|v| >= 2^(E-1), NaN, inf); acc is then left alone.
+// The magnitude is split and the limbs are added or subtracted: the addend contributes trunc(v 2^(128-E)) units of
+// 2^(E-128), every |limb| < 2^32.  Every step is exact: x >= 0, so floor(x) <= x < 2^32 converts in range and
+// x - floor(x) is the low bits of x itself.  (Splitting the signed value by floor() is not: for x < 0 with bits below
+// 2^-53 the difference x - floor(x) does not fit a double - it rounds to 1.0 for -2^-53 < x < 0, the next limb's
+// conversion of 2^32 is out of range and clamps on gfx950 - and a negative addend came out wrong by up to 2^(E-64);
+// tests/test_gpu_exact_sum.py.)  An addend so small that the scaling underflows lies entirely below the window.
 __device__ __forceinline__ bool exact_add(long long (&acc)[kLimbs], const double v, const int E)
 {
-   double x = ldexp(v, 32 - E); // exact; |x| < 2^31 required
-   if (!(fabs(x) < 2147483648.0)) { return false; }
-   double f = floor(x);
-   acc[0] += (long long)(int)f; // signed top limb
-   x = (x - f) * 4294967296.0;  // exact: fractional part, scaled by 2^32
+   double x = fabs(ldexp(v, 32 - E)); // exact; x < 2^31 required
+   if (!(x < 2147483648.0)) { return false; }
+   const long long sgn = (v < 0.0) ? -1LL : 0LL;
 #pragma unroll
-   for (int j = 1; j < kLimbs; j++)
+   for (int j = 0; j < kLimbs; j++)
    {
-      f = floor(x);
-      acc[j] += (long long)(unsigned)f;
-      x = (x - f) * 4294967296.0;
+      const double f = floor(x);
+      const long long l = (long long)(unsigned)f;
+      acc[j] += (l ^ sgn) - sgn; // +l or -l
+      x = (x - f) * 4294967296.0; // exact: fractional part, scaled by 2^32
    }
    return true;
 }

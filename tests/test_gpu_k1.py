@@ -177,3 +177,143 @@ def test_k1_static_schedule_at_64_cubed(monkeypatch):
     for c in range(3):
         assert rel_err(out["slab"][0][c], out["plane"][0][c]) < 2e-12, c
         assert abs(out["slab"][1][c] - out["plane"][1][c]) <= 2e-12 * abs(out["plane"][1][c]), c
+
+
+# ---- the exact accumulators of (d, A d) at their edges (slab form; the primitives alone: tests/test_gpu_exact_sum.py) ----
+EXACT_CASES = [("Q3Q2-16-slab", "box01_hex", 0), ("Q3Q2-512-slab", "cube01_hex", 2)]  # ragged last set / more sets than wavefronts
+
+
+def _slab_sums(prob, d, yE):
+    """sum of d y over the 16 dofs of each z-slab of each zone: [NE, D1D] (element-local index dx + 4 dy + 16 dz).  In the
+    Kronecker form of the slab K1 (compact mass data) this is what one lane hands to exact_add in one pass: lane
+    16 g + 3 el + c holds the 16 nodes dz = g of zone el of the set, component c, and sums dd[j] * v[j] over them."""
+    hmap = np.asarray(prob.h1map).reshape(prob.NE, prob.ND)
+    D = prob.D1D
+    return (d[hmap] * yE.reshape(prob.NE, prob.ND)).reshape(prob.NE, D, D * D).sum(axis=2)
+
+
+def _slab_env(monkeypatch, rank1):
+    for k in ("LGH_VCG_VARIANT", "LGH_MASS_RANK1", "LGH_MASS_KRON", "LGH_SLAB_MERGE", "LGH_RZ_LIMBS", "LGH_SLAB_EXACT"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("LGH_VCG_VARIANT", "4")
+    if not rank1:
+        monkeypatch.setenv("LGH_MASS_RANK1", "0")
+
+
+@pytest.mark.parametrize("first", [True, False], ids=["first", "later"])
+@pytest.mark.parametrize("rank1", [True, False], ids=["compact", "stored"])
+@pytest.mark.parametrize("case", EXACT_CASES, ids=[c[0] for c in EXACT_CASES])
+def test_k1_slab_addends_out_of_the_window(case, rank1, first, monkeypatch):
+    """rz understated by 2^-60 (rz_prev with it: beta keeps its bits): the window of the accumulators lies 60 binades too
+    low and the lane partials do not fit.  (d, A d) must then be NaN in all three components - not a wrong number -, the
+    E-vector must not notice, and the next launch with the true rz must return what the first one did: the flag does
+    not survive into the next solve."""
+    from oracle.fem import Problem
+    _, mesh, rs = case
+    prob = Problem(mesh=mesh, rs=rs, order_v=3, order_e=2, problem=1)
+    _slab_env(monkeypatch, rank1)
+    g, o = make_gpu(prob), make_oracle(prob)
+    try:
+        assert g.ctx.k1_form() == "slab" and g.ctx.mass_data_form() == ("rank1" if rank1 else "stored")
+        N = prob.N
+        r, d_old = seeded(3 * N, 101), seeded(3 * N, 102)
+        dinv = 1.0 / np.asarray(o.diagV)
+        rz = np.array([float(np.dot(r[c * N:(c + 1) * N] ** 2, dinv)) for c in range(3)])
+        rz_prev = rz * np.array([1.7, 0.6, 1.1])
+        low = 2.0 ** -60
+        # the claim, on the oracle's E-vector: every lane partial is beyond the understated window.  Compact data: a lane's
+        # partial is a z-slab sum.  Stored data: the four lanes of a zone sum d y over its quadrature points instead, all
+        # terms >= 0 - the largest of four non-negative partials is at least a quarter of the zone's sum.
+        yE_o, _ = _oracle_k1(prob, o, r, d_old, rz / rz_prev, first)
+        for c in range(3):
+            d = r[c * N:(c + 1) * N] * dinv + (0.0 if first else (rz[c] / rz_prev[c]) * d_old[c * N:(c + 1) * N])
+            edge = 2.0 ** (np.frexp(rz[c] * low)[1] + 12 - 1)
+            s = _slab_sums(prob, d, yE_o[c])
+            assert np.all(np.abs(s) >= edge) if rank1 else np.all(s.sum(axis=1) / 4 >= edge)
+        rd, dd = g.ctx.to_dev(r), None if first else g.ctx.to_dev(d_old)
+        yE1, den1 = g.ctx.test_vcg_k1(rd, dd, rz, rz_prev, first)
+        yE1 = yE1.cpu().numpy().copy()
+        yE2, den2 = g.ctx.test_vcg_k1(rd, dd, rz * low, rz_prev * low, first)
+        yE2 = yE2.cpu().numpy().copy()
+        yE3, den3 = g.ctx.test_vcg_k1(rd, dd, rz, rz_prev, first)
+        yE3 = yE3.cpu().numpy().copy()
+    finally:
+        g.close()
+        o.close()
+    assert np.all(np.isfinite(den1)) and np.all(den1 > 0)
+    assert np.all(np.isnan(den2)), den2
+    assert np.array_equal(yE2.view(np.int64), yE1.view(np.int64))
+    assert np.array_equal(den3.view(np.int64), den1.view(np.int64)), (den1, den3)
+    assert np.array_equal(yE3.view(np.int64), yE1.view(np.int64))
+
+
+def quiet_state_with_one_loud_zone(prob, diag, seed=5):
+    """r of a state with one loud zone and a quiet remainder (a blast in one corner of a mesh at rest): O(1) random on the
+    nodes of zone 0; everywhere else r = diag d with d = 2^-90 g(x) g(y) g(z), g = (1, -4, 0) repeated over the layers of
+    nodes - every zone sees the local profile a = (1, -4, 0, 1) along each axis, and with the Q3 mass tile M1
+    a_0 (M1 a)_0 < 0: the sum of d (A d) over the dofs with index 0 along one axis is negative, and tiny."""
+    N = prob.N
+    S = prob.initial_state()[0]
+    X = np.asarray(S[:prob.dim * N]).reshape(prob.dim, N)
+    gpat = np.array([1.0, -4.0, 0.0])
+    dq = np.full(N, 2.0 ** -90)
+    for ax in range(prob.dim):
+        layers = np.unique(np.round(X[ax], 10))
+        assert len(layers) % 3 == 1  # Q3: 3 layers per zone and one more
+        dq = dq * gpat[np.searchsorted(layers, np.round(X[ax], 10)) % 3]
+    loud = np.asarray(prob.h1map).reshape(prob.NE, prob.ND)[0]
+    r = np.empty(3 * N)
+    for c in range(3):
+        rc = np.asarray(diag) * dq
+        rc[loud] = seeded(len(loud), seed + c)
+        r[c * N:(c + 1) * N] = rc
+    return r
+
+
+@pytest.mark.parametrize("rank1", [True, False], ids=["compact", "stored"])
+@pytest.mark.parametrize("case", EXACT_CASES, ids=[c[0] for c in EXACT_CASES])
+def test_k1_slab_tiny_negative_addends(case, rank1, monkeypatch):
+    """(d, A d) of a state whose addends are mostly tiny and often negative (quiet_state_with_one_loud_zone), where the
+    seeded vectors of the cases above have none.  Reference: the sum of d y in exact arithmetic (fractions) over the
+    device's OWN E-vector (element-local layout, LGH_SLAB_MERGE=0) and the device's own d = r * (1 / diag), both
+    reproduced bit for bit - the operator's 2e-12 is not in the comparison.  Tolerance (n + 2) 2^-53 sum |d y|, n = the
+    number of products a lane adds up before exact_add, read off vcg_apply_slab346: n = 16 in the Kronecker form (compact
+    data: dset = sum over the 16 nodes of the lane's z-slab of dd[j] v[j]; + 1 for the factor s_e the E-vector carries,
+    + 1 for dset * s_e) and n = 54 through the quadrature points (stored data: dset = sum over 9 (qx, qy) pairs x 6 qz of
+    u (u D); those addends are sums of squares, never negative - the case is there for the tiny ones).  The exact
+    accumulation itself adds less than 2^-100 of den per addend.  With compact data the addends are the z-slab sums of
+    _slab_sums: at least 10 % of them must be negative and below 2^-53 of a top-limb unit for the case to mean anything."""
+    from oracle.fem import Problem
+    _, mesh, rs = case
+    prob = Problem(mesh=mesh, rs=rs, order_v=3, order_e=2, problem=1)
+    _slab_env(monkeypatch, rank1)
+    monkeypatch.setenv("LGH_SLAB_MERGE", "0")
+    g = make_gpu(prob)
+    try:
+        assert g.ctx.k1_form() == "slab" and g.ctx.mass_data_form() == ("rank1" if rank1 else "stored")
+        N, NE, ND = prob.N, prob.NE, prob.ND
+        diag = np.asarray(g.ctx.mass_diag, dtype=np.float64)
+        dinv = 1.0 / diag
+        r = quiet_state_with_one_loud_zone(prob, diag)
+        rz = np.array([float(np.dot(r[c * N:(c + 1) * N] ** 2, dinv)) for c in range(3)])
+        yE, den = g.ctx.test_vcg_k1(g.ctx.to_dev(r), None, rz, rz, True)
+        yE = yE.cpu().numpy()
+        assert g.ctx.test_vcg_merged_faces()[1] == 0
+    finally:
+        g.close()
+    from fractions import Fraction
+    hmap = np.asarray(prob.h1map).reshape(-1)
+    n_lane = 16 if rank1 else 54
+    for c in range(3):
+        d = r[c * N:(c + 1) * N] * dinv
+        ref = float(sum(Fraction(a) * Fraction(b) for a, b in zip(d[hmap].tolist(), yE[c].tolist())))  # exact, rounded once
+        mag = float(np.sum(np.abs(d[hmap] * yE[c])))
+        if rank1:
+            s = _slab_sums(prob, d, yE[c])
+            unit = 2.0 ** (np.frexp(rz[c])[1] + 12 - 32)
+            frac = float(np.mean((s < 0) & (np.abs(s) < 2.0 ** -53 * unit)))
+            print(f"component {c}: {frac:.3f} of the {s.size} addends are negative and below 2^-53 of a top-limb unit")
+            assert frac >= 0.10
+        tol = (n_lane + 2) * 2.0 ** -53 * mag
+        print(f"component {c}: den {den[c]!r} reference {ref!r} error {abs(den[c] - ref):.3e} tolerance {tol:.3e}")
+        assert abs(den[c] - ref) <= tol, (c, den[c], ref, abs(den[c] - ref) / tol)

@@ -124,3 +124,46 @@ def test_k2_at_bench_size_vs_oracle_cg(it, monkeypatch):
         monkeypatch.delenv(k, raising=False)
     prob = Problem(mesh="cube01_hex", rs=4, order_v=3, order_e=2, problem=1)
     _run_k2(prob, it, True, "slab")
+
+
+EXACT_CASES = [("Q3Q2-16-slab", "box01_hex", 0), ("Q3Q2-512-slab", "cube01_hex", 2)]
+
+
+@pytest.mark.parametrize("case", EXACT_CASES, ids=[c[0] for c in EXACT_CASES])
+def test_k2_rz_out_of_the_window(case, monkeypatch):
+    """The exact accumulators of (r, z) (slab K1, bounded-grid K2) with rz of the iteration before understated by 2^-60:
+    the window lies 60 binades too low, the workgroups' shares of the new (r, z) - which alpha = rz / den, 2^-60 of what it
+    should be, leaves at the size of the old one - do not fit, and (r, z) must come back NaN in all three components, not
+    as a wrong number.  The next launch with the true rz returns the bits of the first: the flag does not outlive the solve."""
+    from oracle.fem import Problem
+    _, mesh, rs = case
+    for k in ("LGH_VCG_VARIANT", "LGH_RZ_LIMBS", "LGH_K2_U", "LGH_K2_SKIP", "LGH_K2P", "LGH_SLAB_MERGE"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("LGH_VCG_VARIANT", "4")
+    prob = Problem(mesh=mesh, rs=rs, order_v=3, order_e=2, problem=1)
+    g, o = make_gpu(prob), make_oracle(prob)
+    try:
+        assert g.ctx.k1_form() == "slab"
+        it = 2
+        inp, exp = _oracle_iteration(prob, o, it, True)
+        yE = g.ctx.to_dev(np.ascontiguousarray(inp["yE"].reshape(-1)))
+        low = 2.0 ** -60
+        # the claim: (r, z) of the residual the understated alpha leaves (r itself, to 2^-60) against the understated window -
+        # the largest of the workgroups' non-negative shares is at least their mean, and there are fewer workgroups than nodes
+        dinv = 1.0 / np.asarray(o.diagV)
+        for c in range(3):
+            rc = inp["r"][c * prob.N:(c + 1) * prob.N]
+            assert float(np.dot(rc * rc, dinv)) / prob.N >= 2.0 ** (np.frexp(inp["rz"][c] * low)[1] + 11)
+        out = []
+        for f in (1.0, low, 1.0):
+            rd, dd, xd = g.ctx.to_dev(inp["r"]), g.ctx.to_dev(inp["d"]), g.ctx.to_dev(inp["x"])
+            rz_g, deferred = g.ctx.test_vcg_k2(it, yE, rd, dd, xd, inp["den"], inp["rz"] * f, inp["rz_prev"] * f, inp["alpha_prev"])
+            assert deferred
+            out.append(rz_g.copy())
+    finally:
+        g.close()
+        o.close()
+    for c in range(3):
+        assert abs(out[0][c] - exp["rz"][c]) <= 1e-13 * abs(exp["rz"][c])
+    assert np.all(np.isnan(out[1])), out[1]
+    assert np.array_equal(out[2].view(np.int64), out[0].view(np.int64)), (out[0], out[2])
