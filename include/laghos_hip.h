@@ -320,6 +320,33 @@ int lgh_sample_fields(lgh_ctx *ctx, const double *S, const double *rho_l2 /* or 
                       const double *B_l2_lat /* host, R1*L1D, [r + R1*l] */,
                       double *x_out, double *v_out, double *e_out, double *rho_out, double *p_out);
 
+/* ---- conservation and mesh-health diagnostics (the driver's `-hist` time history; the reference prints one number,
+ * "Energy diff", after the last step).  At quadrature point q of zone z, with the context's own tables and rule (those
+ * lgh_qupdate uses): J_q = grad x and detJ_q from the x block of S, v_q from the v block, e_q from the e block through
+ * B_l2, m_q = rho0DetJ0w[z, q], rho_q = (1 / w_q) m_q / detJ_q, p_q = (gamma_z - 1) rho_q max(e_q, 0) - the expressions
+ * of QUpdateBody (laghos_solver.cpp:1074-1083).  A point is NON-FINITE when detJ_q, e_q or a component of v_q is not
+ * finite, INVERTED when detJ_q <= 0.  Slot k, per zone and globally:
+ *    0 mass = sum m_q            1 volume = sum w_q detJ_q      2 internal energy = sum m_q e_q (laghos_solver.cpp:640-667)
+ *    3 kinetic energy = 1/2 sum m_q |v_q|^2 (:669-697)          4-6 momentum = sum m_q v_c(q), 0 for c >= dim
+ *    7 detj_min (finite points)  8, 9 rho_min, rho_max (finite, not inverted)   10, 11 e_min, e_max (finite points)
+ *   12 p_max (finite, not inverted)   13 v_max = max |v_q| (finite points)
+ *   14 n_inverted   15 n_negative_e (e_q < 0)   16 n_nonfinite   (counts, as doubles)
+ * Sums run over all points (a NaN in the state makes them NaN); extremes skip the excluded points, and with no point
+ * left a minimum is +inf and a maximum -inf.  The global array adds 17 = the zone that holds detj_min (the CALLER's id on
+ * its rank, ties to the lowest id), 18 = that zone's rank (ties to the lowest rank), 19 = 0.
+ * No floating-point atomics: a zone's points are folded in a fixed shape inside its workgroup, the zones in ascending
+ * caller id by one workgroup of fixed shape; the same S and context give the same bits whatever the launch grid.  Over
+ * several ranks sums go through the all-reduce, minima through the min-reduce, maxima as negated minima.
+ * Both calls read S, rho0DetJ0w, gamma, the tables and h1_map and write their outputs only: the quadrature data, its
+ * generation counter, the fused force products, dt_est and the velocity snapshot are untouched.  All dimensions.
+ * Before lgh_setup_rho0detj0, or with a NULL argument: LGH_ERR_ARG, no kernel is launched. */
+#define LGH_DIAG_ZONE_COUNT 17
+#define LGH_DIAG_COUNT 20
+/* per zone, structure of arrays: zone_out[k * NE + z], z the CALLER's zone id; device; asynchronous */
+int lgh_diagnostics_zones(lgh_ctx *ctx, const double *S, double *zone_out);
+/* the same folded over zones and ranks; out is HOST memory; synchronous */
+int lgh_diagnostics(lgh_ctx *ctx, const double *S, double out[LGH_DIAG_COUNT]);
+
 /* ---- timing data (TimingData, laghos_solver.hpp:39-56): seconds measured with
  * HIP events around the same regions as the reference stopwatches.
  * t[0..3] = cgH1, cgL2, force, qdata; c[0..2] = H1iter, L2iter, quad_tstep */
@@ -341,6 +368,7 @@ int lgh_enable_timers(lgh_ctx *ctx, int on);
 #define LGH_KERNEL_ALLREDUCE 7    /* one ncclAllReduce of device scalars */
 #define LGH_KERNEL_SAMPLE 8       /* lgh_sample_fields */
 #define LGH_KERNEL_FINGERPRINT 9  /* lgh_vec_fingerprint */
+#define LGH_KERNEL_DIAG 10        /* the zone kernel of lgh_diagnostics_zones / lgh_diagnostics */
 int lgh_ktime_begin(lgh_ctx *ctx, int which, int max_samples);
 int lgh_ktime_end(lgh_ctx *ctx, int *launches, double *mean_seconds);
 /* Whether lgh_create found the 1-D H1 / L2 tables mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (any nodal or

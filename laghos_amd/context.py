@@ -55,6 +55,18 @@ def sedov_eval_point(par, t, r):
     return rho.value, v.value, p.value
 
 
+# lgh_diagnostics: slot k of the zone arrays (the first 17) and of the global array (include/laghos_hip.h)
+DIAG_NAMES = ("mass", "volume", "ie", "ke", "px", "py", "pz", "detj_min", "rho_min", "rho_max", "e_min", "e_max", "p_max", "v_max",
+              "n_inverted", "n_negative_e", "n_nonfinite", "detj_min_zone", "detj_min_rank")
+DIAG_ZONE_COUNT, DIAG_COUNT = 17, 20
+_DIAG_INTS = ("n_inverted", "n_negative_e", "n_nonfinite", "detj_min_zone", "detj_min_rank")
+
+
+def diagnostics_dict(out):
+    """the 20 doubles of lgh_diagnostics by name"""
+    return {k: (int(out[i]) if k in _DIAG_INTS else float(out[i])) for i, k in enumerate(DIAG_NAMES)}
+
+
 class Context:
     """lgh_ctx owner.  Arguments follow struct lgh_config: tables are (Q,D)
     arrays B[q,d]; h1_map is (NE, ND); ess is a list of dim int arrays."""
@@ -416,6 +428,19 @@ class Context:
         opt = lambda t: _ptr(t) if t is not None else None
         check(self.lib.lgh_sample_fields(self.h, _ptr(S), opt(rho_l2), R1, _dbl(Bh), _dbl(Bl), opt(x), opt(v), opt(e), opt(rho),
                                          opt(p)))
+
+    def diagnostics_zones(self, S, out):
+        """lgh_diagnostics_zones: the 17 zone diagnostics of S into the device tensor out (17 * NE), out[k * NE + z] with z
+        the caller's zone id and k the position in DIAG_NAMES.  Asynchronous."""
+        assert out.numel() == DIAG_ZONE_COUNT * self.NE
+        check(self.lib.lgh_diagnostics_zones(self.h, _ptr(S), _ptr(out)))
+
+    def diagnostics(self, S, raw=False):
+        """lgh_diagnostics: the diagnostics of S folded over zones and ranks, as a dict by DIAG_NAMES (counts, the zone and
+        its rank as ints), or the 20 doubles themselves (raw=True).  Synchronous."""
+        out = np.full(DIAG_COUNT, np.nan)   # (an entry the library did not write would show)
+        check(self.lib.lgh_diagnostics(self.h, _ptr(S), _dbl(out)))
+        return out if raw else diagnostics_dict(out)
 
     def solve_energy_begin(self, S, v, dS, e_rhs, rel_tol, max_iter, e_source=None):
         check(self.lib.lgh_solve_energy_begin(self.h, _ptr(S), _ptr(v), _ptr(dS), _ptr(e_rhs),

@@ -598,7 +598,7 @@ int lgh_destroy(lgh_ctx *c)
                    c->stressJinvT, c->Jac0inv, c->Jac0inv_soa, c->Jac0inv_e, c->rho0DetJ0w, c->massD, c->diagV, c->dinvV,
                    c->dt_est_dev, c->erhs_q, c->v_snap, c->dev_flags, c->ones_l2, c->massS, c->ones_ne, c->force_e_q, c->XE, c->YE, c->cg_r, c->cg_z, c->cg_d0, c->cg_d1, c->cg_y,
                    c->partials, c->tickets, c->cgs, c->scal, c->vcg_s, c->vcg_vec, c->vcg_partials,
-                   c->vcg_tickets, c->me_fac, c->fp_dev};
+                   c->vcg_tickets, c->me_fac, c->fp_dev, c->diag_dev};
    for (void *p : ptrs) { if (p) { (void)hipFree(p); } }
    if (c->host_pinned) { (void)hipHostFree(c->host_pinned); }
    if (c->timers.ev[0]) { (void)hipEventDestroy(c->timers.ev[0]); }
@@ -788,10 +788,12 @@ int lgh_setup_rho0detj0(lgh_ctx *c, const double *x0, const double *rho0_l2, con
    invalidate_fused(c);
    c->mass_rank1 = -1; // (new mass data)
    c->mass_gen++;
-   if (c->dim == 1) { return setup_1d(c, x0, rho0_l2, rho0_q, volume); } // (with the diagonal and the zone mass factors)
-   int rc = setup_rho0detj0(c, x0, rho0_l2, rho0_q, volume);
+   int rc = (c->dim == 1) ? setup_1d(c, x0, rho0_l2, rho0_q, volume) // (with the diagonal and the zone mass factors)
+                          : setup_rho0detj0(c, x0, rho0_l2, rho0_q, volume);
    if (rc) { return rc; }
-   return mass_assemble_diag(c);
+   if (c->dim != 1) { rc = mass_assemble_diag(c); }
+   if (rc == LGH_OK) { c->setup_done = 1; }
+   return rc;
 }
 
 int lgh_force_mult(lgh_ctx *c, const double *x_l2, double *y_h1)

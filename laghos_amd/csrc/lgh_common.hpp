@@ -198,6 +198,8 @@ struct lgh_ctx
    void *order;          // lgh::MeshOrder (lgh_order.hip)
    unsigned long mass_gen; // counts changes of the mass data / Jacobi diagonal (the velocity solve keeps copies in its own numbering)
    double *me_fac;       // 1D: NE * L1D^2, Cholesky factors of the zone mass matrices Me(z) of the energy solve (lgh_1d.hip)
+   int setup_done;       // lgh_setup_rho0detj0 has run: rho0DetJ0w holds the masses of the points (lgh_diagnostics refuses before)
+   double *diag_dev;     // lgh_diagnostics (lgh_diag.hip): 32 doubles of folded values, then the 17 zone arrays; allocated on first use
    unsigned long long *fp_dev; // lgh_vec_fingerprint (lgh_fingerprint.hip): the two words of the result and the workgroups' partial words, allocated on first use
 };
 

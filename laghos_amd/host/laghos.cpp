@@ -28,6 +28,7 @@
 #include "sedov_exact.hpp"
 #include "vtk_output.hpp"
 #include "checkpoint.hpp"
+#include "history.hpp"
 
 using namespace laghos;
 
@@ -74,6 +75,7 @@ struct Options
    int ckpt_steps = 0;             // -ckpt N: a checkpoint after every accepted step with ti % N == 0 and after the last one (0: none)
    int ckpt_keep = 2;              // -ckpt-keep K: pieces of this run kept per rank (0: all)
    std::string restart;            // -restart PATH: a checkpoint stem, or "latest" (<basename>_restart/latest)
+   int hist_steps = 0;             // -hist N: a row of <basename>_history.csv at cycle 0, after every accepted step with ti % N == 0 and after the last one (0: none)
    bool fingerprint = false;       // -fp: rank 0 prints the state fingerprint after the last step and per checkpoint
 };
 
@@ -115,6 +117,13 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
          if (!(v = need(i))) { return false; }
          o.ckpt_keep = std::atoi(v);
          if (o.ckpt_keep < 0) { err = "-ckpt-keep / --checkpoint-keep must be 0 (keep all) or more, got " + std::string(v); return false; }
+         continue;
+      }
+      if (a == "-hist" || a == "--history-steps")
+      {
+         if (!(v = need(i))) { return false; }
+         o.hist_steps = std::atoi(v);
+         if (o.hist_steps < 1) { err = "-hist / --history-steps must be at least 1, got " + std::string(v); return false; }
          continue;
       }
       if (a == "-restart" || a == "--restart")
@@ -309,6 +318,9 @@ struct laghos_sim
    std::vector<double> ckpt_host;
    int ckpt_count = 0;
    double ckpt_seconds[3] = {0, 0, 0}; // fingerprint (GPU), device-to-host copy, host fingerprint + file write
+   // -hist: the file (rank 0) and the last cycle that has its row (a restart: the checkpoint's cycle, which gets none)
+   HistoryFile hist;
+   int hist_last = -1;
    int steps_at_start = 0;             // RK steps the checkpoint of a restart had taken: timing / FOM cover the restarted segment
 };
 
@@ -476,6 +488,42 @@ static bool PeriodicCheckpoint(laghos_sim *s, int ti_now)
       (void)std::remove(s->ckpt_mine.front().c_str());
       s->ckpt_mine.erase(s->ckpt_mine.begin());
    }
+   return true;
+}
+
+// One row of the `-hist` file for the state as it stands, cycle `cycle`: the diagnostics on the GPU (collective), the line by rank 0,
+// flushed.  Every rank learns whether the row was written.
+static bool HistoryRecord(laghos_sim *s, int cycle)
+{
+   const Options &o = s->opt;
+   auto &hydro = *s->hydro;
+   double d[LGH_DIAG_COUNT];
+   hydro.Diagnostics(s->S, d);
+   bool ok = true;
+   std::string err;
+   if (o.rank == 0) { ok = HistoryAppend(s->hist, HistoryRow(cycle, s->t, s->dt, s->steps, s->repeats, d, s->energy_init), err); }
+   const bool all_ok = hydro.AllReduce(ok ? 1.0 : 0.0, 1) == 1.0;
+   if (!ok) { return SimFail(s, "cannot write the -hist file: " + err); }
+   if (!all_ok) { return SimFail(s, "rank 0 could not write the -hist file"); }
+   s->hist_last = cycle;
+   return true;
+}
+
+// Opens the `-hist` file on rank 0: a new one, or - a restart from cycle `resume_cycle` >= 0 - the existing one with its later rows dropped.
+static bool HistoryOpen(laghos_sim *s, int resume_cycle)
+{
+   const Options &o = s->opt;
+   bool ok = true;
+   std::string err;
+   if (o.rank == 0)
+   {
+      const std::string path = HistoryPath(o.basename);
+      ok = (resume_cycle < 0) ? HistoryStart(s->hist, path, err) : HistoryResume(s->hist, path, resume_cycle, err);
+   }
+   const bool all_ok = s->hydro->AllReduce(ok ? 1.0 : 0.0, 1) == 1.0;
+   if (!ok) { return SimFail(s, "cannot write the -hist file: " + err); }
+   if (!all_ok) { return SimFail(s, "rank 0 could not open the -hist file"); }
+   s->hist_last = resume_cycle;
    return true;
 }
 
@@ -673,6 +721,7 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
          std::cout << "Restarting from " << ck_piece << ": cycle " << h.ti << ", t = " << std::setprecision(17) << s->t << ", dt = " << s->dt
                    << std::setprecision(6) << std::endl;
       }
+      if (o.hist_steps > 0 && !HistoryOpen(s.get(), h.ti)) { return nullptr; } // (no row for the checkpoint's own state: the run that wrote it has)
       // a checkpoint written after the last step: nothing is left to do
       if (s->t >= o.t_final || (o.max_tsteps >= 0 && s->steps > o.max_tsteps)) { s->last_step = true; }
       return s.release();
@@ -685,6 +734,7 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
    s->t = 0.0;
    s->dt = s->hydro->GetTimeStepEstimate(s->S);                                      // :708
    if (o.paraview && !DumpParaview(s.get(), 0)) { return nullptr; }                   // :691-701
+   if (o.hist_steps > 0 && !(HistoryOpen(s.get(), -1) && HistoryRecord(s.get(), 0))) { return nullptr; }
    return s.release();
 }
 
@@ -732,6 +782,8 @@ int laghos_sim_step(laghos_sim *s)
          // The run ends here when its last step was a repeated one (the loop of laghos.cpp:742-778 has no step left to take):
          // the state is that of the last accepted step again, with the shortened dt - the checkpoint "after the last step"
          if (s->last_step && o.ckpt_steps > 0 && s->ti > 1 && !PeriodicCheckpoint(s, s->ti - 1)) { return -1; }
+         // ... and the row "after the last step", unless that step has its row already (repeated steps themselves write none)
+         if (s->last_step && o.hist_steps > 0 && s->ti - 1 > s->hist_last && !HistoryRecord(s, s->ti - 1)) { return -1; }
          continue;
       }
       else if (dt_est > 1.25 * s->dt) { s->dt *= 1.02; }
@@ -770,6 +822,7 @@ int laghos_sim_step(laghos_sim *s)
          s->checks_ok = CheckNorm(o.dim, o.problem, s->ti, e_norm, s->checks) && s->checks_ok;
       }
       if (o.ckpt_steps > 0 && (s->last_step || (s->ti % o.ckpt_steps) == 0) && !PeriodicCheckpoint(s, s->ti)) { return -1; }
+      if (o.hist_steps > 0 && (s->last_step || (s->ti % o.hist_steps) == 0) && !HistoryRecord(s, s->ti)) { return -1; }
       s->ti++;
       return 1;
    }
@@ -826,6 +879,8 @@ int laghos_sim_write_checkpoint(laghos_sim *s, const char *stem)
    return WriteCheckpointPiece(s, stem, s->ti - 1, nullptr) ? 0 : -1;
 }
 double laghos_sim_enorm(laghos_sim *s) { return s->hydro->ENorm(s->S); }
+// The LGH_DIAG_COUNT doubles of lgh_diagnostics for the state as it stands (collective on several ranks)
+void laghos_sim_diagnostics(laghos_sim *s, double *out) { s->hydro->Diagnostics(s->S, out); }
 double laghos_sim_energy(laghos_sim *s) { return s->hydro->InternalEnergy(s->S) + s->hydro->KineticEnergy(s->S); }
 void laghos_sim_sync(laghos_sim *s) { s->hydro->Sync(); }
 void laghos_sim_enable_timers(laghos_sim *s, int on) { s->hydro->EnableTimers(on != 0); }
@@ -966,6 +1021,34 @@ int laghos_host_read_checkpoint(const char *path, long *ints, double *dbls, unsi
    std::copy(c.pv_cycles.begin(), c.pv_cycles.end(), pv_cycles);
    return CKPT_OK;
 }
+// host-only: the `-hist` file logic (history.hpp).  The header line; one formatted row (returns its length, -1 when buf is too
+// small); and a whole file operation: keep_upto < 0 starts <path> anew, else the existing file is resumed as a restart from cycle
+// keep_upto does; then the lines of `rows` (each with its newline; may be empty) are appended one by one and the file is closed.
+// 0 = done and *rows_in_file set, -1 with the reason in msg otherwise.
+const char *laghos_host_history_header() { return kHistoryHeader; }
+int laghos_host_history_row(long cycle, double t, double dt, long rk_steps, long repeats, const double *diag, double energy_init, char *buf, int len)
+{
+   const std::string r = HistoryRow(cycle, t, dt, rk_steps, repeats, diag, energy_init);
+   if ((int)r.size() + 1 > len) { return -1; }
+   std::memcpy(buf, r.c_str(), r.size() + 1);
+   return (int)r.size();
+}
+int laghos_host_history_write(const char *path, long keep_upto, const char *rows, long *rows_in_file, char *msg, int msg_len)
+{
+   HistoryFile h;
+   std::string err;
+   bool ok = (keep_upto < 0) ? HistoryStart(h, path, err) : HistoryResume(h, path, keep_upto, err);
+   const std::string all = rows ? rows : "";
+   for (size_t pos = 0; ok && pos < all.size();)
+   {
+      const size_t nl = all.find('\n', pos), end = (nl == std::string::npos) ? all.size() : nl + 1;
+      ok = HistoryAppend(h, all.substr(pos, end - pos), err);
+      pos = end;
+   }
+   CkptMsg(err, msg, msg_len);
+   if (rows_in_file) { *rows_in_file = h.rows; }
+   return ok ? 0 : -1;
+}
 // Builds the discretisation of one rank and returns sizes; arrays are copied out
 // by laghos_host_disc_get.  kind: 0 h1map, 1 S0, 2 rho0_l2, 3 gamma, 4 rho0_q,
 // 5 ess[0], 6 ess[1], 7 ess[2], 8 owner, 9 W, 10 nbr_rank, 11.. nbr_nodes[k-11]
@@ -1088,6 +1171,7 @@ int laghos_main(int argc, const char *const *argv)
       std::cout << "Checkpoints: " << s->ckpt_count << " (fingerprint " << s->ckpt_seconds[0] << " s, copy " << s->ckpt_seconds[1] << " s, write "
                 << s->ckpt_seconds[2] << " s) -> " << CheckpointDir(o.basename) << std::endl;
    }
+   if (o.hist_steps > 0 && !o.quiet) { std::cout << "History: " << s->hist.path << ", " << s->hist.rows << " rows" << std::endl; }
    int ret = 0;
    if (o.check_exact_sedov)
    {

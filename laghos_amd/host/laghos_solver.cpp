@@ -255,6 +255,11 @@ void LagrangianHydroOperator::SampleFields(const Vector &S, const Vector &rho, i
                                 o + (2 * dim + 1) * NP, o + (2 * dim + 2) * NP));
 }
 
+void LagrangianHydroOperator::Diagnostics(const Vector &S, double out[LGH_DIAG_COUNT]) const
+{
+   LGH_VERIFY(lgh_diagnostics(ctx, S.Read(), out));
+}
+
 double LagrangianHydroOperator::AllReduce(double v, int op) const
 {
    if (disc.part.nranks > 1) { LGH_VERIFY(lgh_allreduce(ctx, &v, op)); }

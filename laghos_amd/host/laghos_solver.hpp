@@ -91,6 +91,10 @@ public:
    // Asynchronous on the context's stream; the quadrature data is not touched.
    void SampleFields(const Vector &S, const Vector &rho, int R, Vector &out) const;
    long SamplePoints(int R) const; // NE (R+1)^dim
+   // Conserved integrals, extremes of the point values and counts of bad points of the state S, folded over zones and ranks
+   // (lgh_diagnostics; the rows of the driver's `-hist` file).  Synchronous, collective on several ranks; reads S and the
+   // set-up data only - the quadrature data, the force products and dt_est stay as they are.
+   void Diagnostics(const Vector &S, double out[LGH_DIAG_COUNT]) const;
    void PrintTimingData(bool IamRoot, int steps, bool fom) const;
    const TimingData &Timing() const;
    void ResetTiming();

@@ -79,6 +79,13 @@ def load():
         L.laghos_host_write_checkpoint.argtypes = [ctypes.c_char_p, P, P, P, P, Lg, P, P, Lg, ctypes.c_char_p, I]
         L.laghos_host_read_checkpoint.restype = I
         L.laghos_host_read_checkpoint.argtypes = [ctypes.c_char_p, P, P, P, P, Lg, P, P, Lg, ctypes.c_char_p, I]
+        L.laghos_sim_diagnostics.argtypes = [P, P]
+        L.laghos_host_history_header.restype = ctypes.c_char_p
+        L.laghos_host_history_header.argtypes = []
+        L.laghos_host_history_row.restype = I
+        L.laghos_host_history_row.argtypes = [Lg, D, D, Lg, Lg, P, D, ctypes.c_char_p, I]
+        L.laghos_host_history_write.restype = I
+        L.laghos_host_history_write.argtypes = [ctypes.c_char_p, Lg, ctypes.c_char_p, ctypes.POINTER(Lg), ctypes.c_char_p, I]
         L.laghos_host_disc_create.restype = P
         L.laghos_host_disc_create.argtypes = [ctypes.c_char_p, I, I, I, I, D, I, I]
         L.laghos_host_disc_create_renumbered.restype = P
@@ -140,6 +147,14 @@ class Sim:
 
     def energy(self):
         return self.L.laghos_sim_energy(self.h)
+
+    def diagnostics(self):
+        """The conserved integrals, extremes and bad-point counts of the state as it stands (lgh_diagnostics; what a row of
+        the `-hist` file is made of), as a dict by name; every rank calls it."""
+        from .context import DIAG_COUNT, diagnostics_dict
+        out = np.full(DIAG_COUNT, np.nan)   # (an entry the library did not write would show)
+        self.L.laghos_sim_diagnostics(self.h, out.ctypes.data)
+        return diagnostics_dict(out)
 
     def sedov_error(self):
         """`-err`: L2 error of the density against the exact Sedov solution at t_final."""
@@ -261,6 +276,39 @@ def host_write_pvd(path, rel_dir, times, cycles, nranks=1):
     assert t.size == c.size
     if load().laghos_host_write_pvd(str(path).encode(), str(rel_dir).encode(), int(t.size), t.ctypes.data, c.ctypes.data, nranks) != 0:
         raise RuntimeError(f"cannot write {path}")
+
+
+HISTORY_COLUMNS = ("cycle", "t", "dt", "rk_steps", "repeats", "mass", "volume", "ie", "ke", "total", "d_total", "px", "py", "pz", "detj_min",
+                   "detj_min_rank", "detj_min_zone", "rho_min", "rho_max", "e_min", "e_max", "p_max", "v_max", "n_inverted", "n_negative_e",
+                   "n_nonfinite")
+
+
+def host_history_header():
+    """The first line of a `-hist` file (history.hpp), without its newline."""
+    return load().laghos_host_history_header().decode()
+
+
+def host_history_row(cycle, t, dt, rk_steps, repeats, diag, energy_init):
+    """One row of a `-hist` file, with its newline, from the 20 doubles of lgh_diagnostics."""
+    d = _f64(diag)
+    assert d.size == 20
+    buf = ctypes.create_string_buffer(2048)
+    n = load().laghos_host_history_row(int(cycle), float(t), float(dt), int(rk_steps), int(repeats), d.ctypes.data, float(energy_init), buf, len(buf))
+    if n < 0:
+        raise RuntimeError("host_history_row: the row does not fit")
+    return buf.value.decode()
+
+
+def host_history_write(path, rows="", keep_upto=None):
+    """The file operations of `-hist` without a GPU: keep_upto None starts `path` anew (header only), an int resumes it as
+    `-restart` from that cycle does (later rows and a partial last line dropped; a missing file started anew); the lines of
+    `rows` are then appended.  Returns the rows in the file; RuntimeError with the reason when a step fails."""
+    n = ctypes.c_long(-1)
+    msg = ctypes.create_string_buffer(1024)
+    rc = load().laghos_host_history_write(str(path).encode(), -1 if keep_upto is None else int(keep_upto), rows.encode(), ctypes.byref(n), msg, len(msg))
+    if rc != 0:
+        raise RuntimeError(msg.value.decode())
+    return n.value
 
 
 CKPT_INT_KEYS = ("dim", "problem", "order_v", "order_e", "Q1D", "NE", "global_NE", "N", "nranks", "rank", "pgrid0", "pgrid1", "pgrid2",

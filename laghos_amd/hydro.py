@@ -76,6 +76,11 @@ class HydroOperator:
                                             np.asarray(G_h1).T.copy(), np.asarray(B_l2).T.copy())
         return float(np.sqrt(err2))
 
+    def diagnostics(self, S):
+        """Conserved integrals, extremes and bad-point counts of the state S (Context.diagnostics): a dict by name.  Reads S
+        and the set-up data only; the quadrature data stays as it is."""
+        return self.ctx.diagnostics(S)
+
     def reset_time_step_estimate(self):
         self.ctx.set_dt_est(float("inf"))
 
