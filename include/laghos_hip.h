@@ -347,6 +347,34 @@ int lgh_diagnostics_zones(lgh_ctx *ctx, const double *S, double *zone_out);
 /* the same folded over zones and ranks; out is HOST memory; synchronous */
 int lgh_diagnostics(lgh_ctx *ctx, const double *S, double out[LGH_DIAG_COUNT]);
 
+/* ---- binned 1-D profiles of the flow (the driver's `-prof`): the point quantities of lgh_diagnostics above, and the
+ * position x_q = x_first + sum B (x - x_first), reduced into nbins uniform bins of a coordinate xi_q: x_q[axis], or the
+ * distance r_q = |x_q - origin| (axis 3).  n_q is the unit axis vector, or (x_q - origin) / r_q (v.n = 0 where r_q = 0).
+ * Bin index b = floor((xi_q - lo) * inv_w), inv_w = nbins / (hi - lo) formed once on the host; b < 0 goes to row 0,
+ * b >= nbins to row nbins + 1, else to row 1 + b.  A point that is NON-FINITE (detJ_q, e_q, a component of v_q or xi_q) or
+ * INVERTED (detJ_q <= 0) enters no row and is counted in n_excluded (summed over the ranks).  Columns of a row:
+ *    0 n (points, exact)   1 vol = sum w_q detJ_q   2 mass = sum m_q   3 ie = sum m_q e_q   4 ke = 1/2 sum m_q |v_q|^2
+ *    5 mom = sum m_q (v_q . n_q)   6 pv = sum w_q detJ_q p_q   7 mxi = sum m_q xi_q
+ *    8 rho_min, 9 rho_max over the row's points (+inf / -inf for an empty row; m_q > 0 is assumed)
+ * Columns 1-7 go through the exact integer accumulators of the velocity solve (lgh_vcg.hpp), counts and extremes through
+ * integer atomics: no floating-point atomic, and the same bits for every zone order, node numbering, launch grid and rank
+ * count.  An addend that is not finite (an overflowed product of finite factors) turns its (row, column) into NaN.
+ * out: HOST, (nbins + 2) rows of LGH_PROFILE_COLS doubles, row-major.  Synchronous; collective over the ranks of the context.
+ * Reads S, rho0DetJ0w, gamma, the tables and the maps and writes its outputs only (as lgh_diagnostics).  All dimensions.
+ * LGH_ERR_ARG without a launch: before lgh_setup_rho0detj0, a NULL argument, axis outside 0..3 or an axis >= dim, nbins
+ * outside 1..LGH_PROFILE_MAX_BINS, lo, hi or hi - lo not finite, lo >= hi, a non-finite origin component < dim for axis 3.
+ * LGH_PROFILE_FOLD=n (default 8): wavefronts whose points span more than n rows send one atomic per lane and limb instead
+ * of folding their lanes row by row first (0: always); the result has the same bits either way. */
+#define LGH_PROFILE_COLS 10
+#define LGH_PROFILE_MAX_BINS 4096
+typedef struct lgh_profile_spec {
+   int axis;          /* 0, 1, 2: the coordinate x, y, z (must be < dim); 3: r = |x_q - origin| */
+   int nbins;         /* 1 .. LGH_PROFILE_MAX_BINS */
+   double lo, hi;     /* finite, lo < hi; bin b covers [lo + b w, lo + (b+1) w), w = (hi - lo) / nbins */
+   double origin[3];  /* used by axis 3 only; components >= dim ignored */
+} lgh_profile_spec;
+int lgh_profile(lgh_ctx *ctx, const double *S, const lgh_profile_spec *spec, double *out, long *n_excluded);
+
 /* ---- timing data (TimingData, laghos_solver.hpp:39-56): seconds measured with
  * HIP events around the same regions as the reference stopwatches.
  * t[0..3] = cgH1, cgL2, force, qdata; c[0..2] = H1iter, L2iter, quad_tstep */
@@ -369,6 +397,7 @@ int lgh_enable_timers(lgh_ctx *ctx, int on);
 #define LGH_KERNEL_SAMPLE 8       /* lgh_sample_fields */
 #define LGH_KERNEL_FINGERPRINT 9  /* lgh_vec_fingerprint */
 #define LGH_KERNEL_DIAG 10        /* the zone kernel of lgh_diagnostics_zones / lgh_diagnostics */
+#define LGH_KERNEL_PROFILE 11     /* lgh_profile: both passes over the zones and the kernels between and behind them */
 int lgh_ktime_begin(lgh_ctx *ctx, int which, int max_samples);
 int lgh_ktime_end(lgh_ctx *ctx, int *launches, double *mean_seconds);
 /* Whether lgh_create found the 1-D H1 / L2 tables mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (any nodal or

@@ -34,6 +34,12 @@ class LghConfig(ctypes.Structure):
     ]
 
 
+class LghProfileSpec(ctypes.Structure):
+    """struct lgh_profile_spec (include/laghos_hip.h)."""
+    _fields_ = [("axis", ctypes.c_int), ("nbins", ctypes.c_int), ("lo", ctypes.c_double), ("hi", ctypes.c_double),
+                ("origin", ctypes.c_double * 3)]
+
+
 # every symbol include/laghos_hip.h declares: name -> (restype, argtypes)
 _I, _D, _P, _L = ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_long
 SYMBOLS = {
@@ -87,6 +93,7 @@ SYMBOLS = {
     "lgh_sample_fields": (_I, [_P, _P, _P, _I, c_dbl_p, c_dbl_p, _P, _P, _P, _P, _P]),
     "lgh_diagnostics_zones": (_I, [_P, _P, _P]),
     "lgh_diagnostics": (_I, [_P, _P, c_dbl_p]),
+    "lgh_profile": (_I, [_P, _P, ctypes.POINTER(LghProfileSpec), c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
     "lgh_get_timers": (_I, [_P, c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
     "lgh_reset_timers": (_I, [_P]),
     "lgh_enable_timers": (_I, [_P, _I]),

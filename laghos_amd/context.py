@@ -62,6 +62,29 @@ DIAG_ZONE_COUNT, DIAG_COUNT = 17, 20
 _DIAG_INTS = ("n_inverted", "n_negative_e", "n_nonfinite", "detj_min_zone", "detj_min_rank")
 
 
+# lgh_profile: the columns of a row (include/laghos_hip.h) and the axis names of Context.profile
+PROFILE_COLS = ("n", "vol", "mass", "ie", "ke", "mom", "pv", "mxi", "rho_min", "rho_max")
+PROFILE_MAX_BINS = 4096
+PROFILE_AXES = {"x": 0, "y": 1, "z": 2, "r": 3}
+
+
+def profile_dict(rows, n_excluded, lo, hi):
+    """what Context.profile returns, from the (nbins + 2, 10) rows of lgh_profile: the raw rows, the bin edges and the
+    derived curves of the inner rows - rho = mass / vol, e = ie / mass, v = mom / mass, p = pv / vol, xi = mxi / mass, NaN
+    where the divisor is 0"""
+    nbins = rows.shape[0] - 2
+    inner = rows[1:-1]
+    col = {k: inner[:, i] for i, k in enumerate(PROFILE_COLS)}
+
+    def ratio(a, b):
+        out = np.full(nbins, np.nan)
+        np.divide(a, b, out=out, where=(b != 0))
+        return out
+    return dict(rows=rows, n_excluded=int(n_excluded), edges=lo + (hi - lo) * np.arange(nbins + 1) / nbins,
+                rho=ratio(col["mass"], col["vol"]), e=ratio(col["ie"], col["mass"]), v=ratio(col["mom"], col["mass"]),
+                p=ratio(col["pv"], col["vol"]), xi=ratio(col["mxi"], col["mass"]))
+
+
 def diagnostics_dict(out):
     """the 20 doubles of lgh_diagnostics by name"""
     return {k: (int(out[i]) if k in _DIAG_INTS else float(out[i])) for i, k in enumerate(DIAG_NAMES)}
@@ -441,6 +464,23 @@ class Context:
         out = np.full(DIAG_COUNT, np.nan)   # (an entry the library did not write would show)
         check(self.lib.lgh_diagnostics(self.h, _ptr(S), _dbl(out)))
         return out if raw else diagnostics_dict(out)
+
+    def profile(self, S, axis, nbins, lo, hi, origin=None):
+        """lgh_profile: the flow binned along a coordinate - axis 0, 1, 2 (or "x", "y", "z") or 3 ("r", the distance from
+        `origin`) - into nbins uniform bins of [lo, hi): a dict with `rows` ((nbins + 2, 10), PROFILE_COLS; row 0 below lo,
+        the last row at or above hi), `n_excluded`, `edges` and the derived rho, e, v, p, xi of the inner rows
+        (profile_dict).  Exact, order-free sums: the same bits for every numbering, grid and rank count.  Synchronous."""
+        from ._lib import LghProfileSpec
+        spec = LghProfileSpec()
+        spec.axis, spec.nbins, spec.lo, spec.hi = int(PROFILE_AXES.get(axis, axis)), int(nbins), float(lo), float(hi)
+        o = np.zeros(3) if origin is None else np.asarray(origin, dtype=np.float64).reshape(-1)
+        for k in range(min(3, o.size)):
+            spec.origin[k] = float(o[k])
+        n_rows = max(0, min(int(nbins), PROFILE_MAX_BINS)) + 2
+        rows = np.full((n_rows, len(PROFILE_COLS)), np.nan)   # (an entry the library did not write would show)
+        n_excl = ctypes.c_long(-1)
+        check(self.lib.lgh_profile(self.h, _ptr(S), ctypes.byref(spec), _dbl(rows), ctypes.byref(n_excl)))
+        return profile_dict(rows, n_excl.value, spec.lo, spec.hi)
 
     def solve_energy_begin(self, S, v, dS, e_rhs, rel_tol, max_iter, e_source=None):
         check(self.lib.lgh_solve_energy_begin(self.h, _ptr(S), _ptr(v), _ptr(dS), _ptr(e_rhs),

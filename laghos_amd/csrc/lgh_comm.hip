@@ -656,6 +656,20 @@ int allreduce_dev(lgh_ctx *c, double *dev, int count, int op, bool packed)
    return LGH_OK;
 }
 
+// Any number of values: the loopback transports stage 8 doubles at a time, RCCL takes them all at once
+int allreduce_dev_n(lgh_ctx *c, double *dev, long count, int op)
+{
+   const Comm *cm = c->comm;
+   const long piece = (cm && (cm->local || cm->shm)) ? 8 : (1L << 24);
+   for (long i = 0; i < count; i += piece)
+   {
+      const long n = std::min(piece, count - i);
+      const int rc = allreduce_dev(c, dev + i, (int)n, op);
+      if (rc) { return rc; }
+   }
+   return LGH_OK;
+}
+
 } // namespace lgh
 
 using namespace lgh;

@@ -200,6 +200,8 @@ struct lgh_ctx
    double *me_fac;       // 1D: NE * L1D^2, Cholesky factors of the zone mass matrices Me(z) of the energy solve (lgh_1d.hip)
    int setup_done;       // lgh_setup_rho0detj0 has run: rho0DetJ0w holds the masses of the points (lgh_diagnostics refuses before)
    double *diag_dev;     // lgh_diagnostics (lgh_diag.hip): 32 doubles of folded values, then the 17 zone arrays; allocated on first use
+   void *prof_dev = nullptr; // lgh_profile (lgh_profile.hip): accumulator words, flags, maxima and the packed rows for prof_rows rows;
+   int prof_rows = 0;        // allocated at the first call, regrown only when nbins grows
    unsigned long long *fp_dev; // lgh_vec_fingerprint (lgh_fingerprint.hip): the two words of the result and the workgroups' partial words, allocated on first use
 };
 
@@ -561,6 +563,7 @@ bool comm_second_channel(const lgh_ctx *c); // reductions may run on the context
 // peer words - integers, so every rank gets the same bits whatever the arrival order.  All-pairs partitions only.
 int exchange_words(lgh_ctx *c, const long long *src, int nwords);
 int comm_word_peers(lgh_ctx *c, int nwords, const long long **peers, int *n_peers); // (allocates the peer buffer on first use)
+int allreduce_dev_n(lgh_ctx *c, double *dev, long count, int op); // any count: in pieces of what the transport takes at a time
 int allreduce_dev(lgh_ctx *c, double *dev, int count, int op, bool packed = false); // packed: as halo_sum (sums that travel as one exchange with every peer only)
 
 // ---- lgh_1d.hip: the 1D path (the entry points send a context with dim == 1 there; the 2D/3D kernels never see one)

@@ -16,6 +16,7 @@
 // allow, one at Q5Q4 in 3D); every value is the same serial sum either way.
 // diag_fold_k then folds each of the 17 zone arrays in ascending zone id with one workgroup of fixed shape.
 #include "lgh_common.hpp"
+#include "lgh_diag.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -39,21 +40,6 @@ struct DiagArgs
 __host__ __device__ constexpr int diag_kind(const int k)
 {
    return (k <= 6 || k >= 14) ? 0 : ((k == 7 || k == 8 || k == 10) ? 1 : 2);
-}
-
-template <int DIM>
-__device__ __forceinline__ int ipow_c(const int b)
-{
-   return (DIM == 3) ? b * b * b : (DIM == 2 ? b * b : b);
-}
-
-// one contraction of n terms: sum_d T[Q d] u[stride d]
-__device__ __forceinline__ double diag_dot(const int n, const int Q, const double *__restrict__ T, const double *__restrict__ u,
-                                           const int stride)
-{
-   double s = 0.0;
-   for (int d = 0; d < n; d++) { s += T[Q * d] * u[stride * d]; }
-   return s;
 }
 
 template <int DIM>

@@ -29,6 +29,7 @@
 #include "vtk_output.hpp"
 #include "checkpoint.hpp"
 #include "history.hpp"
+#include "profile.hpp"
 
 using namespace laghos;
 
@@ -76,6 +77,14 @@ struct Options
    int ckpt_keep = 2;              // -ckpt-keep K: pieces of this run kept per rank (0: all)
    std::string restart;            // -restart PATH: a checkpoint stem, or "latest" (<basename>_restart/latest)
    int hist_steps = 0;             // -hist N: a row of <basename>_history.csv at cycle 0, after every accepted step with ti % N == 0 and after the last one (0: none)
+   // -prof N: a binned 1-D profile of the flow (lgh_profile) in <basename>_profile_<cycle>.csv at cycle 0, after every accepted step
+   // with ti % N == 0 and after the last one (0: none); profile.hpp, DESIGN.md §7e
+   int prof_steps = 0;
+   std::string prof_axis;          // -prof-axis x|y|z|r (default: r for -p 1, else x)
+   int prof_bins = 64;             // -prof-bins B
+   bool prof_range_set = false;    // -prof-range LO HI (default: from the initial mesh, at cycle 0)
+   double prof_lo = 0, prof_hi = 0;
+   double prof_origin[3] = {0, 0, 0}; // -prof-origin X [Y [Z]] (default: the blast position of -err, the origin)
    bool fingerprint = false;       // -fp: rank 0 prints the state fingerprint after the last step and per checkpoint
 };
 
@@ -124,6 +133,64 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
          if (!(v = need(i))) { return false; }
          o.hist_steps = std::atoi(v);
          if (o.hist_steps < 1) { err = "-hist / --history-steps must be at least 1, got " + std::string(v); return false; }
+         continue;
+      }
+      if (a == "-prof" || a == "--profile-steps")
+      {
+         if (!(v = need(i))) { return false; }
+         o.prof_steps = std::atoi(v);
+         if (o.prof_steps < 1) { err = "-prof / --profile-steps must be at least 1, got " + std::string(v); return false; }
+         continue;
+      }
+      if (a == "-prof-axis" || a == "--profile-axis")
+      {
+         if (!(v = need(i))) { return false; }
+         o.prof_axis = v;
+         if (o.prof_axis != "x" && o.prof_axis != "y" && o.prof_axis != "z" && o.prof_axis != "r") { err = "-prof-axis must be x, y, z or r, got " + o.prof_axis; return false; }
+         continue;
+      }
+      if (a == "-prof-bins" || a == "--profile-bins")
+      {
+         if (!(v = need(i))) { return false; }
+         o.prof_bins = std::atoi(v);
+         if (o.prof_bins < 1 || o.prof_bins > LGH_PROFILE_MAX_BINS)
+         {
+            err = "-prof-bins must be between 1 and " + std::to_string(LGH_PROFILE_MAX_BINS) + ", got " + std::string(v);
+            return false;
+         }
+         continue;
+      }
+      if (a == "-prof-range" || a == "--profile-range")
+      {
+         double lh[2];
+         for (int k = 0; k < 2; k++)
+         {
+            if (!(v = need(i))) { return false; }
+            char *end = nullptr;
+            lh[k] = std::strtod(v, &end);
+            if (end == v || *end) { err = "-prof-range needs two numbers, got " + std::string(v); return false; }
+         }
+         if (!(std::isfinite(lh[0]) && std::isfinite(lh[1]) && std::isfinite(lh[1] - lh[0]) && lh[0] < lh[1]))
+         {
+            err = "-prof-range LO HI needs finite LO < HI";
+            return false;
+         }
+         o.prof_lo = lh[0]; o.prof_hi = lh[1]; o.prof_range_set = true;
+         continue;
+      }
+      if (a == "-prof-origin" || a == "--profile-origin")
+      {
+         int n = 0;
+         while (n < 3 && i + 1 < argc) // one to three numbers
+         {
+            char *end = nullptr;
+            const double x = std::strtod(argv[i + 1], &end);
+            if (end == argv[i + 1] || *end) { break; }
+            if (!std::isfinite(x)) { err = "-prof-origin needs finite coordinates"; return false; }
+            o.prof_origin[n++] = x;
+            i++;
+         }
+         if (n == 0) { err = "-prof-origin needs one to three numbers"; return false; }
          continue;
       }
       if (a == "-restart" || a == "--restart")
@@ -321,6 +388,14 @@ struct laghos_sim
    // -hist: the file (rank 0) and the last cycle that has its row (a restart: the checkpoint's cycle, which gets none)
    HistoryFile hist;
    int hist_last = -1;
+   // -prof: what is binned (axis, range and origin fixed at the start, from the initial mesh), the last cycle that has its file (a
+   // restart: the checkpoint's cycle, which gets none), the files of this run, the table, and the exact Sedov solution where it applies
+   lgh_profile_spec prof_spec = {};
+   char prof_axis = 'x';
+   int prof_last = -1, prof_files = 0;
+   std::vector<double> prof_rows;
+   bool prof_exact = false;
+   double prof_par[21] = {};
    int steps_at_start = 0;             // RK steps the checkpoint of a restart had taken: timing / FOM cover the restarted segment
 };
 
@@ -527,6 +602,88 @@ static bool HistoryOpen(laghos_sim *s, int resume_cycle)
    return true;
 }
 
+// -prof: axis, origin and range of the profiles.  The default range comes from the INITIAL mesh S0 (which a restart rebuilds as
+// every run does), over all ranks: the bounding box along an axis, 0 to the largest distance of a node from the origin for r.
+static void ProfileSetup(laghos_sim *s, const std::vector<double> &S0)
+{
+   const Options &o = s->opt;
+   const Discretization &d = *s->disc;
+   lgh_profile_spec &sp = s->prof_spec;
+   s->prof_axis = o.prof_axis[0];
+   sp.axis = (s->prof_axis == 'r') ? 3 : s->prof_axis - 'x';
+   sp.nbins = o.prof_bins;
+   for (int k = 0; k < 3; k++) { sp.origin[k] = (k < d.dim) ? o.prof_origin[k] : 0.0; }
+   sp.lo = o.prof_lo; sp.hi = o.prof_hi;
+   if (!o.prof_range_set)
+   {
+      double lo = INFINITY, hi = -INFINITY;
+      for (long n = 0; n < d.N; n++)
+      {
+         double xi;
+         if (sp.axis < 3) { xi = S0[(size_t)sp.axis * d.N + n]; }
+         else
+         {
+            double r2 = 0.0;
+            for (int c = 0; c < d.dim; c++) { const double dx = S0[(size_t)c * d.N + n] - sp.origin[c]; r2 += dx * dx; }
+            xi = std::sqrt(r2);
+         }
+         lo = std::min(lo, xi); hi = std::max(hi, xi);
+      }
+      sp.lo = (sp.axis == 3) ? 0.0 : s->hydro->AllReduce(lo, 1);
+      sp.hi = -s->hydro->AllReduce(-hi, 1);
+   }
+   s->prof_rows.assign((size_t)(sp.nbins + 2) * LGH_PROFILE_COLS, 0.0);
+   // the exact solution beside the curves: where -err is accepted (problem 1 on the default mesh, blast at the origin) and the axis is r
+   s->prof_exact = o.problem == 1 && o.mesh_file.compare(0, 7, "default") == 0 && sp.axis == 3 && sp.origin[0] == 0.0 && sp.origin[1] == 0.0 &&
+                   sp.origin[2] == 0.0;
+   if (s->prof_exact && o.rank == 0)
+   {
+      SedovSol asol(o.dim, 1.4, 1.0, o.blast_energy, 0.0);
+      std::copy(asol.par, asol.par + 21, s->prof_par);
+   }
+}
+
+// The `-prof` file of the state as it stands, cycle `cycle`: the table on the GPU (collective), the file by rank 0.  Every rank
+// learns whether it was written.
+static bool ProfileRecord(laghos_sim *s, int cycle)
+{
+   const Options &o = s->opt;
+   auto &hydro = *s->hydro;
+   const lgh_profile_spec &sp = s->prof_spec;
+   long n_excl = 0;
+   hydro.Profile(s->S, sp, s->prof_rows.data(), &n_excl);
+   bool ok = true;
+   std::string err;
+   if (o.rank == 0)
+   {
+      const int R = sp.nbins + 2;
+      std::vector<double> exact;
+      if (s->prof_exact)
+      {
+         exact.assign((size_t)3 * R, NAN);
+         std::vector<int> row;
+         std::vector<double> r, rho, v, p;
+         for (int k = 0; k < R && s->t > 0.0; k++) // (t = 0: the blast has no extent yet; rows without mass have no xi)
+         {
+            const double *d = s->prof_rows.data() + (size_t)k * LGH_PROFILE_COLS;
+            if (d[2] != 0.0 && std::isfinite(d[7] / d[2])) { row.push_back(k); r.push_back(d[7] / d[2]); }
+         }
+         if (!r.empty()) { hydro.SedovEval(s->prof_par, s->t, r, rho, v, p); }
+         for (size_t j = 0; j < row.size(); j++) { exact[3 * row[j]] = rho[j]; exact[3 * row[j] + 1] = v[j]; exact[3 * row[j] + 2] = p[j]; }
+      }
+      ok = ProfileWrite(ProfilePath(o.basename, cycle),
+                        ProfileText(cycle, s->t, s->prof_axis, sp.origin, sp.lo, sp.hi, sp.nbins, n_excl, s->prof_rows.data(),
+                                    s->prof_exact ? exact.data() : nullptr),
+                        err);
+   }
+   const bool all_ok = hydro.AllReduce(ok ? 1.0 : 0.0, 1) == 1.0;
+   if (!ok) { return SimFail(s, "cannot write the -prof file: " + err); }
+   if (!all_ok) { return SimFail(s, "rank 0 could not write the -prof file"); }
+   s->prof_last = cycle;
+   s->prof_files++;
+   return true;
+}
+
 extern "C"
 {
 
@@ -572,6 +729,12 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
       {
          o.p_assembly = false;
          if (rank == 0 && !o.quiet) { std::cout << "Laghos does not support PA in 1D. Switching to FA." << std::endl; }
+      }
+      if (o.prof_axis.empty()) { o.prof_axis = (o.problem == 1) ? "r" : "x"; }
+      if (o.prof_steps > 0 && o.prof_axis != "r" && o.prof_axis[0] - 'x' >= o.dim)
+      {
+         std::fprintf(stderr, "laghos: -prof-axis %s needs a mesh of %d dimensions, this one has %d\n", o.prof_axis.c_str(), o.prof_axis[0] - 'x' + 1, o.dim);
+         return nullptr;
       }
       if (!o.p_assembly && o.dim != 1)
       {
@@ -675,6 +838,7 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
       const bool keep_in_registers = o.ode_solver_type != 7 && d.dim == 3 && !o.store_stress && !(senv && senv[0] == '1');
       if (keep_in_registers) { LGH_VERIFY(lgh_qupdate_store_stress(s->hydro->Context(), 0)); }
    }
+   if (o.prof_steps > 0) { ProfileSetup(s.get(), S0); }
    if (restarting)
    {
       // the set-up data came from S0 as in every run; the state now comes from the file and must have arrived in HBM intact
@@ -722,6 +886,7 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
                    << std::setprecision(6) << std::endl;
       }
       if (o.hist_steps > 0 && !HistoryOpen(s.get(), h.ti)) { return nullptr; } // (no row for the checkpoint's own state: the run that wrote it has)
+      s->prof_last = h.ti;                                                     // (nor a profile)
       // a checkpoint written after the last step: nothing is left to do
       if (s->t >= o.t_final || (o.max_tsteps >= 0 && s->steps > o.max_tsteps)) { s->last_step = true; }
       return s.release();
@@ -735,6 +900,7 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
    s->dt = s->hydro->GetTimeStepEstimate(s->S);                                      // :708
    if (o.paraview && !DumpParaview(s.get(), 0)) { return nullptr; }                   // :691-701
    if (o.hist_steps > 0 && !(HistoryOpen(s.get(), -1) && HistoryRecord(s.get(), 0))) { return nullptr; }
+   if (o.prof_steps > 0 && !ProfileRecord(s.get(), 0)) { return nullptr; }
    return s.release();
 }
 
@@ -784,6 +950,7 @@ int laghos_sim_step(laghos_sim *s)
          if (s->last_step && o.ckpt_steps > 0 && s->ti > 1 && !PeriodicCheckpoint(s, s->ti - 1)) { return -1; }
          // ... and the row "after the last step", unless that step has its row already (repeated steps themselves write none)
          if (s->last_step && o.hist_steps > 0 && s->ti - 1 > s->hist_last && !HistoryRecord(s, s->ti - 1)) { return -1; }
+         if (s->last_step && o.prof_steps > 0 && s->ti - 1 > s->prof_last && !ProfileRecord(s, s->ti - 1)) { return -1; } // (the same rule)
          continue;
       }
       else if (dt_est > 1.25 * s->dt) { s->dt *= 1.02; }
@@ -823,6 +990,7 @@ int laghos_sim_step(laghos_sim *s)
       }
       if (o.ckpt_steps > 0 && (s->last_step || (s->ti % o.ckpt_steps) == 0) && !PeriodicCheckpoint(s, s->ti)) { return -1; }
       if (o.hist_steps > 0 && (s->last_step || (s->ti % o.hist_steps) == 0) && !HistoryRecord(s, s->ti)) { return -1; }
+      if (o.prof_steps > 0 && (s->last_step || (s->ti % o.prof_steps) == 0) && !ProfileRecord(s, s->ti)) { return -1; }
       s->ti++;
       return 1;
    }
@@ -881,6 +1049,17 @@ int laghos_sim_write_checkpoint(laghos_sim *s, const char *stem)
 double laghos_sim_enorm(laghos_sim *s) { return s->hydro->ENorm(s->S); }
 // The LGH_DIAG_COUNT doubles of lgh_diagnostics for the state as it stands (collective on several ranks)
 void laghos_sim_diagnostics(laghos_sim *s, double *out) { s->hydro->Diagnostics(s->S, out); }
+// lgh_profile of the state as it stands (collective on several ranks): axis 0..2 or 3 = r, rows = (nbins + 2) x LGH_PROFILE_COLS
+// doubles, origin = 3 doubles.  0 = ok; otherwise laghos_sim_error() has the library's message and nothing was written.
+int laghos_sim_profile(laghos_sim *s, int axis, int nbins, double lo, double hi, const double *origin, double *rows, long *n_excluded)
+{
+   lgh_profile_spec sp = {};
+   sp.axis = axis; sp.nbins = nbins; sp.lo = lo; sp.hi = hi;
+   for (int k = 0; k < 3; k++) { sp.origin[k] = origin ? origin[k] : 0.0; }
+   const int rc = lgh_profile(s->hydro->Context(), s->S.Read(), &sp, rows, n_excluded);
+   if (rc != 0) { s->error = lgh_last_error(); }
+   return rc;
+}
 double laghos_sim_energy(laghos_sim *s) { return s->hydro->InternalEnergy(s->S) + s->hydro->KineticEnergy(s->S); }
 void laghos_sim_sync(laghos_sim *s) { s->hydro->Sync(); }
 void laghos_sim_enable_timers(laghos_sim *s, int on) { s->hydro->EnableTimers(on != 0); }
@@ -1172,6 +1351,7 @@ int laghos_main(int argc, const char *const *argv)
                 << s->ckpt_seconds[2] << " s) -> " << CheckpointDir(o.basename) << std::endl;
    }
    if (o.hist_steps > 0 && !o.quiet) { std::cout << "History: " << s->hist.path << ", " << s->hist.rows << " rows" << std::endl; }
+   if (o.prof_steps > 0 && !o.quiet) { std::cout << "Profiles: " << s->prof_files << " files, " << o.basename << "_profile_*.csv" << std::endl; }
    int ret = 0;
    if (o.check_exact_sedov)
    {

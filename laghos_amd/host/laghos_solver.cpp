@@ -260,6 +260,28 @@ void LagrangianHydroOperator::Diagnostics(const Vector &S, double out[LGH_DIAG_C
    LGH_VERIFY(lgh_diagnostics(ctx, S.Read(), out));
 }
 
+void LagrangianHydroOperator::Profile(const Vector &S, const lgh_profile_spec &spec, double *rows, long *n_excluded) const
+{
+   LGH_VERIFY(lgh_profile(ctx, S.Read(), &spec, rows, n_excluded));
+}
+
+void LagrangianHydroOperator::SedovEval(const double par[21], double t, const std::vector<double> &r, std::vector<double> &rho,
+                                        std::vector<double> &v, std::vector<double> &p) const
+{
+   const long n = (long)r.size();
+   Vector dev(4 * n);
+   std::vector<double> h(4 * n, 0.0);
+   std::copy(r.begin(), r.end(), h.begin());
+   dev.FromHost(h);
+   double *d = dev.Write();
+   LGH_VERIFY(lgh_sedov_eval(ctx, par, t, n, d, d + n, d + 2 * n, d + 3 * n));
+   Sync();
+   dev.ToHost(h);
+   rho.assign(h.begin() + n, h.begin() + 2 * n);
+   v.assign(h.begin() + 2 * n, h.begin() + 3 * n);
+   p.assign(h.begin() + 3 * n, h.end());
+}
+
 double LagrangianHydroOperator::AllReduce(double v, int op) const
 {
    if (disc.part.nranks > 1) { LGH_VERIFY(lgh_allreduce(ctx, &v, op)); }

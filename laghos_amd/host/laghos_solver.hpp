@@ -95,6 +95,12 @@ public:
    // (lgh_diagnostics; the rows of the driver's `-hist` file).  Synchronous, collective on several ranks; reads S and the
    // set-up data only - the quadrature data, the force products and dt_est stay as they are.
    void Diagnostics(const Vector &S, double out[LGH_DIAG_COUNT]) const;
+   // The state S binned along a coordinate (lgh_profile; the driver's `-prof` files): rows = (nbins + 2) x LGH_PROFILE_COLS host
+   // doubles.  Synchronous, collective on several ranks; reads what Diagnostics reads and leaves alone what it leaves alone.
+   void Profile(const Vector &S, const lgh_profile_spec &spec, double *rows, long *n_excluded) const;
+   // The exact Sedov solution `par` at time t at n radii (host arrays in and out; lgh_sedov_eval on the GPU)
+   void SedovEval(const double par[21], double t, const std::vector<double> &r, std::vector<double> &rho, std::vector<double> &v,
+                  std::vector<double> &p) const;
    void PrintTimingData(bool IamRoot, int steps, bool fom) const;
    const TimingData &Timing() const;
    void ResetTiming();

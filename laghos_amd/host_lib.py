@@ -80,6 +80,8 @@ def load():
         L.laghos_host_read_checkpoint.restype = I
         L.laghos_host_read_checkpoint.argtypes = [ctypes.c_char_p, P, P, P, P, Lg, P, P, Lg, ctypes.c_char_p, I]
         L.laghos_sim_diagnostics.argtypes = [P, P]
+        L.laghos_sim_profile.restype = I
+        L.laghos_sim_profile.argtypes = [P, I, I, D, D, P, P, ctypes.POINTER(Lg)]
         L.laghos_host_history_header.restype = ctypes.c_char_p
         L.laghos_host_history_header.argtypes = []
         L.laghos_host_history_row.restype = I
@@ -155,6 +157,22 @@ class Sim:
         out = np.full(DIAG_COUNT, np.nan)   # (an entry the library did not write would show)
         self.L.laghos_sim_diagnostics(self.h, out.ctypes.data)
         return diagnostics_dict(out)
+
+    def profile(self, axis, nbins, lo, hi, origin=None):
+        """The state as it stands binned along x, y, z or the distance r from `origin` (lgh_profile; what a `-prof` file is
+        made of): the dict of Context.profile; every rank calls it."""
+        from .context import PROFILE_AXES, PROFILE_COLS, PROFILE_MAX_BINS, profile_dict
+        o = np.zeros(3)
+        if origin is not None:
+            g = np.asarray(origin, dtype=np.float64).reshape(-1)[:3]
+            o[:g.size] = g
+        rows = np.full((max(0, min(int(nbins), PROFILE_MAX_BINS)) + 2, len(PROFILE_COLS)), np.nan)
+        n_excl = ctypes.c_long(-1)
+        rc = self.L.laghos_sim_profile(self.h, int(PROFILE_AXES.get(axis, axis)), int(nbins), float(lo), float(hi), o.ctypes.data,
+                                       rows.ctypes.data, ctypes.byref(n_excl))
+        if rc != 0:
+            raise RuntimeError(f"laghos_sim_profile: error {rc}: {self.L.laghos_sim_error(self.h).decode()}")
+        return profile_dict(rows, n_excl.value, float(lo), float(hi))
 
     def sedov_error(self):
         """`-err`: L2 error of the density against the exact Sedov solution at t_final."""

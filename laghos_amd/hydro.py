@@ -81,6 +81,11 @@ class HydroOperator:
         and the set-up data only; the quadrature data stays as it is."""
         return self.ctx.diagnostics(S)
 
+    def profile(self, S, axis, nbins, lo, hi, origin=None):
+        """The state S binned along x, y, z or the distance from `origin` (Context.profile): exact, order-free bin sums and
+        the curves derived from them.  Reads S and the set-up data only; the quadrature data stays as it is."""
+        return self.ctx.profile(S, axis, nbins, lo, hi, origin)
+
     def reset_time_step_estimate(self):
         self.ctx.set_dt_est(float("inf"))
 
