@@ -102,6 +102,8 @@ def _run_case(prob, monkeypatch, variant, form, rank1, first):
         g.close()
         o.close()
     tol = 2e-12 if rank1 else 1e-13
+    print(f"FIG k1-{'compact' if rank1 else 'stored'} {expect} E-vector {max(rel_err(yE[c], yE_o[c]) for c in range(3)):.2e}"
+          f" den {max(abs(den[c] - den_o[c]) / abs(den_o[c]) for c in range(3)):.2e}")
     for c in range(3):
         assert rel_err(yE[c], yE_o[c]) < tol, (c, "E-vector")
         assert abs(den[c] - den_o[c]) <= tol * abs(den_o[c]), (c, "den", den[c], den_o[c])

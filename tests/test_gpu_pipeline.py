@@ -528,6 +528,13 @@ MULTI_RANK_CASES = [
     (8, (16, 16, 16), 1, 0, (3, 2), {"LGH_VCG_VARIANT": "4", "LGH_COMM2": "0", "LGH_RENUMBER": "mfem", "LGH_HALO_FUSED_PACK": "0", "_lockstep": "0"}),
     (8, (16, 16, 16), 1, 0, (3, 2), {"LGH_VCG_VARIANT": "4", "_lockstep": "0"}),  # (second channel: the energy solve beside the velocity solve)
     (8, (16, 16, 16), 1, 1, (3, 2), {"LGH_VCG_VARIANT": "4", "LGH_COMM2": "0", "_lockstep": "0"}),  # (region timers: sequential semantics)
+    # blocks that are no powers of two (tests/shape_cases.py), slab K1: 5 x 3 x 2 per rank - every set a chain, the ranks share
+    # an x-face; 7 x 3 x 1 - sets at every offset of a row; 5 x 2 x 2 in a 3 x 1 x 1 partition (not all-pairs); and the two
+    # ranks again on one communicator with the energy CG in lockstep
+    (2, (10, 3, 2), 1, 0, (3, 2), {"LGH_VCG_VARIANT": "4"}),
+    (8, (14, 6, 2), 1, 0, (3, 2), {"LGH_VCG_VARIANT": "4"}),
+    (3, (15, 2, 2), 1, 1, (3, 2), {"LGH_VCG_VARIANT": "4"}),
+    (2, (10, 3, 2), 1, 0, (3, 2), {"LGH_VCG_VARIANT": "4", "LGH_COMM2": "0", "_lockstep": "1"}),
 ]
 
 
