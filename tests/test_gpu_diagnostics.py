@@ -409,7 +409,21 @@ def test_refused_before_the_setup():
         c.close()
 
 
+MESH_3D = ["-dim", 3, "-nx", 4, "-ny", 2, "-nz", 2, "-Sx", 2, "-Sy", 1, "-Sz", 1]
+MESH_2D = ["-dim", 2, "-nx", 4, "-ny", 2, "-Sx", 2, "-Sy", 1]
+
+
 def test_two_emulated_ranks():
+    """3D, 4 x 2 x 2 zones on two ranks: see _two_emulated_ranks"""
+    _two_emulated_ranks(MESH_3D)
+
+
+def test_two_emulated_ranks_2d():
+    """the same on 2D blocks: 4 x 2 zones on two ranks (momentum has two components: p_z stays 0)"""
+    _two_emulated_ranks(MESH_2D)
+
+
+def _two_emulated_ranks(mesh_args):
     """3D, 4 x 2 x 2 zones, Q2Q1 on two ranks (threads, "LGHLOCAL" communicator).
     At the initial state (the same bits on every partition, so the point values are) against the one-rank run of the same
     problem: both ranks return the same array; sums to the sum bound, extremes and counts exactly; slot 18 is the rank whose
@@ -421,8 +435,8 @@ def test_two_emulated_ranks():
     import torch
     from laghos_amd import _lib, host_lib
     from laghos_amd.context import DIAG_COUNT, DIAG_ZONE_COUNT
-    args = ["-dim", 3, "-nx", 4, "-ny", 2, "-nz", 2, "-Sx", 2, "-Sy", 1, "-Sz", 1, "-rs", 0, "-p", 1, "-ok", 2, "-ot", 1, "-pa",
-            "-tf", 1e9, "-ms", 10 ** 6, "-vs", 10 ** 9, "-q"]
+    dim = mesh_args[1]
+    args = mesh_args + ["-rs", 0, "-p", 1, "-ok", 2, "-ot", 1, "-pa", "-tf", 1e9, "-ms", 10 ** 6, "-vs", 10 ** 9, "-q"]
     L = _lib.load()
 
     def look(sim):
@@ -465,7 +479,7 @@ def test_two_emulated_ranks():
     assert np.array_equal(a.view(np.uint64), b.view(np.uint64))
     sizes = one[0][1]
     assert two[0][1]["NE"] == two[1][1]["NE"] == sizes["NE"] // 2
-    nterms, ND = sizes["global_NE"] * sizes["NQ"], sizes["D1D"] ** 3
+    nterms, ND = sizes["global_NE"] * sizes["NQ"], sizes["D1D"] ** dim
     for k in SUMS:
         # every term of mass, volume, ie and ke is non-negative here, so sum |term| is the sum; the fluid is at rest: momentum is 0
         print(f"{NAMES[k]}: two ranks {a[k]!r}, one rank {ref[k]!r}")
@@ -485,7 +499,7 @@ def test_two_emulated_ranks():
     g, g1 = two[0][3][0], two[1][3][0]
     assert not np.isnan(g).any() and np.array_equal(g.view(np.uint64), g1.view(np.uint64))
     z = np.concatenate([two[0][3][1], two[1][3][1]], axis=1)           # [17, global NE]
-    assert g[3] > 0 and g[13] > 0 and all(g[k] != 0 for k in (4, 5, 6))  # ke, v_max, momentum: values of their own
+    assert g[3] > 0 and g[13] > 0 and all(g[k] != 0 for k in (4, 5, 6)[:dim])  # ke, v_max, momentum: values of their own
     for k in SUMS:
         print(f"after two steps, {NAMES[k]}: {g[k]!r}, sum of the zone arrays {z[k].sum()!r}")
         assert abs(g[k] - z[k].sum()) <= (sizes["global_NE"] + 3 * ND + 8) * EPS * np.abs(z[k]).sum(), NAMES[k]

@@ -4,6 +4,7 @@ full sizes the size-independent properties of the operators are checked."""
 import numpy as np
 import pytest
 
+import rank_cases as rc
 from helpers import deformed_state, make_gpu, rel_err, seeded
 
 pytestmark = pytest.mark.gpu
@@ -327,16 +328,12 @@ def test_cpp_driver_unknown_kernel():
     assert "Unknown kernel" in (p.stderr + p.stdout)
 
 
-def test_multi_rank_code_path_on_one_gpu():
-    """LGH_FORCE_MULTI=1: communicator of size 1, so the multi-GPU sequencing
-    (separate E->L gather, halo hook, ncclAllReduce of den / (r,z) / dt on the
-    context stream, finish kernels) runs for real on this single-GPU box and must
-    reproduce the fused single-rank path."""
+def _force_multi_parity(mesh_args):
     import json
     import subprocess
     import sys
     code = ("import json,sys; from laghos_amd import host_lib; "
-            "s=host_lib.Sim(['-p',1,'-m','data/cube01_hex.mesh','-rs',1,'-ok',3,'-ot',2,'-ms',6,'-tf',0.6,'-q']); "
+            "s=host_lib.Sim(['-p',1," + mesh_args + ",'-ms',6,'-tf',0.6,'-q']); "
             "n=0\nwhile s.step()==1: n+=1\n"
             "print(json.dumps(dict(e=s.e_norm(), steps=s.rk_steps, t=s.t)))")
     outs = []
@@ -352,6 +349,20 @@ def test_multi_rank_code_path_on_one_gpu():
     assert a["steps"] == b["steps"]
     assert abs(a["e"] - b["e"]) / a["e"] < 1e-10
     assert abs(a["t"] - b["t"]) / a["t"] < 1e-10
+
+
+def test_multi_rank_code_path_on_one_gpu():
+    """LGH_FORCE_MULTI=1: communicator of size 1, so the multi-GPU sequencing
+    (separate E->L gather, halo hook, ncclAllReduce of den / (r,z) / dt on the
+    context stream, finish kernels) runs for real on this single-GPU box and must
+    reproduce the fused single-rank path."""
+    _force_multi_parity("'-m','data/cube01_hex.mesh','-rs',1,'-ok',3,'-ot',2")
+
+
+def test_multi_rank_code_path_on_one_gpu_2d():
+    """... and in 2D (data/square01_quad.mesh -rs 2 -ok 2 -ot 1), where the velocity solve is the scalar CG of lgh_mass.hip, one
+    component after the other: its several-rank sequencing over real RCCL, on a communicator of size 1."""
+    _force_multi_parity("'-m','data/square01_quad.mesh','-rs',2,'-ok',2,'-ot',1")
 
 
 def test_rccl_grouped_send_recv_on_this_gpu():
@@ -536,6 +547,25 @@ MULTI_RANK_CASES = [
     (3, (15, 2, 2), 1, 1, (3, 2), {"LGH_VCG_VARIANT": "4"}),
     (2, (10, 3, 2), 1, 0, (3, 2), {"LGH_VCG_VARIANT": "4", "LGH_COMM2": "0", "_lockstep": "1"}),
 ]
+# 2D (a zone tuple of two): the velocity solve is the scalar CG of lgh_mass.hip, once per component, with its own several-rank
+# sequencing - no lockstep solver, hence no energy solve in lockstep and no "_lockstep" with LGH_COMM2=0.  Blocks of 13 x 5 zones
+# on the six rank grids of tests/rank_cases.py (tests/test_rank_cases.py: laghos::Partition picks exactly these grids), region
+# timers off and on; Q2Q1 (the order of BASELINE config 1) and Q4Q3; problem 0 (the one configuration with an energy source),
+# problem 7 (gravity through the halo-summed MultFull); problem 3 on the 7 x 3 box ("_size") so that its materials cross the
+# rank boundaries - 28 x 12 zones (split 4 x 1 by laghos::Partition: a chain of four) and 28 x 16 (2 x 2); the transport and
+# numbering switches
+MULTI_RANK_CASES += [(rc.n_ranks(g), rc.global_shape(g), 1, t, (3, 2), {}) for t in (0, 1) for g in rc.RANK_GRIDS]
+MULTI_RANK_CASES += [
+    (4, rc.global_shape((2, 2)), 1, 0, (2, 1), {}), (4, rc.global_shape((2, 2)), 1, 0, (4, 3), {}),
+    (4, rc.global_shape((2, 2)), 0, 0, (3, 2), {}), (3, rc.global_shape((3, 1)), 0, 0, (3, 2), {}),
+    (4, rc.global_shape((2, 2)), 7, 0, (3, 2), {}),
+    (4, (28, 12), 3, 0, (3, 2), {"_size": "7x3"}), (4, (28, 16), 3, 0, (3, 2), {"_size": "7x3"}),
+    (4, rc.global_shape((2, 2)), 1, 0, (3, 2), {"LGH_COMM2": "0"}),
+    (4, rc.global_shape((2, 2)), 1, 0, (3, 2), {"LGH_HALO_PIGGYBACK": "0"}),
+    (4, rc.global_shape((2, 2)), 1, 0, (3, 2), {"LGH_HALO_FUSED_PACK": "0"}),
+    (4, rc.global_shape((2, 2)), 1, 0, (3, 2), {"LGH_RENUMBER": "random"}),
+    (4, rc.global_shape((2, 2)), 1, 0, (3, 2), {"LGH_RENUMBER": "mfem"}),
+]
 
 
 @pytest.mark.parametrize("nranks,nel,problem,timers,order,env", MULTI_RANK_CASES,
@@ -554,7 +584,8 @@ def test_multi_rank_run_on_one_gpu(nranks, nel, problem, timers, order, env, mon
     must fall back to the all-reduce on every rank.  The 4-rank case runs problem 7
     (vorticity-scaled viscosity, gravity source through the halo-summed MultFull).
     timers = 0: region timers off, as in bench.py - the energy solve then runs beside the velocity solve on
-    the second stream, with its dot products summed over the ranks on the communicator's second channel."""
+    the second stream, with its dot products summed over the ranks on the communicator's second channel.
+    A zone tuple of two is a 2D run (-dim 2 -nx -ny -Sx 1 -Sy 1): see the comment above the 2D entries."""
     import ctypes
     import os
     import threading
@@ -563,8 +594,11 @@ def test_multi_rank_run_on_one_gpu(nranks, nel, problem, timers, order, env, mon
     for k, v in env.items():
         if k[0] != "_":
             monkeypatch.setenv(k, v)
-    args = ["-p", problem, "-dim", 3, "-nx", nel[0], "-ny", nel[1], "-nz", nel[2], "-Sx", 1, "-Sy", 1, "-Sz", 1, "-rs", 0,
-            "-ok", order[0], "-ot", order[1], "-pa", "-tf", 0.6, "-ms", 6 if order == (3, 2) else 3, "-q"]
+    size = [int(x) for x in env.get("_size", "x".join("1" * len(nel))).split("x")]
+    args = ["-p", problem, "-dim", len(nel)]
+    for a in range(len(nel)):   # the dimension is the length of the zone tuple
+        args += ["-n" + "xyz"[a], nel[a], "-S" + "xyz"[a], size[a]]
+    args += ["-rs", 0, "-ok", order[0], "-ot", order[1], "-pa", "-tf", 0.6, "-ms", 6 if order == (3, 2) else 3, "-q"]
     ref = host_lib.Sim(args)
     ref.enable_timers(timers)
     while ref.step() == 1:
@@ -603,6 +637,8 @@ def test_multi_rank_run_on_one_gpu(nranks, nel, problem, timers, order, env, mon
         # (orders 4 and 5: the unpreconditioned L2 CG on the Bernstein mass matrix amplifies the rounding differences of
         #  the rank-ordered sums - cond ~ 1e6; the README runs themselves are held to 1e-9)
         assert abs(got["e"] - want["e"]) <= (1e-10 if order == (3, 2) else 1e-9) * want["e"], (r, got, want)
+        if len(nel) == 2:
+            assert got["ls"] == [0, 0, 0, 0], (r, got)   # no lockstep velocity solve in 2D, so no energy solve in lockstep with it
         if "_lockstep" in env:
             solves, inside, after, ready = got["ls"]
             if env["_lockstep"] == "1":

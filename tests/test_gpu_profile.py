@@ -186,14 +186,24 @@ def test_same_bits_under_every_numbering(renumber):
 
 
 def test_two_emulated_ranks():
+    """3D, 4 x 2 x 2 zones on two ranks: see _two_emulated_ranks"""
+    _two_emulated_ranks(["-dim", 3, "-nx", 4, "-ny", 2, "-nz", 2, "-Sx", 2, "-Sy", 1, "-Sz", 1],
+                        [("x", 5, 0.0, 2.0, None), ("r", 6, 0.0, 2.5, (0.0, 0.0, 0.0)), ("z", 3, 0.1, 0.9, None)])
+
+
+def test_two_emulated_ranks_2d():
+    """the same on 2D blocks: 4 x 2 zones on two ranks, binned along x, r and y"""
+    _two_emulated_ranks(["-dim", 2, "-nx", 4, "-ny", 2, "-Sx", 2, "-Sy", 1],
+                        [("x", 5, 0.0, 2.0, None), ("r", 6, 0.0, 2.5, (0.0, 0.0)), ("y", 3, 0.1, 0.9, None)])
+
+
+def _two_emulated_ranks(mesh_args, looks):
     """3D, 4 x 2 x 2 zones, Q2Q1 on two ranks (threads, "LGHLOCAL" communicator; the harness of
     test_gpu_diagnostics.test_two_emulated_ranks).  At the initial state (the same bits on every partition) both ranks return
     the bytes of the one-rank run; after two steps (the states of a one-rank run differ by then, in the last bits of the CG
     sums) both ranks still return the same bytes, with values of their own in every column."""
     from laghos_amd import host_lib
-    args = ["-dim", 3, "-nx", 4, "-ny", 2, "-nz", 2, "-Sx", 2, "-Sy", 1, "-Sz", 1, "-rs", 0, "-p", 1, "-ok", 2, "-ot", 1, "-pa",
-            "-tf", 1e9, "-ms", 10 ** 6, "-vs", 10 ** 9, "-q"]
-    looks = [("x", 5, 0.0, 2.0, None), ("r", 6, 0.0, 2.5, (0.0, 0.0, 0.0)), ("z", 3, 0.1, 0.9, None)]
+    args = mesh_args + ["-rs", 0, "-p", 1, "-ok", 2, "-ot", 1, "-pa", "-tf", 1e9, "-ms", 10 ** 6, "-vs", 10 ** 9, "-q"]
 
     def run_rank(nranks, rank, cid, out, err):
         try:

@@ -308,10 +308,10 @@ def test_without_the_options_nothing_changes(tmp_path):
 
 
 # ---- two ranks as threads in one process (the LGHLOCAL communicator, as tests/test_gpu_multiproc.py::_in_process) --------
-def two_ranks(extra_by_rank, block=4, steps=6):
+def two_ranks(extra_by_rank, block=4, steps=6, dim=3):
     """both ranks' legs; a rank whose Sim is refused reports 'refused'"""
-    args = ["-dim", 3, "-nx", 2 * block, "-ny", block, "-nz", block, "-Sx", 2, "-Sy", 1, "-Sz", 1, "-rs", 0, "-p", 1, "-ok", 2, "-ot", 1,
-            "-pa", "-tf", 1e9, "-ms", steps - 1, "-vs", 10 ** 9]
+    mesh = ["-dim", dim, "-nx", 2 * block, "-ny", block, "-Sx", 2, "-Sy", 1] + (["-nz", block, "-Sz", 1] if dim == 3 else [])
+    args = mesh + ["-rs", 0, "-p", 1, "-ok", 2, "-ot", 1, "-pa", "-tf", 1e9, "-ms", steps - 1, "-vs", 10 ** 9]
     cid = (b"LGHLOCAL" + os.urandom(16).hex().encode()).ljust(128, b"\0")
     out, err = {}, {}
 
@@ -335,16 +335,26 @@ def two_ranks(extra_by_rank, block=4, steps=6):
 
 
 def test_two_ranks(tmp_path, capfd):
+    _two_ranks(tmp_path, capfd, 3)
+
+
+def test_two_ranks_2d(tmp_path, capfd):
+    """the same on two 2D blocks of 4 x 4 zones"""
+    _two_ranks(tmp_path, capfd, 2)
+
+
+def _two_ranks(tmp_path, capfd, dim):
     base = str(tmp_path / "two" / "run")
-    A, args = two_ranks([[], []])
+    run2 = lambda extra: two_ranks(extra, dim=dim)
+    A, args = run2([[], []])
     assert A[0]["ti"] == 6 and A[0]["fp"] == A[1]["fp"]                     # the rank-ordered combination: one value for the run
     assert A[0]["fp"] != fp_ref(A[0]["S"]) and not np.array_equal(A[0]["S"], A[1]["S"])
-    B, _ = two_ranks([["-ckpt", 3, "-k", base]] * 2)
+    B, _ = run2([["-ckpt", 3, "-k", base]] * 2)
     for r in range(2):
         same(A[r], B[r], f"B against A, rank {r}")
     assert pieces(base) == ["cycle_000003.lgr.0", "cycle_000003.lgr.1", "cycle_000006.lgr.0", "cycle_000006.lgr.1", "latest"]
     assert open(base + "_restart/latest").read() == "cycle_000006.lgr\n"
-    C, _ = two_ranks([["-restart", stem_of(base, 3)]] * 2)
+    C, _ = run2([["-restart", stem_of(base, 3)]] * 2)
     for r in range(2):
         assert C[r]["taken"] == 3
         same(A[r], C[r], f"C against A, rank {r}")
@@ -353,14 +363,14 @@ def test_two_ranks(tmp_path, capfd):
     d = base + "_restart/"
     for r in range(2):
         shutil.copy(d + f"cycle_000003.lgr.{r}", d + f"swapped.lgr.{1 - r}")
-    R, _ = two_ranks([["-restart", d + "swapped.lgr"]] * 2)
+    R, _ = run2([["-restart", d + "swapped.lgr"]] * 2)
     assert R == {0: "refused", 1: "refused"}
     msg = capfd.readouterr().err
     assert "it is the piece of rank 1 of 2, this is rank 0 of 2" in msg and "swapped.lgr.0" in msg
     # pieces of two different cycles: each passes its own checks, the ranks find out together
     shutil.copy(d + "cycle_000003.lgr.0", d + "mixed.lgr.0")
     shutil.copy(d + "cycle_000006.lgr.1", d + "mixed.lgr.1")
-    R, _ = two_ranks([["-restart", d + "mixed.lgr"]] * 2)
+    R, _ = run2([["-restart", d + "mixed.lgr"]] * 2)
     assert R == {0: "refused", 1: "refused"}
     assert "pieces of different checkpoints" in capfd.readouterr().err
     # a one-rank restart of the two-rank checkpoint

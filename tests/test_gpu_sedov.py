@@ -150,13 +150,10 @@ def test_cpp_driver_err_option_guards():
     assert p.returncode != 0 and "reflections" in (p.stdout + p.stderr)
 
 
-@pytest.mark.parametrize("nranks", [2, 8])
-def test_err_option_on_emulated_ranks(nranks):
-    """-err on several ranks (loopback communicator, see test_multi_rank_run_on_one_gpu): every rank
-    integrates its own zones, the squared error is all-reduced; must match the single-rank value."""
+def _err_on_emulated_ranks(mesh_args, nranks):
     import threading
     from laghos_amd import host_lib
-    args = ["-p", 1, "-dim", 3, "-nx", 8, "-ny", 8, "-nz", 8, "-rs", 0, "-ok", 2, "-ot", 1, "-pa", "-E0", 0.25, "-tf", 0.05, "-q"]
+    args = ["-p", 1] + mesh_args + ["-rs", 0, "-ok", 2, "-ot", 1, "-pa", "-E0", 0.25, "-tf", 0.05, "-q"]
     ref = host_lib.Sim(args)
     while ref.step() == 1:
         pass
@@ -185,3 +182,16 @@ def test_err_option_on_emulated_ranks(nranks):
     assert not err, err
     for r in range(nranks):
         assert abs(out[r] - want) <= 1e-9 * want, (r, out[r], want)
+
+
+@pytest.mark.parametrize("nranks", [2, 8])
+def test_err_option_on_emulated_ranks(nranks):
+    """-err on several ranks (loopback communicator, see test_multi_rank_run_on_one_gpu): every rank
+    integrates its own zones, the squared error is all-reduced; must match the single-rank value."""
+    _err_on_emulated_ranks(["-dim", 3, "-nx", 8, "-ny", 8, "-nz", 8], nranks)
+
+
+@pytest.mark.parametrize("nranks", [2, 4])
+def test_err_option_on_emulated_ranks_2d(nranks):
+    """... and on 2D blocks: 8 x 8 zones on 2 x 1 and 2 x 2 ranks"""
+    _err_on_emulated_ranks(["-dim", 2, "-nx", 8, "-ny", 8], nranks)

@@ -4,6 +4,7 @@ conditions, block partition / neighbour lists.  CPU only."""
 import numpy as np
 import pytest
 
+import rank_cases
 from laghos_amd import host_lib
 from oracle.fem import Problem
 
@@ -61,9 +62,32 @@ def test_partition(nranks):
     mesh, rs, ok, ot = "cube01_hex", 1, 2, 1
     discs = [host_lib.host_disc(mesh, rs, ok, ot, 1, nranks=nranks, rank=r) for r in range(nranks)]
     ref = Problem(mesh=mesh, rs=rs, order_v=ok, order_e=ot, problem=1)
+    oracle = [Problem(mesh=mesh, rs=rs, order_v=ok, order_e=ot, problem=1, rank=r,
+                      pgrid={2: [2, 1, 1], 4: [2, 2, 1], 8: [2, 2, 2]}[nranks]) for r in range(nranks)]
+    _check_partition(discs, ref, oracle)
+
+
+@pytest.mark.parametrize("pgrid", list(rank_cases.RANK_GRIDS), ids=rank_cases.grid_id)
+def test_partition_2d(pgrid):
+    """... on the 2D rank grids of tests/rank_cases.py (blocks of 13 x 5 zones, through laghos_host_disc_create_cartesian):
+    corner nodes held by four ranks, a middle rank with eight neighbours"""
+    discs, ref, oracle = _discs_2d(pgrid)
+    assert [len(d["nbr_rank"]) for d in discs] == rank_cases.PEERS[pgrid]
+    _check_partition(discs, ref, oracle)
+
+
+def _discs_2d(pgrid, ok=2, ot=1):
+    """(the C++ Discretization of every rank, the oracle's global problem, the oracle's rank problems) of a 2D rank grid"""
+    shape, n = rank_cases.global_shape(pgrid), rank_cases.n_ranks(pgrid)
+    discs = [host_lib.host_disc(None, 0, ok, ot, 1, nranks=n, rank=r, zones=shape) for r in range(n)]
+    kw = dict(breaks=[np.linspace(0.0, 1.0, m + 1) for m in shape], order_v=ok, order_e=ot, problem=1)
+    return discs, Problem(**kw), [Problem(rank=r, pgrid=list(pgrid), **kw) for r in range(n)]
+
+
+def _check_partition(discs, ref, oracle):
     owned = sum(int(d["owner"].sum()) for d in discs)
     assert owned == ref.global_N
-    dim = 3
+    dim = ref.dim
     for r, d in enumerate(discs):
         N = len(d["owner"])
         X = d["S0"][:dim * N].reshape(dim, N)
@@ -78,10 +102,9 @@ def test_partition(nranks):
     # the Sedov energy lives on exactly one rank
     nz = [np.count_nonzero(d["S0"][2 * dim * len(d["owner"]):]) for d in discs]
     assert sum(1 for n in nz if n) == 1
-    # oracle partition agrees (same pgrid choice for the cube)
+    # oracle partition agrees (same pgrid choice)
     for r, d in enumerate(discs):
-        pr = Problem(mesh=mesh, rs=rs, order_v=ok, order_e=ot, problem=1, rank=r,
-                     pgrid={2: [2, 1, 1], 4: [2, 2, 1], 8: [2, 2, 2]}[nranks])
+        pr = oracle[r]
         assert np.array_equal(d["h1map"], pr.h1map.reshape(-1))
         assert np.array_equal(d["owner"], pr.owner)
 
@@ -162,11 +185,21 @@ def test_owner_and_neighbours_from_group_lists(nranks):
     every global node owned exactly once and equal to Partition's (both: lowest rank owns), and into per-peer
     lists that name the same physical nodes, in the same order, on both ranks of every pair, and cover exactly
     the nodes Partition shares between them."""
+    mesh, rs, ok, ot = "cube01_hex", 1, 2, 1
+    _check_groups([host_lib.host_disc(mesh, rs, ok, ot, 1, nranks=nranks, rank=r) for r in range(nranks)], 3)
+
+
+@pytest.mark.parametrize("pgrid", list(rank_cases.RANK_GRIDS), ids=rank_cases.grid_id)
+def test_owner_and_neighbours_from_group_lists_2d(pgrid):
+    """... on the 2D rank grids of tests/rank_cases.py: groups of two ranks (edges) and of four (corner nodes)"""
+    _check_groups(_discs_2d(pgrid)[0], 2)
+
+
+def _check_groups(discs, dim):
     import ctypes
     from laghos_amd import _lib
     lib = _lib.load()
-    mesh, rs, ok, ot, dim = "cube01_hex", 1, 2, 1, 3
-    discs = [host_lib.host_disc(mesh, rs, ok, ot, 1, nranks=nranks, rank=r) for r in range(nranks)]
+    nranks = len(discs)
     keys = []      # per rank: global identity of every local node
     holders = {}   # global node -> ranks holding it
     for r, d in enumerate(discs):
@@ -209,7 +242,7 @@ def test_owner_and_neighbours_from_group_lists(nranks):
         for i, nr in enumerate(d["nbr_rank"]):
             assert sorted(lists[int(nr)]) == sorted(d["nbr_nodes"][i])  # the same set of shared nodes as Partition's
         result.append(lists)
-    assert sum(int(np.sum(host_lib.host_disc(mesh, rs, ok, ot, 1, nranks=nranks, rank=r)["owner"])) for r in range(nranks)) == len(holders)
+    assert sum(int(np.sum(d["owner"])) for d in discs) == len(holders)
     for a in range(nranks):
         for b, mine in result[a].items():
             theirs = result[b][a]
