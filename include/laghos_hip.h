@@ -320,6 +320,29 @@ int lgh_sample_fields(lgh_ctx *ctx, const double *S, const double *rho_l2 /* or 
                       const double *B_l2_lat /* host, R1*L1D, [r + R1*l] */,
                       double *x_out, double *v_out, double *e_out, double *rho_out, double *p_out);
 
+/* ---- derived flow fields on the same lattice (the driver's `-paraview -pv-fields`): what needs derivatives of the Q_k fields
+ * inside a zone and cannot be recovered from a file of linear cells.  Lattice, point index pt, NP and the table layout are
+ * those of lgh_sample_fields; G_h1_lat[r + R1 * d] is the derivative of the H1 Gauss-Lobatto basis function d at r / (R1 - 1)
+ * (lgh_config.G_h1 with Q1D -> R1).  Per lattice point, with J_ij = dx_i / dxi_j and V_ij = dv_i / dxi_j from the H1 dofs of
+ * the zone:
+ *   detj_out[pt]                    det J
+ *   gradv_out[(i*dim + j)*NP + pt]  L_ij = dv_i / dx_j = (V adj(J))_ij / det J  (sgrad_v of QUpdateBody before Symmetrize,
+ *                                   laghos_solver.cpp: Mult(dV, Jinv)); no branch on the sign of det J: an inverted point has
+ *                                   the value of the formula, det J == 0 what IEEE gives
+ *   div_out[pt]                     L_00 (+ L_11 (+ L_22)), summed in this order from the entries stored
+ *   vort_out                        2D: NP values L_10 - L_01; 3D: 3 NP values (L_21 - L_12, L_02 - L_20, L_10 - L_01),
+ *                                   component-major as v_out; 1D: LGH_ERR_ARG when not NULL
+ *   cs_out[pt]                      sqrt((gamma_z (gamma_z - 1)) max(e, 0)), the sound speed of QUpdateBody, e the value
+ *                                   lgh_sample_fields gives at the point (the same bits)
+ * Each output is a device array, may be NULL and is then skipped; the others keep their bits.  Refusals as lgh_sample_fields:
+ * R1 out of range, a NULL table, vort_out in 1D: LGH_ERR_ARG; tables of more than 81 entries or a zone that needs more than
+ * 64 KB of LDS: LGH_ERR_UNSUPPORTED with the bytes in the message.  No kernel is launched in either case.
+ * Asynchronous on the context's stream; reads S and the context's constant data (h1_map, gamma), writes its outputs only: the
+ * quadrature data, its generation counter and the fused force products are untouched.  All dimensions. */
+int lgh_sample_derived(lgh_ctx *ctx, const double *S, int R1, const double *B_h1_lat /* host, R1*D1D, [r + R1*d] */,
+                       const double *G_h1_lat /* host, R1*D1D */, const double *B_l2_lat /* host, R1*L1D */,
+                       double *detj_out, double *gradv_out, double *div_out, double *vort_out, double *cs_out);
+
 /* ---- conservation and mesh-health diagnostics (the driver's `-hist` time history; the reference prints one number,
  * "Energy diff", after the last step).  At quadrature point q of zone z, with the context's own tables and rule (those
  * lgh_qupdate uses): J_q = grad x and detJ_q from the x block of S, v_q from the v block, e_q from the e block through
@@ -398,6 +421,7 @@ int lgh_enable_timers(lgh_ctx *ctx, int on);
 #define LGH_KERNEL_FINGERPRINT 9  /* lgh_vec_fingerprint */
 #define LGH_KERNEL_DIAG 10        /* the zone kernel of lgh_diagnostics_zones / lgh_diagnostics */
 #define LGH_KERNEL_PROFILE 11     /* lgh_profile: both passes over the zones and the kernels between and behind them */
+#define LGH_KERNEL_DERIVED 12     /* lgh_sample_derived */
 int lgh_ktime_begin(lgh_ctx *ctx, int which, int max_samples);
 int lgh_ktime_end(lgh_ctx *ctx, int *launches, double *mean_seconds);
 /* Whether lgh_create found the 1-D H1 / L2 tables mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (any nodal or

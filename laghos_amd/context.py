@@ -452,6 +452,19 @@ class Context:
         check(self.lib.lgh_sample_fields(self.h, _ptr(S), opt(rho_l2), R1, _dbl(Bh), _dbl(Bl), opt(x), opt(v), opt(e), opt(rho),
                                          opt(p)))
 
+    def sample_derived(self, S, B_h1_lat, G_h1_lat, B_l2_lat, detj=None, grad_v=None, div_v=None, vorticity=None, sound_speed=None):
+        """lgh_sample_derived: the derived fields of S on the lattice whose host tables are B_h1_lat, G_h1_lat (R1, D1D; values and
+        derivatives of the H1 basis) and B_l2_lat (R1, L1D), indexed [r, d]; device tensors of NP = NE * R1^dim (detj, div_v,
+        sound_speed), dim^2 * NP (grad_v, entry i*dim + j = dv_i/dx_j) and NP in 2D / 3 * NP in 3D (vorticity), each may be None
+        (skipped).  Asynchronous."""
+        Bh = _np_f64(np.asarray(B_h1_lat).T.reshape(-1))   # -> [r + R1*d]
+        Gh = _np_f64(np.asarray(G_h1_lat).T.reshape(-1))
+        Bl = _np_f64(np.asarray(B_l2_lat).T.reshape(-1))
+        R1 = int(np.asarray(B_h1_lat).shape[0])
+        opt = lambda t: _ptr(t) if t is not None else None
+        check(self.lib.lgh_sample_derived(self.h, _ptr(S), R1, _dbl(Bh), _dbl(Gh), _dbl(Bl), opt(detj), opt(grad_v), opt(div_v), opt(vorticity),
+                                          opt(sound_speed)))
+
     def diagnostics_zones(self, S, out):
         """lgh_diagnostics_zones: the 17 zone diagnostics of S into the device tensor out (17 * NE), out[k * NE + z] with z
         the caller's zone id and k the position in DIAG_NAMES.  Asynchronous."""

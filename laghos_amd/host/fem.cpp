@@ -146,6 +146,14 @@ void LatticeTables(int order_v, int order_e, int R, std::vector<double> &B_h1_la
    BernsteinTable(order_e, pts, B_l2_lat);
 }
 
+void LatticeGradTable(int order_v, int R, std::vector<double> &G_h1_lat)
+{
+   std::vector<double> gll, pts((size_t)R + 1), B;
+   for (int r = 0; r <= R; r++) { pts[r] = (double)r / (double)R; }
+   GaussLobatto(order_v + 1, gll);
+   LagrangeTables(gll, pts, B, G_h1_lat);
+}
+
 // ---- mesh ---------------------------------------------------------------------------
 CartMesh CartMesh::Named(const std::string &name_in)
 {

@@ -40,6 +40,8 @@ struct Tables
 // points per direction): B_h1_lat[r + R1*d] (Gauss-Lobatto Lagrange, order_v), B_l2_lat[r + R1*l] (Bernstein, order_e) -
 // Tables::B / Bl with Q1D -> R1.
 void LatticeTables(int order_v, int order_e, int R, std::vector<double> &B_h1_lat, std::vector<double> &B_l2_lat);
+// The derivatives of the H1 basis there (lgh_sample_derived): G_h1_lat[r + R1*d] = l_d'(r/R) - Tables::G with Q1D -> R1.
+void LatticeGradTable(int order_v, int R, std::vector<double> &G_h1_lat);
 
 // ---- mesh ---------------------------------------------------------------------------
 // Tensor-product mesh given by per-axis break points; element e = ex + nx*(ey + ny*ez).

@@ -60,6 +60,10 @@ struct Options
    bool paraview = false;
    bool vis_refine_set = false;
    int vis_refine = 0;             // -vr: lattice cells per zone and direction (default: order_v), 1..8
+   // -pv-fields LIST: derived fields in the -paraview dumps (lgh_sample_derived): a comma list of div_v, vorticity,
+   // grad_v, detj, sound_speed, or all (which leaves vorticity out in 1D); the DERIVED_* bits of LagrangianHydroOperator
+   bool pv_fields_set = false, pv_vort_named = false; // (named: `vorticity` itself, not through `all`)
+   unsigned pv_fields = 0;
    int dev = 0;
    // multi-rank (set by the launcher, not the reference CLI)
    int nranks = 1, rank = 0;
@@ -224,6 +228,37 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
          o.vis_refine_set = true;
          continue;
       }
+      if (a == "-pv-fields" || a == "--paraview-fields")
+      {
+         if (!(v = need(i))) { return false; }
+         using H = hydrodynamics::LagrangianHydroOperator;
+         static const struct { const char *name; unsigned bit; } known[] = {
+            {"div_v", H::DERIVED_DIV}, {"vorticity", H::DERIVED_VORT}, {"grad_v", H::DERIVED_GRAD}, {"detj", H::DERIVED_DETJ},
+            {"sound_speed", H::DERIVED_CS}};
+         const std::string list = v;
+         o.pv_fields_set = true;
+         o.pv_vort_named = false;
+         o.pv_fields = 0;
+         for (size_t pos = 0; pos <= list.size();)
+         {
+            const size_t comma = std::min(list.find(',', pos), list.size());
+            const std::string name = list.substr(pos, comma - pos);
+            pos = comma + 1;
+            if (name.empty()) { continue; }
+            unsigned bit = 0;
+            if (name == "all") { bit = H::DERIVED_ALL; }
+            for (const auto &k : known) { if (name == k.name) { bit = k.bit; } }
+            if (!bit)
+            {
+               err = "-pv-fields: unknown field " + name + " (div_v, vorticity, grad_v, detj, sound_speed or all)";
+               return false;
+            }
+            if (name == "vorticity") { o.pv_vort_named = true; }
+            o.pv_fields |= bit;
+         }
+         if (!o.pv_fields) { err = "-pv-fields needs a list of div_v, vorticity, grad_v, detj, sound_speed, or all: the list is empty"; return false; }
+         continue;
+      }
       if (a == "-store-stress" || a == "--store-stress") { o.store_stress = true; continue; }
       if (a == "-no-store-stress" || a == "--no-store-stress") { o.store_stress = false; continue; }
       if (a == "-renumber" || a == "--renumber") { if (!(v = need(i))) { return false; } o.renumber = v; continue; }
@@ -237,6 +272,11 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
    if ((o.vis_refine_set || o.paraview) && (o.vis_refine < 1 || o.vis_refine > 8))
    {
       err = "-vr / --vis-refine must be between 1 and 8, got " + std::to_string(o.vis_refine);
+      return false;
+   }
+   if (o.pv_fields_set && !o.paraview)
+   {
+      err = "-pv-fields adds fields to the -paraview dumps: it needs -paraview";
       return false;
    }
    return true;
@@ -416,7 +456,11 @@ static bool DumpParaview(laghos_sim *s, int cycle, const Vector *rho = nullptr)
       hydro.ComputeDensity(s->S, s->pv_rho); // rho_gf is refreshed before the output (laghos.cpp:827-830)
       rho = &s->pv_rho;
    }
+   using H = hydrodynamics::LagrangianHydroOperator;
+   const long base = (2 * dim + 3) * NP; // the blocks of SampleFields; those of SampleDerived follow in the same vector
+   if (o.pv_fields && s->pv_dev.Size() < base + hydro.DerivedSize(R)) { s->pv_dev.SetSize(base + hydro.DerivedSize(R)); }
    hydro.SampleFields(s->S, *rho, R, s->pv_dev);
+   if (o.pv_fields) { hydro.SampleDerived(s->S, R, o.pv_fields, s->pv_dev, base); }
    hydro.Sync();
    const clk::time_point t1 = clk::now();
    s->pv_dev.ToHost(s->pv_host);
@@ -425,13 +469,46 @@ static bool DumpParaview(laghos_sim *s, int cycle, const Vector *rho = nullptr)
    const std::string dir = o.basename + "_paraview";
    const size_t slash = o.basename.find_last_of('/');
    const std::string rel_dir = (slash == std::string::npos ? o.basename : o.basename.substr(slash + 1)) + "_paraview";
-   bool ok = WriteVtu(dir, dim, s->disc->NE, R + 1, h, h + dim * NP, h + 2 * dim * NP, h + (2 * dim + 1) * NP,
-                      h + (2 * dim + 2) * NP, cycle, s->t, o.rank, o.nranks);
+   // the derived blocks as the file holds them, in the order of the table of DESIGN.md §7f: point by point, vectors and
+   // tensors padded with zeros to 3 and 3 x 3 (the 2D vorticity is the z component)
+   std::vector<VtuField> extra;
+   std::vector<double> pv_vort, pv_grad;
+   if (o.pv_fields)
+   {
+      const int nv = (dim == 3) ? 3 : (dim == 2 ? 1 : 0);
+      const double *detj = h + base, *grad = detj + NP, *div = grad + (long)dim * dim * NP, *vort = div + NP, *cs = vort + nv * NP;
+      if (o.pv_fields & H::DERIVED_DIV) { extra.push_back({"div_v", 1, div}); }
+      if (o.pv_fields & H::DERIVED_VORT)
+      {
+         pv_vort.assign(3 * (size_t)NP, 0.0);
+         for (int c = 0; c < nv; c++)
+         {
+            for (long i = 0; i < NP; i++) { pv_vort[3 * i + (dim == 2 ? 2 : c)] = vort[c * NP + i]; }
+         }
+         extra.push_back({"vorticity", 3, pv_vort.data()});
+      }
+      if (o.pv_fields & H::DERIVED_GRAD)
+      {
+         pv_grad.assign(9 * (size_t)NP, 0.0);
+         for (int a = 0; a < dim; a++)
+         {
+            for (int b = 0; b < dim; b++)
+            {
+               for (long i = 0; i < NP; i++) { pv_grad[9 * i + 3 * a + b] = grad[(a * dim + b) * NP + i]; }
+            }
+         }
+         extra.push_back({"velocity_gradient", 9, pv_grad.data()});
+      }
+      if (o.pv_fields & H::DERIVED_DETJ) { extra.push_back({"detJ", 1, detj}); }
+      if (o.pv_fields & H::DERIVED_CS) { extra.push_back({"sound_speed", 1, cs}); }
+   }
+   bool ok = WriteVtuFields(dir, dim, s->disc->NE, R + 1, h, h + dim * NP, h + 2 * dim * NP, h + (2 * dim + 1) * NP,
+                            h + (2 * dim + 2) * NP, extra, cycle, s->t, o.rank, o.nranks);
    s->pv_times.push_back(s->t);
    s->pv_cycles.push_back(cycle);
    if (ok && o.rank == 0)
    {
-      if (o.nranks > 1) { ok = WritePvtu(dir, cycle, s->t, o.nranks); }
+      if (o.nranks > 1) { ok = WritePvtuFields(dir, cycle, s->t, o.nranks, extra); }
       ok = ok && WritePvd(o.basename + ".pvd", rel_dir, s->pv_times, s->pv_cycles, o.nranks);
    }
    const clk::time_point t3 = clk::now();
@@ -729,6 +806,15 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
       {
          o.p_assembly = false;
          if (rank == 0 && !o.quiet) { std::cout << "Laghos does not support PA in 1D. Switching to FA." << std::endl; }
+      }
+      if (o.dim == 1 && (o.pv_fields & hydrodynamics::LagrangianHydroOperator::DERIVED_VORT))
+      {
+         if (o.pv_vort_named)
+         {
+            std::fprintf(stderr, "laghos: -pv-fields vorticity: there is no vorticity in 1D\n");
+            return nullptr;
+         }
+         o.pv_fields &= ~(unsigned)hydrodynamics::LagrangianHydroOperator::DERIVED_VORT; // (all)
       }
       if (o.prof_axis.empty()) { o.prof_axis = (o.problem == 1) ? "r" : "x"; }
       if (o.prof_steps > 0 && o.prof_axis != "r" && o.prof_axis[0] - 'x' >= o.dim)
@@ -1060,6 +1146,29 @@ int laghos_sim_profile(laghos_sim *s, int axis, int nbins, double lo, double hi,
    if (rc != 0) { s->error = lgh_last_error(); }
    return rc;
 }
+// lgh_sample_derived of the state as it stands on the lattice of R cells per zone and direction (1 <= R <= 8), into host arrays
+// in the layouts of that entry: detj, div, cs NP = NE (R+1)^dim doubles, gradv dim^2 NP, vort NP (2D) or 3 NP (3D); each may be
+// NULL.  0 = ok; -1 with laghos_sim_error() set for an R out of range or vort in 1D, and nothing was written.
+int laghos_sim_derived_fields(laghos_sim *s, int R, double *detj, double *gradv, double *div, double *vort, double *cs)
+{
+   using H = hydrodynamics::LagrangianHydroOperator;
+   const int dim = s->disc->dim, nv = (dim == 3) ? 3 : (dim == 2 ? 1 : 0);
+   if (R < 1 || R > 8) { s->error = "laghos_sim_derived_fields: R = " + std::to_string(R) + " is out of range (1 <= R <= 8)"; return -1; }
+   if (vort && dim == 1) { s->error = "laghos_sim_derived_fields: vort: there is no vorticity in 1D"; return -1; }
+   const unsigned mask = (detj ? H::DERIVED_DETJ : 0) | (gradv ? H::DERIVED_GRAD : 0) | (div ? H::DERIVED_DIV : 0) | (vort ? H::DERIVED_VORT : 0) |
+                         (cs ? H::DERIVED_CS : 0);
+   if (!mask) { return 0; }
+   const long NP = s->hydro->SamplePoints(R);
+   Vector dev;
+   std::vector<double> h;
+   s->hydro->SampleDerived(s->S, R, mask, dev);
+   s->hydro->Sync();
+   dev.ToHost(h);
+   const double *p = h.data();
+   auto take = [&](double *dst, long n) { if (dst) { std::memcpy(dst, p, n * sizeof(double)); } p += n; };
+   take(detj, NP); take(gradv, (long)dim * dim * NP); take(div, NP); take(vort, nv * NP); take(cs, NP);
+   return 0;
+}
 double laghos_sim_energy(laghos_sim *s) { return s->hydro->InternalEnergy(s->S) + s->hydro->KineticEnergy(s->S); }
 void laghos_sim_sync(laghos_sim *s) { s->hydro->Sync(); }
 void laghos_sim_enable_timers(laghos_sim *s, int on) { s->hydro->EnableTimers(on != 0); }
@@ -1142,6 +1251,33 @@ int laghos_host_write_vtu(const char *dir, int dim, int NE, int R1, const double
    return WriteVtu(dir, dim, NE, R1, x, v, e, rho, p, cycle, time, rank, nranks) ? 0 : -1;
 }
 int laghos_host_write_pvtu(const char *dir, int cycle, double time, int nranks) { return WritePvtu(dir, cycle, time, nranks) ? 0 : -1; }
+// ... with n_extra further PointData arrays behind the four standing ones (WriteVtuFields): names[k], comps[k] values per point,
+// data[k] point by point
+static std::vector<VtuField> HostExtra(int n_extra, const char *const *names, const int *comps, const double *const *data)
+{
+   std::vector<VtuField> extra;
+   for (int k = 0; k < n_extra; k++) { extra.push_back({names[k] ? names[k] : "", comps[k], data ? data[k] : nullptr}); }
+   return extra;
+}
+int laghos_host_write_vtu_fields(const char *dir, int dim, int NE, int R1, const double *x, const double *v, const double *e,
+                                 const double *rho, const double *p, int n_extra, const char *const *names, const int *comps,
+                                 const double *const *data, int cycle, double time, int rank, int nranks)
+{
+   return WriteVtuFields(dir, dim, NE, R1, x, v, e, rho, p, HostExtra(n_extra, names, comps, data), cycle, time, rank, nranks) ? 0 : -1;
+}
+int laghos_host_write_pvtu_fields(const char *dir, int cycle, double time, int nranks, int n_extra, const char *const *names, const int *comps)
+{
+   return WritePvtuFields(dir, cycle, time, nranks, HostExtra(n_extra, names, comps, nullptr)) ? 0 : -1;
+}
+// host-only: the derivatives of the H1 basis at the lattice abscissae, G_h1_lat[r + (R+1)*d] ((R+1)*(order_v+1))
+int laghos_host_lattice_grad_table(int order_v, int R, double *G_h1_lat)
+{
+   if (order_v < 1 || R < 1) { return -1; }
+   std::vector<double> G;
+   LatticeGradTable(order_v, R, G);
+   std::memcpy(G_h1_lat, G.data(), G.size() * sizeof(double));
+   return 0;
+}
 int laghos_host_write_pvd(const char *pvd_path, const char *rel_dir, int n, const double *times, const int *cycles, int nranks)
 {
    return WritePvd(pvd_path, rel_dir, std::vector<double>(times, times + n), std::vector<int>(cycles, cycles + n), nranks) ? 0 : -1;

@@ -247,12 +247,33 @@ long LagrangianHydroOperator::SamplePoints(int R) const
 void LagrangianHydroOperator::SampleFields(const Vector &S, const Vector &rho, int R, Vector &out) const
 {
    const long NP = SamplePoints(R);
-   if (out.Size() != (2 * dim + 3) * NP) { out.SetSize((2 * dim + 3) * NP); }
+   if (out.Size() < (2 * dim + 3) * NP) { out.SetSize((2 * dim + 3) * NP); }
    std::vector<double> Bh, Bl;
    LatticeTables(disc.tab.order_v, disc.tab.order_e, R, Bh, Bl);
    double *o = out.Write();
    LGH_VERIFY(lgh_sample_fields(ctx, S.Read(), rho.Read(), R + 1, Bh.data(), Bl.data(), o, o + dim * NP, o + 2 * dim * NP,
                                 o + (2 * dim + 1) * NP, o + (2 * dim + 2) * NP));
+}
+
+long LagrangianHydroOperator::DerivedSize(int R) const
+{
+   const int nv = (dim == 3) ? 3 : (dim == 2 ? 1 : 0);
+   return (3 + dim * dim + nv) * SamplePoints(R);
+}
+
+void LagrangianHydroOperator::SampleDerived(const Vector &S, int R, unsigned mask, Vector &out, long offset) const
+{
+   const long NP = SamplePoints(R);
+   const int nv = (dim == 3) ? 3 : (dim == 2 ? 1 : 0);
+   if (out.Size() < offset + DerivedSize(R)) { out.SetSize(offset + DerivedSize(R)); }
+   std::vector<double> Bh, Bl, Gh;
+   LatticeTables(disc.tab.order_v, disc.tab.order_e, R, Bh, Bl);
+   LatticeGradTable(disc.tab.order_v, R, Gh);
+   double *o = out.Write() + offset;
+   double *detj = o, *grad = detj + NP, *div = grad + (long)dim * dim * NP, *vort = div + NP, *cs = vort + nv * NP;
+   LGH_VERIFY(lgh_sample_derived(ctx, S.Read(), R + 1, Bh.data(), Gh.data(), Bl.data(), (mask & DERIVED_DETJ) ? detj : nullptr,
+                                 (mask & DERIVED_GRAD) ? grad : nullptr, (mask & DERIVED_DIV) ? div : nullptr,
+                                 (mask & DERIVED_VORT) ? vort : nullptr, (mask & DERIVED_CS) ? cs : nullptr));
 }
 
 void LagrangianHydroOperator::Diagnostics(const Vector &S, double out[LGH_DIAG_COUNT]) const

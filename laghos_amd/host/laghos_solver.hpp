@@ -87,10 +87,21 @@ public:
                             const double origin[3], int err_order) const;
    // The fields of S and the density rho on the lattice of R + 1 points per direction in every zone (lgh_sample_fields;
    // stands in for the grid-function evaluation behind the reference's data collections, laghos.cpp:691-701, :845-871):
-   // out = [x | v | e | rho | p] in blocks of dim, dim, 1, 1, 1 times NE (R+1)^dim values, zones in the caller's order.
+   // out = [x | v | e | rho | p] in blocks of dim, dim, 1, 1, 1 times NE (R+1)^dim values, zones in the caller's order
+   // (out is sized anew when it is smaller than that; a larger one keeps what lies behind the blocks).
    // Asynchronous on the context's stream; the quadrature data is not touched.
    void SampleFields(const Vector &S, const Vector &rho, int R, Vector &out) const;
    long SamplePoints(int R) const; // NE (R+1)^dim
+   // The derived fields of S on the same lattice (lgh_sample_derived).  With NP = SamplePoints(R) and nv = 0, 1, 3 vorticity
+   // components in 1D, 2D, 3D, out holds from `offset` on, whatever the mask:
+   //    [detJ | grad v | div v | vorticity | sound speed] in blocks of 1, dim^2, 1, nv, 1 times NP values
+   // (DerivedSize(R) in all; grad v entry (i, j) = dv_i/dx_j at block i*dim + j, vorticity component-major), each block in
+   // the layout of lgh_sample_derived.  mask: the blocks that are computed (DERIVED_*); the others are left as they are.
+   // out is sized anew (contents lost) when it is smaller than offset + DerivedSize(R).  Asynchronous on the context's
+   // stream; the quadrature data is not touched.
+   enum { DERIVED_DIV = 1, DERIVED_VORT = 2, DERIVED_GRAD = 4, DERIVED_DETJ = 8, DERIVED_CS = 16, DERIVED_ALL = 31 };
+   void SampleDerived(const Vector &S, int R, unsigned mask, Vector &out, long offset = 0) const;
+   long DerivedSize(int R) const; // (3 + dim^2 + nv) NP
    // Conserved integrals, extremes of the point values and counts of bad points of the state S, folded over zones and ranks
    // (lgh_diagnostics; the rows of the driver's `-hist` file).  Synchronous, collective on several ranks; reads S and the
    // set-up data only - the quadrature data, the force products and dt_est stay as they are.

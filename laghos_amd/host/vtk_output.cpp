@@ -82,7 +82,18 @@ const char *kPointArrays[4][2] = {{"density", "1"}, {"velocity", "3"}, {"specifi
 bool WriteVtu(const std::string &dir, int dim, int NE, int R1, const double *x, const double *v, const double *e,
               const double *rho, const double *p, int cycle, double time, int rank, int nranks)
 {
+   return WriteVtuFields(dir, dim, NE, R1, x, v, e, rho, p, {}, cycle, time, rank, nranks);
+}
+
+bool WriteVtuFields(const std::string &dir, int dim, int NE, int R1, const double *x, const double *v, const double *e,
+                    const double *rho, const double *p, const std::vector<VtuField> &extra, int cycle, double time, int rank,
+                    int nranks)
+{
    if (dim < 1 || dim > 3 || NE < 0 || R1 < 2 || !x || !v || !e || !rho || !p) { return false; }
+   for (const VtuField &f : extra)
+   {
+      if (f.name.empty() || f.components < 1 || !f.data) { return false; }
+   }
    const int R = R1 - 1;
    size_t NPZ = 1, NCZ = 1;
    for (int a = 0; a < dim; a++) { NPZ *= R1; NCZ *= R; }
@@ -130,6 +141,7 @@ bool WriteVtu(const std::string &dir, int dim, int NE, int R1, const double *x, 
    h << ap.Array("Float64", "velocity", 3, vel.data(), vel.size() * sizeof(double));
    h << ap.Array("Float64", "specific_internal_energy", 1, e, NP * sizeof(double));
    h << ap.Array("Float64", "pressure", 1, p, NP * sizeof(double));
+   for (const VtuField &f : extra) { h << ap.Array("Float64", f.name.c_str(), f.components, f.data, NP * f.components * sizeof(double)); }
    h << "</PointData>\n<CellData>\n";
    h << ap.Array("Int32", "zone", 1, zone.data(), zone.size() * sizeof(int32_t));
    h << ap.Array("Int32", "rank", 1, rnk.data(), rnk.size() * sizeof(int32_t));
@@ -144,8 +156,14 @@ bool WriteVtu(const std::string &dir, int dim, int NE, int R1, const double *x, 
    return !f.fail();
 }
 
-bool WritePvtu(const std::string &dir, int cycle, double time, int nranks)
+bool WritePvtu(const std::string &dir, int cycle, double time, int nranks) { return WritePvtuFields(dir, cycle, time, nranks, {}); }
+
+bool WritePvtuFields(const std::string &dir, int cycle, double time, int nranks, const std::vector<VtuField> &extra)
 {
+   for (const VtuField &f : extra)
+   {
+      if (f.name.empty() || f.components < 1) { return false; }
+   }
    MakeDirs(dir);
    std::ofstream f((dir + "/" + PvtuName(cycle)).c_str());
    if (!f) { return false; }
@@ -158,6 +176,10 @@ bool WritePvtu(const std::string &dir, int cycle, double time, int nranks)
    for (auto &a : kPointArrays)
    {
       f << "<PDataArray type=\"Float64\" Name=\"" << a[0] << "\" NumberOfComponents=\"" << a[1] << "\"/>\n";
+   }
+   for (const VtuField &a : extra)
+   {
+      f << "<PDataArray type=\"Float64\" Name=\"" << a.name << "\" NumberOfComponents=\"" << a.components << "\"/>\n";
    }
    f << "</PPointData>\n<PCellData>\n<PDataArray type=\"Int32\" Name=\"zone\" NumberOfComponents=\"1\"/>\n"
         "<PDataArray type=\"Int32\" Name=\"rank\" NumberOfComponents=\"1\"/>\n</PCellData>\n";

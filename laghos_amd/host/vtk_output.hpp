@@ -23,8 +23,21 @@ std::string PvtuName(int cycle);
 // rank (Int32); FieldData TIME, CYCLE.  Little endian, UInt64 headers, every array in one raw appended block.
 bool WriteVtu(const std::string &dir, int dim, int NE, int R1, const double *x, const double *v, const double *e,
               const double *rho, const double *p, int cycle, double time, int rank, int nranks);
+// The same piece with further PointData arrays behind the four standing ones, in the order given: each `components`
+// Float64 values per point, point by point (data[components * pt + c]).  No extras: the bytes of WriteVtu.
+struct VtuField
+{
+   std::string name;
+   int components;
+   const double *data;
+};
+bool WriteVtuFields(const std::string &dir, int dim, int NE, int R1, const double *x, const double *v, const double *e,
+                    const double *rho, const double *p, const std::vector<VtuField> &extra, int cycle, double time, int rank,
+                    int nranks);
 // <dir>/PvtuName(): the pieces of all ranks of one cycle
 bool WritePvtu(const std::string &dir, int cycle, double time, int nranks);
+// ... whose pieces carry the extra arrays (name and components are read, data is not)
+bool WritePvtuFields(const std::string &dir, int cycle, double time, int nranks, const std::vector<VtuField> &extra);
 // The collection <pvd_path>: one DataSet per dump so far, file = <rel_dir>/<piece or .pvtu>
 bool WritePvd(const std::string &pvd_path, const std::string &rel_dir, const std::vector<double> &times,
               const std::vector<int> &cycles, int nranks);

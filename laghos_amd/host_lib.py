@@ -65,6 +65,15 @@ def load():
         L.laghos_host_write_pvtu.argtypes = [ctypes.c_char_p, I, D, I]
         L.laghos_host_write_pvd.restype = I
         L.laghos_host_write_pvd.argtypes = [ctypes.c_char_p, ctypes.c_char_p, I, P, P, I]
+        L.laghos_host_lattice_grad_table.restype = I
+        L.laghos_host_lattice_grad_table.argtypes = [I, I, P]
+        L.laghos_host_write_vtu_fields.restype = I
+        L.laghos_host_write_vtu_fields.argtypes = [ctypes.c_char_p, I, I, I, P, P, P, P, P, I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(I),
+                                                   ctypes.POINTER(P), I, D, I, I]
+        L.laghos_host_write_pvtu_fields.restype = I
+        L.laghos_host_write_pvtu_fields.argtypes = [ctypes.c_char_p, I, D, I, I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(I)]
+        L.laghos_sim_derived_fields.restype = I
+        L.laghos_sim_derived_fields.argtypes = [P, I, P, P, P, P, P]
         ULL = ctypes.c_ulonglong
         L.laghos_sim_repeats.restype = I
         L.laghos_sim_repeats.argtypes = [P]
@@ -174,6 +183,24 @@ class Sim:
             raise RuntimeError(f"laghos_sim_profile: error {rc}: {self.L.laghos_sim_error(self.h).decode()}")
         return profile_dict(rows, n_excl.value, float(lo), float(hi))
 
+    def derived_fields(self, R):
+        """The derived fields of the state as it stands on the lattice of R cells per zone and direction (lgh_sample_derived;
+        what `-pv-fields` adds to a dump): a dict detj, div_v, sound_speed (NP), grad_v (dim^2, NP; entry i*dim + j = dv_i/dx_j)
+        and, in 2D and 3D, vorticity (NP or (3, NP)), NP = NE (R+1)^dim, zones in the caller's order."""
+        sz = self.sizes()
+        dim, NP = sz["dim"], sz["NE"] * (R + 1) ** sz["dim"]
+        # NaN-filled: an entry the library did not write would show
+        out = dict(detj=np.full(NP, np.nan), grad_v=np.full((dim * dim, NP), np.nan), div_v=np.full(NP, np.nan))
+        if dim > 1:
+            out["vorticity"] = np.full(NP if dim == 2 else (3, NP), np.nan)
+        out["sound_speed"] = np.full(NP, np.nan)
+        vort = out["vorticity"].ctypes.data if dim > 1 else None
+        rc = self.L.laghos_sim_derived_fields(self.h, int(R), out["detj"].ctypes.data, out["grad_v"].ctypes.data, out["div_v"].ctypes.data, vort,
+                                              out["sound_speed"].ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"laghos_sim_derived_fields: error {rc}: {self.L.laghos_sim_error(self.h).decode()}")
+        return out
+
     def sedov_error(self):
         """`-err`: L2 error of the density against the exact Sedov solution at t_final."""
         return self.L.laghos_sim_sedov_error(self.h)
@@ -264,6 +291,15 @@ def host_lattice_tables(order_v, order_e, R):
     return Bh.reshape(D, R1).T, Bl.reshape(Ld, R1).T
 
 
+def host_lattice_grad_table(order_v, R):
+    """The derivatives of the 1-D H1 basis at the lattice abscissae r/R (Context.sample_derived): (R+1, order_v+1), indexed [r, d]."""
+    R1, D = R + 1, order_v + 1
+    G = np.empty(R1 * D)
+    if load().laghos_host_lattice_grad_table(order_v, R, G.ctypes.data) != 0:
+        raise ValueError(f"host_lattice_grad_table({order_v}, {R})")
+    return G.reshape(D, R1).T
+
+
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
@@ -279,6 +315,41 @@ def host_write_vtu(directory, dim, NE, R1, x, v, e, rho, p, cycle, time, rank=0,
         raise RuntimeError(f"cannot write a .vtu under {directory}")
     tag = f"cycle_{cycle:06d}" + (f".{rank}" if nranks > 1 else "")
     return os.path.join(str(directory), tag + ".vtu")
+
+
+def _extra_args(extra, NP=None):
+    """(n, names, comps, data pointers, the arrays kept alive) of a list of (name, components, array) for the *_fields writers"""
+    n = len(extra)
+    arrs = [None if a is None else _f64(a).reshape(-1) for _, _, a in extra]
+    if NP is not None:
+        assert all(a is not None and a.size == NP * int(c) for (_, c, _), a in zip(extra, arrs))
+    names = (ctypes.c_char_p * max(n, 1))(*[str(k).encode() for k, _, _ in extra])
+    comps = (ctypes.c_int * max(n, 1))(*[int(c) for _, c, _ in extra])
+    data = (ctypes.c_void_p * max(n, 1))(*[None if a is None else a.ctypes.data for a in arrs])
+    return n, names, comps, data, arrs
+
+
+def host_write_vtu_fields(directory, dim, NE, R1, x, v, e, rho, p, extra, cycle, time, rank=0, nranks=1):
+    """host_write_vtu with further PointData arrays behind the four standing ones: extra = [(name, components, array)], each
+    array NE * R1^dim * components doubles, point by point ((NP, components) in numpy's order)."""
+    L = load()
+    arrs = [_f64(a) for a in (x, v, e, rho, p)]
+    NP = NE * R1 ** dim
+    assert [a.size for a in arrs] == [dim * NP, dim * NP, NP, NP, NP]
+    n, names, comps, data, keep = _extra_args(extra, NP)
+    if L.laghos_host_write_vtu_fields(str(directory).encode(), dim, NE, R1, *[a.ctypes.data for a in arrs], n, names, comps, data, cycle, time,
+                                      rank, nranks) != 0:
+        raise RuntimeError(f"cannot write a .vtu under {directory}")
+    tag = f"cycle_{cycle:06d}" + (f".{rank}" if nranks > 1 else "")
+    return os.path.join(str(directory), tag + ".vtu")
+
+
+def host_write_pvtu_fields(directory, cycle, time, nranks, extra):
+    """host_write_pvtu whose pieces carry the extra arrays: extra = [(name, components)] (a third entry is ignored)."""
+    n, names, comps, _, _ = _extra_args([(e[0], e[1], None) for e in extra])
+    if load().laghos_host_write_pvtu_fields(str(directory).encode(), cycle, time, nranks, n, names, comps) != 0:
+        raise RuntimeError(f"cannot write a .pvtu under {directory}")
+    return os.path.join(str(directory), f"cycle_{cycle:06d}.pvtu")
 
 
 def host_write_pvtu(directory, cycle, time, nranks):

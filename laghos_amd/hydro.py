@@ -86,6 +86,25 @@ class HydroOperator:
         the curves derived from them.  Reads S and the set-up data only; the quadrature data stays as it is."""
         return self.ctx.profile(S, axis, nbins, lo, hi, origin)
 
+    def derived_fields(self, S, R):
+        """The derived fields of the state S on the lattice of R cells per zone and direction (Context.sample_derived; what
+        `-pv-fields` adds to a dump): a dict of numpy arrays detj, div_v, sound_speed (NP), grad_v (dim^2, NP; entry i*dim + j =
+        dv_i/dx_j) and, in 2D and 3D, vorticity (NP or (3, NP)).  Reads S and the set-up data only."""
+        import numpy as np
+        from . import host_lib
+        p, ctx = self.p, self.ctx
+        dim, NP = p.dim, p.NE * (R + 1) ** p.dim
+        Bh, Bl = host_lib.host_lattice_tables(p.order_v, p.order_e, R)
+        Gh = host_lib.host_lattice_grad_table(p.order_v, R)
+        nan = lambda n: ctx.to_dev(np.full(n, np.nan))   # (an entry the library did not write would show)
+        out = dict(detj=nan(NP), grad_v=nan(dim * dim * NP), div_v=nan(NP), sound_speed=nan(NP))
+        if dim > 1:
+            out["vorticity"] = nan(NP if dim == 2 else 3 * NP)
+        ctx.sample_derived(S, Bh, Gh, Bl, **out)
+        ctx.sync()
+        shape = dict(grad_v=(dim * dim, NP), vorticity=(NP,) if dim == 2 else (3, NP))
+        return {k: t.cpu().numpy().reshape(shape.get(k, (NP,))) for k, t in out.items()}
+
     def reset_time_step_estimate(self):
         self.ctx.set_dt_est(float("inf"))
 
