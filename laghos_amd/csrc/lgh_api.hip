@@ -8,6 +8,7 @@
 
 #include "lgh_common.hpp"
 
+#include <atomic>
 #include <chrono>
 #include <dlfcn.h>
 
@@ -209,7 +210,7 @@ void timer_stop(lgh_ctx *c, int which)
    c->timers.t[which] += 1e-3 * ms;
 }
 
-// ---- roctx ranges (LGH_ROCTX=1) ----------------------------------------------------------------
+// ---- roctx ranges (LGH_ROCTX=1): the library is loaded by the first context created with the switch, for the process
 namespace
 {
 struct Roctx
@@ -218,8 +219,6 @@ struct Roctx
    int (*pop)() = nullptr;
    Roctx()
    {
-      const char *env = getenv("LGH_ROCTX");
-      if (!(env && env[0] == '1')) { return; }
       void *h = nullptr;
       for (const char *n : {"librocprofiler-sdk-roctx.so", "librocprofiler-sdk-roctx.so.1", "libroctx64.so", "libroctx64.so.4"})
       {
@@ -232,19 +231,103 @@ struct Roctx
       if (!push || !pop) { push = nullptr; pop = nullptr; }
    }
 };
-const Roctx &roctx()
+std::atomic<const Roctx *> g_roctx{nullptr};
+void roctx_enable()
 {
    static const Roctx r;
-   return r;
+   g_roctx.store(&r);
+}
+
+// ---- the environment switches (lgh_common.hpp Switches): the one place that reads them
+// a flag: '0...' is 0, '1...' is 1, anything else (and no variable) is `unset`
+int env_flag(const char *name, const int unset)
+{
+   const char *e = getenv(name);
+   return (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : unset;
+}
+// a number; a variable that does not start with one counts as not set
+long env_long(const char *name, const long unset)
+{
+   const char *e = getenv(name);
+   char *end = nullptr;
+   const long v = e ? strtol(e, &end, 10) : 0;
+   return (e && end != e) ? v : unset;
+}
+double env_double(const char *name, const double unset)
+{
+   const char *e = getenv(name);
+   char *end = nullptr;
+   const double v = e ? strtod(e, &end) : 0.0;
+   return (e && end != e) ? v : unset;
+}
+std::string env_string(const char *name)
+{
+   const char *e = getenv(name);
+   return e ? e : "";
 }
 } // namespace
-RoctxRange::RoctxRange(const char *name) : on(roctx().push != nullptr)
+RoctxRange::RoctxRange(const char *name) : on(false)
 {
-   if (on) { (void)roctx().push(name); }
+   const Roctx *r = g_roctx.load();
+   on = r && r->push != nullptr;
+   if (on) { (void)r->push(name); }
 }
 RoctxRange::~RoctxRange()
 {
-   if (on) { (void)roctx().pop(); }
+   if (on) { (void)g_roctx.load()->pop(); }
+}
+
+Switches read_switches()
+{
+   Switches s;
+   s.vcg_variant = (int)env_long("LGH_VCG_VARIANT", -1);
+   s.slab_wide = env_flag("LGH_SLAB_WIDE", 1);
+   s.slab_exact = env_flag("LGH_SLAB_EXACT", 1);
+   s.slab_merge = env_flag("LGH_SLAB_MERGE", 1);
+   s.slab_defer = env_flag("LGH_SLAB_DEFER", 1);
+   s.slab_ye_wide = env_flag("LGH_SLAB_YE_WIDE", 0);
+   s.slab_dyn = env_flag("LGH_SLAB_DYN", -1);
+   s.rz_limbs = env_flag("LGH_RZ_LIMBS", 1);
+   s.kron_neb = env_flag("LGH_KRON_NEB", 1);
+   s.fused_init = env_flag("LGH_FUSED_INIT", 1);
+   s.k2p = env_flag("LGH_K2P", 1);
+   s.k2_skip = env_flag("LGH_K2_SKIP", 1);
+   s.k2_grid = (int)env_long("LGH_K2_GRID", 0);
+   s.k2_node_weight = env_long("LGH_K2_NODE_WEIGHT", 5);
+   s.order = env_flag("LGH_ORDER", 1);
+   s.order_multi = env_flag("LGH_ORDER_MULTI", 1);
+   s.comm2 = env_flag("LGH_COMM2", -1);
+   s.force_multi = env_flag("LGH_FORCE_MULTI", 0);
+   s.halo_piggyback = env_flag("LGH_HALO_PIGGYBACK", 1);
+   s.halo_fused_pack = env_flag("LGH_HALO_FUSED_PACK", 1);
+   s.overlap = env_flag("LGH_OVERLAP", 1);
+   s.energy_lockstep = env_flag("LGH_ENERGY_LOCKSTEP", 1);
+   s.spin = env_flag("LGH_SPIN", 1);
+   s.mass_sep = env_flag("LGH_MASS_SEP", 1);
+   s.mass_kron = env_flag("LGH_MASS_KRON", 1);
+   s.mass_rank1 = env_flag("LGH_MASS_RANK1", 1);
+   s.mass_rank1_tol = env_double("LGH_MASS_RANK1_TOL", kMassRank1Tol);
+   s.l2_neb = env_flag("LGH_L2_NEB", 1);
+   s.l2_plane = env_flag("LGH_L2_PLANE", 1);
+   s.l2_fused = env_flag("LGH_L2_FUSED", 1);
+   s.q_form = env_flag("LGH_Q_FORM", 1);
+   s.q_ppt = env_flag("LGH_Q_PPT", 0);
+   s.q_swz = (int)env_long("LGH_Q_SWZ", -1);
+   s.q_occ4 = env_flag("LGH_Q_OCC4", -1);
+   s.q_tiny_grad = env_double("LGH_Q_TINY_GRAD", 1e-30); // 0: exact zeros only; -1: off
+   s.fused_ftv = env_flag("LGH_FUSED_FTV", 1);
+   s.fused_f1 = env_flag("LGH_FUSED_F1", 1);
+   s.b_sym = env_flag("LGH_B_SYM", 1);
+   s.jac0_compact = env_flag("LGH_JAC0_COMPACT", 1);
+   // (a tolerance above 1e-10 would turn curved zones into affine ones: clamped - round-5 advisor)
+   s.jac0_tol = std::min(std::max(env_double("LGH_JAC0_TOL", kJac0Tol), 0.0), 1e-10);
+   s.profile_fold = (int)std::max(0L, env_long("LGH_PROFILE_FOLD", 8));
+   s.roctx = env_flag("LGH_ROCTX", 0);
+   s.vcg_trace = env_string("LGH_VCG_TRACE");
+   s.vcg_trace_phases = getenv("LGH_VCG_TRACE_PHASES") != nullptr;
+   s.q_trace = env_string("LGH_Q_TRACE");
+   s.q_trace_call = (int)env_long("LGH_Q_TRACE_CALL", 40);
+   return s;
 }
 
 template <typename T> static int dev_alloc_copy(T **dst, const T *src, size_t n)
@@ -280,8 +363,7 @@ namespace lgh
 {
 int host_wait_token(lgh_ctx *c, volatile unsigned long long *word, const unsigned long long token)
 {
-   const bool spin = !(getenv("LGH_SPIN") && getenv("LGH_SPIN")[0] == '0'); // (per call: the switch tests flip it inside one process)
-   if (spin)
+   if (c->sw.spin)
    {
       // polling for at most ~50 ms (a look normally returns within the tail of the last enqueued kernels: a chunk of
       // iterations, 1-20 ms); a host that would wait longer than that sleeps in the stream synchronisation below instead
@@ -375,6 +457,8 @@ int lgh_create(const lgh_config *cfg, lgh_ctx **out)
    lgh_ctx *c = new lgh_ctx();
    memset((void *)c, 0, sizeof(lgh_ctx));
    new (&c->timers) Timers();
+   new (&c->sw) Switches(read_switches());
+   if (c->sw.roctx) { roctx_enable(); }
    c->device = cfg->device;
    // every failure below (HIP errors, out of memory) releases what was built so far
    const int rc_create = (cfg->dim == 1) ? create_1d(cfg, c) : create_impl(cfg, c, kid);
@@ -402,13 +486,9 @@ static int create_impl(const lgh_config *cfg, lgh_ctx *c, const int kid)
    c->vort = cfg->use_vorticity != 0;
    c->cfl = cfg->cfl;
    c->h1order = (double)cfg->order_v;
-   {
-      // LGH_Q_TINY_GRAD=<value>: default threshold of the QUpdate shortcut; 0: exact zeros only; -1: off
-      const char *env = getenv("LGH_Q_TINY_GRAD");
-      c->q_tiny_grad = env ? atof(env) : 1e-30;
-      c->stress_store = 1; // (the reference's behaviour: UpdateQuadratureData leaves stressJinvT in memory)
-      c->stress_current = 0;
-   }
+   c->q_tiny_grad = c->sw.q_tiny_grad;
+   c->stress_store = 1; // (the reference's behaviour: UpdateQuadratureData leaves stressJinvT in memory)
+   c->stress_current = 0;
    c->h0 = 0.0;
    c->device = cfg->device;
    c->cur_ess = -1;
@@ -422,9 +502,8 @@ static int create_impl(const lgh_config *cfg, lgh_ctx *c, const int kid)
    LGH_TRY(dev_alloc_copy(&c->B, cfg->B_h1, (size_t)c->Q1D * c->D1D));
    {
       // mirror symmetry of the tables (every nodal or Bernstein basis on symmetric points has it); LGH_B_SYM=0: assume not
-      const char *env = getenv("LGH_B_SYM");
       auto mirror = [&](const double *B, const int n) {
-         if (env && env[0] == '0') { return 0; }
+         if (!c->sw.b_sym) { return 0; }
          for (int i = 0; i < n; i++)
          {
             const double u = B[i], v = B[n - 1 - i];
@@ -463,12 +542,10 @@ static int create_impl(const lgh_config *cfg, lgh_ctx *c, const int kid)
          const double prod = (dim == 3) ? w1[qx] * w1[qy] * w1[qz] : w1[qx] * w1[qy];
          ok = std::fabs(prod - cfg->weights[q]) <= 1.8e-15 * std::fabs(cfg->weights[q]);
       }
-      const char *senv = getenv("LGH_MASS_SEP"); // A/B: 0 = weights from the NQ-entry table
-      if (ok && !(senv && senv[0] == '0')) { LGH_TRY(dev_alloc_copy(&c->w1d, w1.data(), (size_t)Q)); }
+      if (ok && c->sw.mass_sep) { LGH_TRY(dev_alloc_copy(&c->w1d, w1.data(), (size_t)Q)); } // (LGH_MASS_SEP=0, A/B: weights from the NQ-entry table)
       // 1-D mass tiles of the two bases on this rule, M1[i + n j] = sum_q B[q, i] w[q] B[q, j] (long double sums, rounded
       // once): with compact mass data the element matrices are s_e M1 (x) M1 (x) M1 (lgh_vcg_slab.hip, lgh_mass.hip)
-      const char *kenv = getenv("LGH_MASS_KRON"); // A/B: 0 = always contract through the quadrature points
-      if (c->w1d && !(kenv && kenv[0] == '0'))
+      if (c->w1d && c->sw.mass_kron) // (LGH_MASS_KRON=0, A/B: always contract through the quadrature points)
       {
          auto tile = [&](const double *Bt, const int n, double **out) -> int {
             std::vector<double> M((size_t)n * n);
@@ -512,17 +589,6 @@ static int create_impl(const lgh_config *cfg, lgh_ctx *c, const int kid)
          for (int k = off[n]; k < off[(size_t)n + 1]; k++) { ell[(size_t)(k - off[n]) * c->N + n] = idx[k]; }
       c->t_deg = deg;
       LGH_TRY(dev_alloc_copy(&c->t_ell, ell.data(), ell.size()));
-      const char *env = getenv("LGH_VCG_VARIANT"); // A/B switch of the lockstep K1 (lgh_vcg.hip)
-      c->vcg_variant = (env && env[0] >= '0' && env[0] <= '9') ? env[0] - '0' : -1; // -1: by kernel id and mesh size (vcg_k1_form)
-      // slab-form K1 (lgh_vcg_slab.hip), A/B: wavefronts per SIMD (default 1), row loads, exact sum of (d, A d), sets drawn from a workgroup queue
-      env = getenv("LGH_SLAB_WPS");
-      c->slab_wps = (env && env[0] == '2') ? 2 : 1;
-      env = getenv("LGH_SLAB_WIDE");
-      c->slab_wide = (env && env[0] == '0') ? 0 : 1;
-      env = getenv("LGH_SLAB_EXACT");
-      c->slab_exact = (env && env[0] == '0') ? 0 : 1;
-      env = getenv("LGH_SLAB_DYN");
-      c->slab_dyn = (env && env[0] == '0') ? 0 : (env && env[0] == '1') ? 1 : -1; // -1: by passes per wavefront (launch_vcg_slab)
    }
    for (int k = 0; k < 3; k++)
    {
@@ -550,16 +616,15 @@ static int create_impl(const lgh_config *cfg, lgh_ctx *c, const int kid)
    LGH_TRY(dev_alloc_zero(&c->dinvV, (size_t)c->N));
    LGH_TRY(dev_alloc_zero(&c->dt_est_dev, (size_t)kDtSlotStride * (1 + kDtSlots)));
    {
-      const char *env = getenv("LGH_FUSED_FTV"); // A/B: 0 = F^T v always by its own kernel
-      if (!(env && env[0] == '0'))
+      if (c->sw.fused_ftv) // (LGH_FUSED_FTV=0, A/B: F^T v always by its own kernel)
       {
          LGH_TRY(dev_alloc_zero(&c->erhs_q, (size_t)c->L2V));
          LGH_TRY(dev_alloc_zero(&c->v_snap, (size_t)c->H1V));
       }
       LGH_TRY(dev_alloc_zero(&c->dev_flags, (size_t)8));
       c->mass_rank1 = -1;
-      env = getenv("LGH_FUSED_F1");              // A/B: 0 = F.1 always by its own kernel
-      if (c->dim == 3 && !(env && env[0] == '0')) { LGH_TRY(dev_alloc_zero(&c->force_e_q, nmap * dim + (size_t)dim * c->ND)); } // (+ a zero element: vcg_init_force_z_k)
+      // (LGH_FUSED_F1=0, A/B: F.1 always by its own kernel)
+      if (c->dim == 3 && c->sw.fused_f1) { LGH_TRY(dev_alloc_zero(&c->force_e_q, nmap * dim + (size_t)dim * c->ND)); } // (+ a zero element: vcg_init_force_z_k)
    }
    const size_t ne_nd = nmap * dim;
    LGH_TRY(dev_alloc_zero(&c->XE, std::max<size_t>(ne_nd, (size_t)c->L2V)));
@@ -619,7 +684,6 @@ int lgh_destroy(lgh_ctx *c)
       (void)hipEventDestroy(c->ev_fork);
       (void)hipEventDestroy(c->ev_join);
    }
-   for (auto &ring : c->ls_ev) { for (hipEvent_t e : ring) { if (e) { (void)hipEventDestroy(e); } } }
    extern void lgh_comm_free(lgh_ctx *);
    lgh_comm_free(c);
    if (c->own_stream) { (void)hipStreamDestroy(c->stream); }
@@ -1165,15 +1229,13 @@ int lgh_solve_energy(lgh_ctx *c, const double *S, const double *v_h1, double *dS
 // velocity solve is the longer of the two at every order up to Q4Q3 and its kernels fill the device; the energy solve's small
 // kernels then take what is left instead of an equal share of the dispatch slots: 8.81 -> 8.75 ms per step at C2 on one box,
 // 8.85 -> 8.78 on another; config 5, where the energy CG is the longer one, does not lose (372 -> 367 ms), the highest priority
-// gains nothing anywhere (profiles/r6_stream_priority.txt).  LGH_STREAM2_PRIORITY=d / h: the default / the highest priority.
+// gains nothing anywhere (profiles/r6_stream_priority.txt).
 static int create_stream2(lgh_ctx *c)
 {
-   const char *penv = getenv("LGH_STREAM2_PRIORITY");
-   const char want = (penv && (penv[0] == 'd' || penv[0] == 'h')) ? penv[0] : 'l';
    int least = 0, greatest = 0;
-   if (want != 'd' && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
+   if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
    {
-      LGH_HIP_CHECK(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, want == 'h' ? greatest : least));
+      LGH_HIP_CHECK(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, least));
    }
    else { LGH_HIP_CHECK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking)); }
    LGH_HIP_CHECK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
@@ -1182,8 +1244,7 @@ static int create_stream2(lgh_ctx *c)
 }
 static bool energy_overlap_ok(const lgh_ctx *c)
 {
-   const bool on = !(getenv("LGH_OVERLAP") && getenv("LGH_OVERLAP")[0] == '0');
-   return on && (c->multi == 0 || comm_second_channel(c)) && !c->timers.enabled && !(c->ktime && c->ktime->which >= 0) && vcg_available(c);
+   return c->sw.overlap && (c->multi == 0 || comm_second_channel(c)) && !c->timers.enabled && !(c->ktime && c->ktime->which >= 0) && vcg_available(c);
 }
 int lgh_solve_energy_begin(lgh_ctx *c, const double *S, const double *v_h1, double *dS_dt, double *e_rhs,
                            const double *e_source, double rel_tol, int max_iter)
@@ -1202,29 +1263,13 @@ int lgh_solve_energy_begin(lgh_ctx *c, const double *S, const double *v_h1, doub
       // CG on this one stream and communicator instead of after it - its two dot products per iteration ride on exchanges the
       // velocity iteration makes anyway.  Right-hand side and initial residual here, the iterations inside
       // lgh_solve_velocity, what is left of them in _end.  LGH_ENERGY_LOCKSTEP=0: the solve after the velocity solve.
-      const bool ls_on = !(getenv("LGH_ENERGY_LOCKSTEP") && getenv("LGH_ENERGY_LOCKSTEP")[0] == '0');
-      const bool overlap_wanted = !(getenv("LGH_OVERLAP") && getenv("LGH_OVERLAP")[0] == '0');
-      if (ls_on && overlap_wanted && c->multi != 0 && !comm_second_channel(c) && !c->timers.enabled && !(c->ktime && c->ktime->which >= 0) && vcg_available(c) &&
+      if (c->sw.energy_lockstep && c->sw.overlap && c->multi != 0 && !comm_second_channel(c) && !c->timers.enabled && !(c->ktime && c->ktime->which >= 0) && vcg_available(c) &&
           l2_lockstep_possible(c) && vcg_lockstep_ready(c))
       {
          int rc = energy_rhs(c, v_h1, e_rhs); // :473
          if (rc == LGH_OK && e_source) { rc = vec_axpby(c, e_rhs, 1.0, e_rhs, 1.0, e_source, c->L2V); } // :477
          if (rc == LGH_OK) { rc = cg_l2_begin_lockstep(c, e_rhs, dS_dt + 2 * (size_t)c->H1V, rel_tol, max_iter); }
          if (rc) { return rc; }
-         // its iterations exchange nothing themselves, so their kernels may run BESIDE K1 / K2 on the second stream (no second
-         // communicator needed), ordered by four events per iteration (vcg_solve): LGH_LOCKSTEP_STREAM2=1.  Not the default: the
-         // cross-stream waits cost more than the overlap hides (11.0-11.2 against 10.1 ms per step through the N-rank path on one
-         // rank, profiles/r6_lockstep.txt)
-         c->ls_side = (getenv("LGH_LOCKSTEP_STREAM2") && getenv("LGH_LOCKSTEP_STREAM2")[0] == '1') ? 1 : 0;
-         if (c->ls_side)
-         {
-            if (!c->stream2)
-            {
-               const int rc2 = create_stream2(c);
-               if (rc2) { return rc2; }
-            }
-            for (auto &ring : c->ls_ev) { for (hipEvent_t &e : ring) { if (!e) { LGH_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); } } }
-         }
          c->e_async = 3;
          c->e_lockstep = 1;
          return LGH_OK;

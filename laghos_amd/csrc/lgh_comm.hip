@@ -372,8 +372,7 @@ halo_combine_k(const int n_shared, const int ncomp, const int N, const int *__re
 
 bool halo_can_piggyback(const lgh_ctx *c)
 {
-   const bool on = !(getenv("LGH_HALO_PIGGYBACK") && getenv("LGH_HALO_PIGGYBACK")[0] == '0');
-   return on && c->comm && c->comm->allpairs;
+   return c->sw.halo_piggyback && c->comm && c->comm->allpairs;
 }
 
 // extra != nullptr (device, nextra <= 3 doubles, requires halo_can_piggyback): replaced
@@ -740,7 +739,7 @@ int lgh_comm_init(lgh_ctx *c, int nranks, int rank, const char unique_id[128])
       int rc = shm_open_group(unique_id, nranks, rank, c->comm->shm);
       if (rc) { return rc; }
       // (the exchanges are synchronous on the host: the energy solve's sums may use the second channel's buffers safely)
-      c->comm->channel2 = !(getenv("LGH_COMM2") && getenv("LGH_COMM2")[0] == '0');
+      c->comm->channel2 = c->sw.comm2 != 0;
       c->nranks = nranks;
       c->rank = rank;
       c->multi = 1;
@@ -768,7 +767,7 @@ int lgh_comm_init(lgh_ctx *c, int nranks, int rank, const char unique_id[128])
          g = slot;
       }
       c->comm->local = g;
-      c->comm->channel2 = !(getenv("LGH_COMM2") && getenv("LGH_COMM2")[0] == '0');
+      c->comm->channel2 = c->sw.comm2 != 0;
       c->nranks = nranks;
       c->rank = rank;
       c->multi = 1;
@@ -785,10 +784,7 @@ int lgh_comm_init(lgh_ctx *c, int nranks, int rank, const char unique_id[128])
    LGH_NCCL_CHECK(g_nccl.CommInitRank(&c->comm->comm, nranks, id, rank));
    c->nranks = nranks;
    c->rank = rank;
-   {
-      const char *env = getenv("LGH_FORCE_MULTI");
-      c->multi = (nranks > 1 || (env && env[0] == '1')) ? 1 : 0;
-   }
+   c->multi = (nranks > 1 || c->sw.force_multi) ? 1 : 0;
    // Second communicator (same ranks) for the second stream, so that the energy solve can run beside the velocity solve
    // on several ranks too.  Its id is drawn by rank 0 and travels over the first one TOGETHER with rank 0's verdict (a
    // rank that got no id must not leave the others blocked in CommInitRank); the outcome is then agreed on by a MIN over
@@ -797,8 +793,7 @@ int lgh_comm_init(lgh_ctx *c, int nranks, int rank, const char unique_id[128])
    // in-process loopback here (no multi-GPU box): collectives of different communicators that the ranks happen to
    // schedule in different orders can block each other.  Until a real multi-GPU run has validated it, the channel is
    // therefore opt-in on more than one rank: LGH_COMM2=1 on every rank (LGH_COMM2=0 switches it off everywhere).
-   const char *env2 = getenv("LGH_COMM2");
-   const bool want2 = env2 ? env2[0] == '1' : (nranks == 1);
+   const bool want2 = c->sw.comm2 >= 0 ? c->sw.comm2 == 1 : (nranks == 1);
    if (c->multi && g_nccl.Broadcast && want2)
    {
       Comm *cm = c->comm;

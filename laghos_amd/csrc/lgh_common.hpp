@@ -85,10 +85,47 @@ struct MeshOrder
    int *zorder_d = nullptr, *ncaller_d = nullptr, *nnum_d = nullptr; // the same on the device (nullptr when identity)
 };
 
+constexpr double kMassRank1Tol = 1e-12; // relative spread of D / W inside an element up to which the mass data counts as W[q] s_e (mass_rank1_k)
+constexpr double kJac0Tol = 1e-12;      // ... of Jac0inv inside a zone up to which it counts as one matrix per zone (jac0_compact_k)
+
+// Every environment switch of the library (DESIGN.md "Environment switches"), read ONCE per context: a context's switches
+// are those of the environment at its lgh_create (read_switches, lgh_api.hip - the only place that asks the environment,
+// but for the two properties of the shared-memory transport, LGH_SHM_MB and LGH_SHM_TIMEOUT, read where it is opened).
+// Changing the environment afterwards changes nothing for a context that exists; contexts of one process may differ.
+// Flags are 0 / 1; -1 where "not set" is an answer of its own.  Field x holds LGH_X unless noted.
+struct Switches
+{
+   // velocity CG (lgh_vcg.hip, lgh_vcg_slab.hip)
+   int vcg_variant;      // which K1 form vcg_solve launches; -1: by kernel id and mesh size (vcg_k1_form)
+   int slab_wide, slab_exact, slab_merge, slab_defer, slab_ye_wide; // slab-form K1
+   int slab_dyn;         // ... sets drawn from a workgroup queue: 0 / 1, -1: by passes per wavefront (launch_vcg_slab)
+   int rz_limbs, kron_neb, fused_init;
+   int k2p, k2_skip, k2_grid; // K2; k2_grid: node ranges per CU, 0: by mesh size
+   long k2_node_weight;  // fixed part of a node's cost in units of half a contribution; < 0: equal counts
+   int order, order_multi;
+   // several ranks (lgh_comm.hip), energy solve beside the velocity solve (lgh_api.hip), host looks
+   int comm2;            // -1: not set (the loop-back transports then have the second channel, RCCL on more than one rank does not)
+   int force_multi, halo_piggyback, halo_fused_pack, overlap, energy_lockstep, spin;
+   // mass operators (lgh_mass.hip)
+   int mass_sep, mass_kron, mass_rank1, l2_neb, l2_plane, l2_fused;
+   double mass_rank1_tol; // (default kMassRank1Tol)
+   // quadrature update and set-up
+   int q_form, q_ppt, q_swz, fused_ftv, fused_f1, b_sym, jac0_compact;
+   int q_occ4;           // -1: not set (by viscosity and the form of Jac0inv, launch_qrows)
+   double q_tiny_grad;   // the threshold a context starts with (lgh_ctx::q_tiny_grad)
+   double jac0_tol;      // (default kJac0Tol; at most 1e-10)
+   int profile_fold;
+   // debug
+   int roctx, vcg_trace_phases, q_trace_call;
+   std::string vcg_trace, q_trace; // files; empty: no trace
+};
+Switches read_switches();
+
 } // namespace lgh
 
 struct lgh_ctx
 {
+   lgh::Switches sw;     // the environment switches as they were at lgh_create
    int dim, NE, D1D, Q1D, L1D, ND, NQ, NL, N, H1V, L2V;
    int kid; // (dim<<8)|(D1D<<4)|Q1D, the reference's kernel id
    bool visc, vort;
@@ -104,9 +141,6 @@ struct lgh_ctx
    const double *accel_src; // dim*N acceleration source of SolveVelocity (source_type 2) or nullptr
    int e_async;          // 1: lgh_solve_energy_begin enqueued the solve, 2: deferred to _end
    int e_lockstep;       // lgh_solve_energy_begin has set the energy CG up for LOCKSTEP with the velocity CG on the one stream and communicator
-   int ls_side = 0;      // ... with its kernels on the second stream (they exchange nothing themselves), ordered against the velocity iteration by
-   hipEvent_t ls_ev[4][4] = {}; // events: [0] main -> side after the word exchange, [1] side -> main after the apply, [2] main -> side after the
-                         // halo sums, [3] side -> main after the update; rings of four (iteration & 3).  LGH_LOCKSTEP_STREAM2=1 (default: one stream)
    long ls_stats[3] = {0, 0, 0}; // lockstep energy solves; their iterations enqueued inside the velocity solve; ... and after it (lgh_energy_lockstep_stats)
                          // (several ranks without a second channel; lgh_mass.hip "lockstep"): lgh_solve_velocity interleaves its iterations
    int e_polled, e_iters; // the enqueued solve has already been completed (energy_overlap_poll, from inside the velocity solve): its iteration count
@@ -183,8 +217,6 @@ struct lgh_ctx
    int vcg_grid;         // persistent grid size of the K1 kernel (one resident wave)
    int b_h1_sym, b_l2_sym; // the 1-D H1 / L2 table is mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (to 1e-14: the round-off of its evaluation): kernels may hold half of it
    int ncu;              // CUs of this context's device (0: not asked yet)
-   int vcg_variant;      // LGH_VCG_VARIANT: which K1 form vcg_solve launches (lgh_vcg.hip); -1: by kernel id and mesh size
-   int slab_wps, slab_wide, slab_exact, slab_dyn; // A/B switches of the slab-form K1 (LGH_SLAB_WPS / _WIDE / _EXACT / _DYN, read by lgh_create)
    void *vcg_aux;        // tables of the node kernel K2 (lgh_vcg.hip VcgAux), allocated on first use
 
    lgh::Timers timers;

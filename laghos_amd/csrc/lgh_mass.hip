@@ -866,8 +866,7 @@ mass_apply_l2_kron(const MassArgs a)
 template <int Q> constexpr int neb_for() { return (256 / (Q * Q)) > 0 ? (256 / (Q * Q)) : 1; }
 static bool l2_one_round(const lgh_ctx *c)
 {
-   const char *e = getenv("LGH_L2_NEB");
-   return c->L1D >= 5 && !(e && e[0] == '0');
+   return c->L1D >= 5 && c->sw.l2_neb;
 }
 
 // Which kernel the L2 mass apply (modes 0 / 3: the energy CG) launches, decided in ONE place for the dispatch below
@@ -881,8 +880,7 @@ static int l2_mass_kernel(lgh_ctx *c, int *form, int *compact)
    *form = 0;
    *compact = 0;
    const bool kron_ok = c->dim == 3 && c->M1l && c->w1d && c->L1D <= 5;
-   const char *penv = getenv("LGH_L2_PLANE"); // A/B: 0 = column form
-   const bool plane_ok = c->b_l2_sym && (id == 0x336 || id == 0x348 || id == 0x35A) && !(penv && penv[0] == '0');
+   const bool plane_ok = c->b_l2_sym && (id == 0x336 || id == 0x348 || id == 0x35A) && c->sw.l2_plane; // (LGH_L2_PLANE=0: column form)
    if (kron_ok || plane_ok)
    {
       const int rc = mass_data(c, &Dq, &dqs, &Se);
@@ -994,16 +992,14 @@ template <int MODE> static int launch_mass(lgh_ctx *c, int space, const MassArgs
 // its Kronecker form.  LGH_L2_FUSED=0: cg_update_k reads the stored product (rounds 1-5).
 static bool l2_fused_update(lgh_ctx *c)
 {
-   const bool on = !(getenv("LGH_L2_FUSED") && getenv("LGH_L2_FUSED")[0] == '0'); // (looked up per call: the switch tests flip it inside one process)
    int form = 0, compact = 0;
-   return on && l2_mass_kernel(c, &form, &compact) == LGH_OK && form == 2;
+   return c->sw.l2_fused && l2_mass_kernel(c, &form, &compact) == LGH_OK && form == 2;
 }
 // D[q, e] = W[q] s_e ?  In exact arithmetic the data of laghos_assembly.cpp:92-95, w_q detJ0(x_q) rho0(x_q), has this
 // form whenever the initial element is affine and rho0 constant in it; the stored entries carry the rounding of the
 // Jacobian and density evaluation at each point (measured: 220 ulp at Q3Q2 on the 8^3 box mesh, it grows like 1 / h).
 // One thread per element: s_e = mean of D / W over the points (the centre of that rounding cloud), every point within
 // tol (relative; kMassRank1Tol unless LGH_MASS_RANK1_TOL) or the stored table stays in use.
-constexpr double kMassRank1Tol = 1e-12;
 __global__ void __launch_bounds__(256)
 mass_rank1_k(const int NE, const int NQ, const double tol, const double *__restrict__ D, const double *__restrict__ W, double *__restrict__ S,
              double *__restrict__ ones, int *flag)
@@ -1031,13 +1027,10 @@ int mass_data(lgh_ctx *c, const double **Dq, int *dqs, const double **Se)
       }
       int *flag = c->dev_flags + 3, h = 1;
       LGH_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), c->stream));
-      const char *tenv = getenv("LGH_MASS_RANK1_TOL");
-      const double tol = tenv ? atof(tenv) : kMassRank1Tol;
-      hipLaunchKernelGGL(mass_rank1_k, dim3(ceil_div(c->NE, 256)), dim3(256), 0, c->stream, c->NE, c->NQ, tol, c->massD, c->W, c->massS, c->ones_ne, flag);
+      hipLaunchKernelGGL(mass_rank1_k, dim3(ceil_div(c->NE, 256)), dim3(256), 0, c->stream, c->NE, c->NQ, c->sw.mass_rank1_tol, c->massD, c->W, c->massS, c->ones_ne, flag);
       LGH_HIP_CHECK(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
       LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
-      const char *env = getenv("LGH_MASS_RANK1");
-      c->mass_rank1 = (h == 0 && !(env && env[0] == '0')) ? 1 : 0;
+      c->mass_rank1 = (h == 0 && c->sw.mass_rank1) ? 1 : 0;
    }
    if (c->mass_rank1 == 1) { *Dq = c->W; *dqs = 0; *Se = c->massS; }
    else { *Dq = c->massD; *dqs = c->NQ; *Se = c->ones_ne; }

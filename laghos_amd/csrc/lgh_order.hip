@@ -193,8 +193,7 @@ int mesh_order_build(lgh_ctx *c, const int *map)
    mesh_order_free(c);
    MeshOrder *o = new MeshOrder();
    c->order = o;
-   const char *env = getenv("LGH_ORDER"); // A/B: 0 = the caller's numbering everywhere (rounds 1-5)
-   if (c->dim != 3 || (env && env[0] == '0')) { return LGH_OK; }
+   if (c->dim != 3 || !c->sw.order) { return LGH_OK; } // (LGH_ORDER=0, A/B: the caller's numbering everywhere, rounds 1-5)
    o->structured = analyse(map, c->NE, c->N, c->D1D, *o);
    if (!o->structured)
    {

@@ -567,8 +567,7 @@ extern "C" int lgh_profile(lgh_ctx *c, const double *S, const lgh_profile_spec *
    a.lo = spec->lo;
    a.inv_w = (double)spec->nbins / (spec->hi - spec->lo);
    for (int k = 0; k < 3; k++) { a.origin[k] = (spec->axis == 3 && k < dim) ? spec->origin[k] : 0.0; }
-   const char *fenv = getenv("LGH_PROFILE_FOLD");
-   a.fold = fenv ? std::max(0, atoi(fenv)) : 8;
+   a.fold = c->sw.profile_fold;
    // LDS: as diag_zones_k, with one more array in front of the last axis in 2D and the x offsets beside v and e in 1D
    const size_t S1 = (dim == 3) ? (size_t)D * D * Q : 0, S2 = (dim == 1) ? 0 : (size_t)D * (c->NQ / Q);
    const size_t narr = (dim == 3) ? 9 : (dim == 2 ? 5 : 0);

@@ -853,8 +853,7 @@ template <int MODE> static int launch_q(lgh_ctx *c, const QArgs &a)
          if constexpr (MODE == QMODE_UPDATE)
          {
             // two points per thread: 500-thread workgroups under a cap of 256 registers instead of 1000 under 128 (41 spilled)
-            const char *penv = getenv("LGH_Q_PPT"); // A/B: 1 = one point per thread (read per launch: tests switch it)
-            if (!(penv && penv[0] == '1'))
+            if (!c->sw.q_ppt) // (LGH_Q_PPT=1, A/B: one point per thread)
             {
                hipLaunchKernelGGL((qpoint_kernel<3, 6, 10, 5, 1, 6, MODE, 2>), dim3(c->NE), dim3(500), 0, c->stream, a);
                break;
@@ -893,10 +892,7 @@ static QArgs q_base(lgh_ctx *c)
    a.visc = c->visc;
    a.vort = c->vort;
    a.tiny_grad = c->q_tiny_grad;
-   {
-      const char *senv = getenv("LGH_Q_SWZ"); // A/B: -1 contiguous eighths, 0 none, n: runs of 2^n elements
-      a.q_swz = senv ? atoi(senv) : -1;
-   }
+   a.q_swz = c->sw.q_swz; // A/B: -1 contiguous eighths, 0 none, n: runs of 2^n elements
    a.erhs_q = c->fused_forces_off ? nullptr : c->erhs_q;
    a.force_e = (c->dim == 3 && !c->fused_forces_off) ? c->force_e_q : nullptr;
    {

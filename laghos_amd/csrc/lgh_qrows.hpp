@@ -430,12 +430,11 @@ static bool qrows_available(const lgh_ctx *c)
 // (the buffer and the call counter live in the context - round-5 advisor: file-scope statics were shared by every context)
 static void qrows_trace_dump(lgh_ctx *c)
 {
-   const char *path = getenv("LGH_Q_TRACE");
-   if (!path || !c->q_trace_dev || c->q_trace_n <= 0) { return; }
+   if (c->sw.q_trace.empty() || !c->q_trace_dev || c->q_trace_n <= 0) { return; }
    (void)hipStreamSynchronize(c->stream);
    std::vector<unsigned long long> h((size_t)kQTraceRec * c->q_trace_n);
    if (hipMemcpy(h.data(), c->q_trace_dev, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) { return; }
-   FILE *f = fopen(path, "w");
+   FILE *f = fopen(c->sw.q_trace.c_str(), "w");
    if (!f) { return; }
    for (int i = 0; i < c->q_trace_n; i++)
    {
@@ -447,7 +446,7 @@ static void qrows_trace_dump(lgh_ctx *c)
 }
 template <int MINW6> static int launch_qrows_w(lgh_ctx *c, const QArgs &a)
 {
-   if (c->kid == 0x346 && getenv("LGH_Q_TRACE"))
+   if (c->kid == 0x346 && !c->sw.q_trace.empty())
    {
       if (c->q_trace_n != c->NE)
       {
@@ -458,8 +457,7 @@ template <int MINW6> static int launch_qrows_w(lgh_ctx *c, const QArgs &a)
       if (a.Jac0inv_e) { hipLaunchKernelGGL((qrows_kernel<4, 6, 3, MINW6, true, true>), dim3(c->NE), dim3(216), 0, c->stream, a, c->q_trace_dev); }
       else { hipLaunchKernelGGL((qrows_kernel<4, 6, 3, MINW6, true, false>), dim3(c->NE), dim3(216), 0, c->stream, a, c->q_trace_dev); }
       LGH_HIP_CHECK(hipGetLastError());
-      const char *nenv = getenv("LGH_Q_TRACE_CALL"); // which call to dump (default 40: a developed bench window)
-      if (++c->q_trace_calls == (nenv ? atoi(nenv) : 40)) { qrows_trace_dump(c); }
+      if (++c->q_trace_calls == c->sw.q_trace_call) { qrows_trace_dump(c); } // (LGH_Q_TRACE_CALL: which call to dump)
       return LGH_OK;
    }
 #define LGH_QROWS(D_, Q_, L_, W_, NT_) do { if (a.Jac0inv_e) { hipLaunchKernelGGL((qrows_kernel<D_, Q_, L_, W_, false, true>), dim3(c->NE), dim3(NT_), 0, c->stream, a, (unsigned long long *)nullptr); } \
@@ -478,10 +476,10 @@ template <int MINW6> static int launch_qrows_w(lgh_ctx *c, const QArgs &a)
 }
 static int launch_qrows(lgh_ctx *c, const QArgs &a)
 {
-   const char *oenv = getenv("LGH_Q_OCC4"); // A/B: 0 = the three-wavefront build for every context, 1 = the four-wavefront build
+   // LGH_Q_OCC4, A/B: 0 = the three-wavefront build for every context, 1 = the four-wavefront build
    // (round 5: with one Jac0inv per zone in scalar registers the 128-register build spills 11 instead of 26 and wins with
    //  viscosity as well - 591 -> 584 us at C2, 3.96 -> 3.75 ms at 64^3 Sedov, profiles/r5_q_jac0inv_ab.txt)
-   const bool w4 = oenv ? oenv[0] == '1' : (!a.visc || a.Jac0inv_e != nullptr);
+   const bool w4 = c->sw.q_occ4 >= 0 ? c->sw.q_occ4 == 1 : (!a.visc || a.Jac0inv_e != nullptr);
    return w4 ? launch_qrows_w<4>(c, a) : launch_qrows_w<1>(c, a);
 }
 

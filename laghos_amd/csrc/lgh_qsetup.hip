@@ -7,7 +7,6 @@ namespace lgh
 {
 
 // one thread per zone: Je[k + n2 e] = Jac0inv(point 0 of zone e)[k]; *flag = 1 when a point of some zone differs
-constexpr double kJac0Tol = 1e-12;
 __global__ void __launch_bounds__(64)
 jac0_compact_k(const int NE, const int NQ, const int n2, const double *__restrict__ soa, const double tol, double *__restrict__ Je, int *flag)
 {
@@ -49,16 +48,14 @@ int setup_rho0detj0(lgh_ctx *c, const double *x0, const double *rho0_l2, const d
    // Every entry of every point against the zone's first point, to kJac0Tol of the zone's largest entry; the update then
    // reads nine doubles per zone (lgh_jac0inv_form; LGH_JAC0_COMPACT=0: never).
    {
-      const char *env = getenv("LGH_JAC0_COMPACT"), *tenv = getenv("LGH_JAC0_TOL");
       int *flag = c->dev_flags + 5, h = 1;
       LGH_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), c->stream));
       hipLaunchKernelGGL(jac0_compact_k, dim3(ceil_div(c->NE, 64)), dim3(64), 0, c->stream, c->NE, c->NQ, c->dim * c->dim, c->Jac0inv_soa,
-                         // (a tolerance above 1e-10 would turn curved zones into affine ones: clamped - round-5 advisor)
-                         tenv ? std::min(std::max(atof(tenv), 0.0), 1e-10) : kJac0Tol, c->Jac0inv_e, flag);
+                         c->sw.jac0_tol, c->Jac0inv_e, flag);
       LGH_HIP_CHECK(hipGetLastError());
       LGH_HIP_CHECK(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
       LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
-      c->jac0_compact = (h == 0 && !(env && env[0] == '0')) ? 1 : 0;
+      c->jac0_compact = (h == 0 && c->sw.jac0_compact) ? 1 : 0;
    }
    *volume = c->host_pinned[0];
    return LGH_OK;

@@ -38,8 +38,7 @@ int qupdate(lgh_ctx *c, const double *S)
 // which form lgh_qupdate launches for this context: 1 = row form (lgh_qrows.hpp), 0 = point form (qpoint_kernel)
 int qupdate_form(lgh_ctx *c)
 {
-   const char *fenv = getenv("LGH_Q_FORM");
-   return (qrows_available(c) && !(fenv && fenv[0] == '0')) ? 1 : 0;
+   return (qrows_available(c) && c->sw.q_form) ? 1 : 0;
 }
 
 int interp_energy(lgh_ctx *c, int which, const double *vec, double *result)

@@ -1343,9 +1343,9 @@ vcg_update_k(const VcgArgs a)
 //  * four workgroups of 512 threads per CU (more on large meshes: ranges of at most ~1000 nodes), each with a contiguous node range of equal COST (a node costs a
 //    fixed part plus a part per element contribution; with equal counts the ranges that cover
 //    element-boundary planes take 40 % longer), all ~35 loads of a node issued before the first use,
-//    straight-line code.  One node per thread and pass (U = 1: 106 VGPRs, two workgroups resident per CU)
-//    beats two (U = 2: 182 VGPRs, one resident; what the persistent kernel's node phase used): 55.4 -> 49.7 us
-//    at C2 (LGH_K2_U=2, LGH_K2_GRID=<workgroups per CU> for A/B);
+//    straight-line code.  One node per thread and pass (106 VGPRs, two workgroups resident per CU) - two
+//    (182 VGPRs, one resident; what the persistent kernel's node phase used) lost, 55.4 against 49.7 us
+//    at C2 (LGH_K2_GRID=<workgroups per CU> for A/B);
 //  * the ELL row holds byte offsets and absent contributions point at a zero slot behind the Y_E plane: no
 //    predicated loads, addresses are one SGPR base + a 32-bit VGPR offset;
 //  * x is only needed at the end of the solve: it is updated every second iteration with both terms,
@@ -1359,7 +1359,7 @@ vcg_update_k(const VcgArgs a)
 // 4 = the budget of rounds 2-4 (up to 128 VGPRs: two workgroups of eight wavefronts per CU), 6 = at most 80 (three).  The kernel is a chain of dependent memory round trips per pass
 // (table -> element contributions -> stores), and what hides them is the number of wavefronts a CU holds; the second
 // table (slots 4..7) is summed in a branch of its own so that its 24 registers exist only there.
-template <bool XU, int U, int MINW = 4>
+template <bool XU, int MINW>
 __global__ void __launch_bounds__(512, MINW)
 vcg_update_p_k(const VcgArgs a)
 {
@@ -1416,48 +1416,31 @@ vcg_update_p_k(const VcgArgs a)
    const unsigned zoff = 8u * (unsigned)(a.ye_stride - kYePad); // byte offset of the zero slot (make_ellz)
    const char *const ellhi = (const char *)a.ellz + (size_t)16 * (size_t)a.N; // slots 4..7
    double part[kVC] = {0.0, 0.0, 0.0};
-   for (int base = n0; base < n1; base += NT * U)
+   for (int base = n0; base < n1; base += NT)
    {
-      unsigned nn[U];
-      bool ok[U];
-#pragma unroll
-      for (int u = 0; u < U; u++)
-      {
-         const int n = base + tid + u * NT;
-         ok[u] = n < n1;
-         nn[u] = (unsigned)(ok[u] ? n : n0);
-      }
+      const int n = base + tid;
+      const bool ok = n < n1;
+      const unsigned nn = (unsigned)(ok ? n : n0);
       // ELL rows as two tables of four offsets per node (16 bytes each): slots 0..3 with one load per node; slots 4..7 -
       // only a vertex node of the mesh has more than four contributions, with the merged E-vector of the slab K1 only
       // where a set boundary meets an element edge in y and z - are fetched when some node of the wavefront uses them
       // (rows hold their contributions first, so slot 3 tells): a ninth of the wavefronts, 16 of the table's 32 bytes per
       // node for the others
-      unsigned ix[U][4];
-      bool hi_any = false;
+      unsigned ix[4];
+      const v4u_ q0 = *(const v4u_ *)((const char *)a.ellz + 16u * nn);
+      ix[0] = q0[0]; ix[1] = q0[1]; ix[2] = q0[2]; ix[3] = q0[3];
+      const bool hi = !a.k2_skip || __any(q0[3] != zoff);
+      double ro[kVC], dol[kVC], xo[kVC];
+      const double di = vcg_ld(a.dinv, 8u * nn);
+      const unsigned es = a.essbits[nn];
 #pragma unroll
-      for (int u = 0; u < U; u++)
+      for (int k = 0; k < kVC; k++)
       {
-         const v4u_ q0 = *(const v4u_ *)((const char *)a.ellz + 16u * nn[u]);
-         ix[u][0] = q0[0]; ix[u][1] = q0[1]; ix[u][2] = q0[2]; ix[u][3] = q0[3];
-         hi_any = hi_any || (q0[3] != zoff);
-      }
-      const bool hi = !a.k2_skip || __any(hi_any);
-      double di[U], ro[U][kVC], dol[U][kVC], xo[U][kVC];
-      unsigned es[U];
-#pragma unroll
-      for (int u = 0; u < U; u++)
-      {
-         di[u] = vcg_ld(a.dinv, 8u * nn[u]);
-         es[u] = a.essbits[nn[u]];
-#pragma unroll
-         for (int k = 0; k < kVC; k++)
-         {
-            const unsigned vb = 8u * nn[u] + (unsigned)k * compb;
-            ro[u][k] = vcg_ld(a.r, vb);
-            dol[u][k] = vcg_ld(a.d, vb);
-            xo[u][k] = 0.0;
-            if (XU && MINW < 6) { xo[u][k] = vcg_ld(a.x, vb); }
-         }
+         const unsigned vb = 8u * nn + (unsigned)k * compb;
+         ro[k] = vcg_ld(a.r, vb);
+         dol[k] = vcg_ld(a.d, vb);
+         xo[k] = 0.0;
+         if (XU && MINW < 6) { xo[k] = vcg_ld(a.x, vb); }
       }
       // Slot j of the ELL rows is only fetched when some node of the wavefront has a j-th contribution (rows hold
       // their contributions first): a wave of consecutive nodes of a tensor-product mesh rarely needs all 8 (a
@@ -1466,45 +1449,26 @@ vcg_update_p_k(const VcgArgs a)
       bool need[4];
       need[0] = true;
 #pragma unroll
-      for (int j = 1; j < 4; j++)
+      for (int j = 1; j < 4; j++) { need[j] = !a.k2_skip || __any(ix[j] != zoff); }
+      double zsum[kVC]; // ascending contribution order (absent slots add 0.0): the sum of vcg_update_k
       {
-         bool any = false;
-#pragma unroll
-         for (int u = 0; u < U; u++) { any = any || (ix[u][j] != zoff); }
-         need[j] = !a.k2_skip || __any(any);
-      }
-      double zsum[U][kVC]; // ascending contribution order (absent slots add 0.0): the sum of vcg_update_k
-      {
-         double ye[U][kVC][4];
+         double ye[kVC][4];
 #pragma unroll
          for (int j = 0; j < 4; j++)
          {
             if (need[j])
             {
 #pragma unroll
-               for (int k = 0; k < kVC; k++)
-               {
-                  const double *yc = a.YE + (size_t)k * a.ye_stride;
-#pragma unroll
-                  for (int u = 0; u < U; u++) { ye[u][k][j] = vcg_ld(yc, ix[u][j]); }
-               }
+               for (int k = 0; k < kVC; k++) { ye[k][j] = vcg_ld(a.YE + (size_t)k * a.ye_stride, ix[j]); }
             }
             else
             {
 #pragma unroll
-               for (int k = 0; k < kVC; k++)
-               {
-#pragma unroll
-                  for (int u = 0; u < U; u++) { ye[u][k][j] = 0.0; }
-               }
+               for (int k = 0; k < kVC; k++) { ye[k][j] = 0.0; }
             }
          }
 #pragma unroll
-         for (int u = 0; u < U; u++)
-         {
-#pragma unroll
-            for (int k = 0; k < kVC; k++) { zsum[u][k] = ((0.0 + ye[u][k][0]) + ye[u][k][1]) + ye[u][k][2]; zsum[u][k] += ye[u][k][3]; }
-         }
+         for (int k = 0; k < kVC; k++) { zsum[k] = ((0.0 + ye[k][0]) + ye[k][1]) + ye[k][2]; zsum[k] += ye[k][3]; }
       }
       if (XU && MINW >= 6 && xload)
       {
@@ -1512,65 +1476,46 @@ vcg_update_p_k(const VcgArgs a)
          //  per node would otherwise be live beside their 24, and the budget of 80 does not hold both; the other
          //  wavefronts of the SIMD cover the round trip)
 #pragma unroll
-         for (int u = 0; u < U; u++)
-         {
-#pragma unroll
-            for (int k = 0; k < kVC; k++) { asm volatile("" : "+v"(zsum[u][k])); xo[u][k] = vcg_ld(a.x, 8u * nn[u] + (unsigned)k * compb); }
-         }
+         for (int k = 0; k < kVC; k++) { asm volatile("" : "+v"(zsum[k])); xo[k] = vcg_ld(a.x, 8u * nn + (unsigned)k * compb); }
       }
       if (hi)
       {
          // contributions 5..8 (a ninth of the wavefronts): second table, then the values, added behind the first four
-#pragma unroll
-         for (int u = 0; u < U; u++)
-         {
-            const v4u_ q1 = *(const v4u_ *)(ellhi + 16u * nn[u]);
-#pragma unroll
-            for (int k = 0; k < kVC; k++)
-            {
-               const double *yc = a.YE + (size_t)k * a.ye_stride;
-               const double y4 = vcg_ld(yc, q1[0]), y5 = vcg_ld(yc, q1[1]), y6 = vcg_ld(yc, q1[2]), y7 = vcg_ld(yc, q1[3]);
-               zsum[u][k] = (((zsum[u][k] + y4) + y5) + y6) + y7;
-            }
-         }
-      }
-      // several ranks: a node shared with another rank takes its A d from the L-vector the halo exchange has summed
-      double ysh[U][kVC];
-      bool anysh = false;
-#pragma unroll
-      for (int u = 0; u < U; u++) { anysh = anysh || ((es[u] >> 3) & 1u); }
-      anysh = a.multi && __any(anysh);
-#pragma unroll
-      for (int u = 0; u < U; u++)
-      {
-#pragma unroll
-         for (int k = 0; k < kVC; k++) { ysh[u][k] = anysh ? vcg_ld(a.yL, 8u * nn[u] + (unsigned)k * compb) : 0.0; }
-      }
-#pragma unroll
-      for (int u = 0; u < U; u++)
-      {
-         const double ow = ((es[u] >> 4) & 1u) ? 0.0 : 1.0; // (1 on one rank)
+         const v4u_ q1 = *(const v4u_ *)(ellhi + 16u * nn);
 #pragma unroll
          for (int k = 0; k < kVC; k++)
          {
-            const unsigned vb = 8u * nn[u] + (unsigned)k * compb;
-            double zs = zsum[u][k];
-            if (anysh && ((es[u] >> 3) & 1u)) { zs = ysh[u][k]; }
-            const double z_ = ((es[u] >> k) & 1u) ? 0.0 : zs;
-            const double zold = __dmul_rn(ro[u][k], di[u]); // z of the previous iterate, not stored
-            const double dnew = first ? zold : fma(beta[k], dol[u][k], zold);
-            const double rnew = ro[u][k] - alpha[k] * z_;
-            if (ok[u] && todo[k])
+            const double *yc = a.YE + (size_t)k * a.ye_stride;
+            const double y4 = vcg_ld(yc, q1[0]), y5 = vcg_ld(yc, q1[1]), y6 = vcg_ld(yc, q1[2]), y7 = vcg_ld(yc, q1[3]);
+            zsum[k] = (((zsum[k] + y4) + y5) + y6) + y7;
+         }
+      }
+      // several ranks: a node shared with another rank takes its A d from the L-vector the halo exchange has summed
+      double ysh[kVC];
+      const bool anysh = a.multi && __any((es >> 3) & 1u);
+#pragma unroll
+      for (int k = 0; k < kVC; k++) { ysh[k] = anysh ? vcg_ld(a.yL, 8u * nn + (unsigned)k * compb) : 0.0; }
+      const double ow = ((es >> 4) & 1u) ? 0.0 : 1.0; // (1 on one rank)
+#pragma unroll
+      for (int k = 0; k < kVC; k++)
+      {
+         const unsigned vb = 8u * nn + (unsigned)k * compb;
+         double zs = zsum[k];
+         if (anysh && ((es >> 3) & 1u)) { zs = ysh[k]; }
+         const double z_ = ((es >> k) & 1u) ? 0.0 : zs;
+         const double zold = __dmul_rn(ro[k], di); // z of the previous iterate, not stored
+         const double dnew = first ? zold : fma(beta[k], dol[k], zold);
+         const double rnew = ro[k] - alpha[k] * z_;
+         if (ok && todo[k])
+         {
+            *vcg_ptr(a.d, vb) = dnew;
+            *vcg_ptr(a.r, vb) = rnew;
+            if (XU)
             {
-               *vcg_ptr(a.d, vb) = dnew;
-               *vcg_ptr(a.r, vb) = rnew;
-               if (XU)
-               {
-                  const double x0 = xload ? xo[u][k] : 0.0;
-                  *vcg_ptr(a.x, vb) = fma(alpha[k], dnew, fma(alpha_prev[k], first ? 0.0 : dol[u][k], x0));
-               }
-               part[k] += (a.multi ? ow : 1.0) * rnew * __dmul_rn(rnew, di[u]);
+               const double x0 = xload ? xo[k] : 0.0;
+               *vcg_ptr(a.x, vb) = fma(alpha[k], dnew, fma(alpha_prev[k], first ? 0.0 : dol[k], x0));
             }
+            part[k] += (a.multi ? ow : 1.0) * rnew * __dmul_rn(rnew, di);
          }
       }
    }
@@ -1817,8 +1762,7 @@ int partition_nodes_by_cost(lgh_ctx *c, const int W, int **out, const std::vecto
       for (int n = 0; n < N; n++) { off[(size_t)n + 1] = off[n] + (*valence)[n]; }
    }
    else { LGH_HIP_CHECK(hipMemcpy(off.data(), c->t_off, off.size() * sizeof(int), hipMemcpyDeviceToHost)); }
-   const char *wenv = getenv("LGH_K2_NODE_WEIGHT"); // fixed part in units of half a contribution; <0: equal counts
-   const long fixed = wenv ? atol(wenv) : 5;
+   const long fixed = c->sw.k2_node_weight; // fixed part in units of half a contribution; <0: equal counts
    std::vector<long> cum((size_t)N + 1, 0);
    for (int n = 0; n < N; n++) { cum[(size_t)n + 1] = cum[n] + (fixed < 0 ? 1 : fixed + 2 * (long)(off[(size_t)n + 1] - off[n])); }
    std::vector<int> ns((size_t)std::max(W, 1) + 1, N);
@@ -2074,7 +2018,7 @@ template <int D, int NEB> static void launch_vcg_kron(lgh_ctx *c, const VcgArgs 
 // LGH_VCG_VARIANT: 0 = (qx,qy)-column K1, otherwise the plane-per-thread K1
 #define VCG_DISPATCH(D_, Q_)                                                       \
    do {                                                                            \
-      if (c->vcg_variant == 0) { launch_vcg_apply<D_, Q_>(c, a); }                 \
+      if (c->sw.vcg_variant == 0) { launch_vcg_apply<D_, Q_>(c, a); }                 \
       else { launch_vcg_plane<D_, Q_>(c, a); }                                     \
    } while (0)
 
@@ -2083,29 +2027,27 @@ bool vcg_available(const lgh_ctx *c) { return vcg_supported(c); }
 int vcg_k1_form(lgh_ctx *c)
 {
    if (!vcg_supported(c)) { return -1; }
-   if (c->kid == 0x346 && c->vcg_variant == 4 && vcg_slab_available(c)) { return 4; }
+   if (c->kid == 0x346 && c->sw.vcg_variant == 4 && vcg_slab_available(c)) { return 4; }
    // Default at Q3Q2 from kSlabMinElements zones per rank: 40.6 vs 48.5 us per launch at 32^3 zones, 316 vs 383 at 64^3
    // (profiles/README.md); smaller meshes do not fill its one workgroup per CU.
-   if (c->kid == 0x346 && c->vcg_variant < 0 && c->NE >= kSlabMinElements && vcg_slab_available(c)) { return 4; }
+   if (c->kid == 0x346 && c->sw.vcg_variant < 0 && c->NE >= kSlabMinElements && vcg_slab_available(c)) { return 4; }
    // default at D1D >= 5 when the mass data is compact on a tensor-product rule: the Kronecker form (vcg_apply_kron;
    // config 5: 438 against 585 us).  At Q3Q2 the plane form stays the default below the slab threshold (32^3 zones:
    // plane 49.9, generic Kronecker 55.3 us - its LDS stages and one-node gathers cost more than the FMAs it saves,
    // profiles/r4_k1_forms.txt); LGH_VCG_VARIANT=5 selects it at any order (tests)
-   if (((c->vcg_variant < 0 && c->D1D >= 5) || c->vcg_variant == 5) && c->M1h && c->w1d)
+   if (((c->sw.vcg_variant < 0 && c->D1D >= 5) || c->sw.vcg_variant == 5) && c->M1h && c->w1d)
    {
       const double *Dq, *Se;
       int dqs = 1;
       if (mass_data(c, &Dq, &dqs, &Se) == LGH_OK && dqs == 0) { return 5; }
    }
-   if (c->vcg_variant == 0) { return 0; }
+   if (c->sw.vcg_variant == 0) { return 0; }
    if ((c->kid == 0x358 || c->kid == 0x36A) && !c->b_h1_sym) { return 0; }
    return 2;
 }
 bool vcg_fused_init_ok(const lgh_ctx *c)
 {
-   const char *env = getenv("LGH_FUSED_INIT"); // A/B switch
-   if (env && env[0] == '0') { return false; }
-   return vcg_supported(c) && c->multi == 0 && c->t_deg <= 8;
+   return c->sw.fused_init && vcg_supported(c) && c->multi == 0 && c->t_deg <= 8;
 }
 
 // B, X: dim*N (byNODES).  X must be zero on entry (dv = 0, laghos_solver.cpp:338, :382).
@@ -2114,9 +2056,7 @@ bool vcg_fused_init_ok(const lgh_ctx *c)
 // iters[c] = GetNumIterations() of component c.
 // Everything a launch of the lockstep kernels needs: work vectors, tables of K2, the argument block (vcg_solve, and the
 // one-launch test hook vcg_test_k1 below).  Launches vcg_set_tol_k on the context stream.
-static const char *trace_path = nullptr; // debug: LGH_VCG_TRACE=<file>
-static bool trace_asked = false;
-static unsigned long long *trace_dev = nullptr;
+static unsigned long long *trace_dev = nullptr; // debug (LGH_VCG_TRACE=<file>): one buffer for the contexts that ask for it
 struct VcgPlan
 {
    VcgArgs a;
@@ -2164,8 +2104,7 @@ static int vcg_build_merged_tables(lgh_ctx *c, VcgAux *x)
 // once (HaloNodeAlias) - which nodes travel, in which order and how they are summed does not depend on their numbers.
 static const MeshOrder *vcg_order_for(const lgh_ctx *c)
 {
-   const char *env = getenv("LGH_ORDER_MULTI"); // A/B: 0 = several ranks keep the caller's numbering in the solve
-   if (c->multi != 0 && env && env[0] == '0') { return nullptr; }
+   if (c->multi != 0 && !c->sw.order_multi) { return nullptr; } // (LGH_ORDER_MULTI=0, A/B: several ranks keep the caller's numbering in the solve)
    return mesh_order(c);
 }
 // Tables and vectors of the solve in the internal order (VcgAux::o_*): the element -> node map (internal zone i, internal
@@ -2308,8 +2247,7 @@ static int vcg_prepare(lgh_ctx *c, double *B, double *X, double rel_tol, VcgPlan
          // node ranges (= workgroups) of vcg_update_p_k: four per CU, and not more than ~1000 nodes (two passes) each -
          // on large meshes long static ranges lose to the hardware's dynamic distribution of many short ones
          // (64^3 zones: 367 vs 424 us; 128^3: H1 CG 2.72 vs 3.04 s).  LGH_K2_GRID=<ranges per CU> for A/B.
-         const char *genv = getenv("LGH_K2_GRID");
-         if (genv && atoi(genv) > 0) { x->grid2 = atoi(genv) * ncu; }
+         if (c->sw.k2_grid > 0) { x->grid2 = c->sw.k2_grid * ncu; }
          else { x->grid2 = (int)std::max<long>(4L * ncu, (((long)c->N + 1023) / 1024 + 7) & ~7L); }
          x->grid2 = std::min<long>(x->grid2, (long)c->vcg_stride - (long)kShards); // (one partial per workgroup in a reduction slot)
          rc = make_ellz(c, &x->ellz, x->o_ell, x->o_ell ? c->t_deg : 0);
@@ -2356,39 +2294,33 @@ static int vcg_prepare(lgh_ctx *c, double *B, double *X, double rel_tol, VcgPlan
          LGH_HIP_CHECK(hipMalloc((void **)&x->rzl, 3 * kLimbWords * sizeof(long long)));
          LGH_HIP_CHECK(hipMemset(x->rzl, 0, 3 * kLimbWords * sizeof(long long)));
       }
+      if (vcg_k1_form(c) == 4 && x->ellz && c->sw.slab_merge) // (LGH_SLAB_MERGE=0, A/B: element-local E-vector for every set, the layout of rounds 3 and 4)
       {
-         const char *menv = getenv("LGH_SLAB_MERGE"); // A/B: 0 = element-local E-vector for every set (the layout of rounds 3 and 4)
-         if (vcg_k1_form(c) == 4 && x->ellz && !(menv && menv[0] == '0'))
-         {
-            rc = vcg_build_merged_tables(c, x);
-            if (rc) { return rc; }
-         }
+         rc = vcg_build_merged_tables(c, x);
+         if (rc) { return rc; }
       }
       LGH_HIP_CHECK(hipStreamSynchronize(nullptr)); // the fills run asynchronously on the null stream
    }
    VcgAux *aux = (VcgAux *)c->vcg_aux;
    const int k1form = vcg_k1_form(c);
-   const char *k2env = getenv("LGH_K2P"); // A/B: 0 = vcg_update_k (one node per thread, x every iteration)
-   const bool k2p = aux->ellz != nullptr && !(k2env && k2env[0] == '0');
+   const bool k2p = aux->ellz != nullptr && c->sw.k2p; // (LGH_K2P=0, A/B: vcg_update_k - one node per thread, x every iteration)
    VcgScalars *ds = (VcgScalars *)c->vcg_s;
    // exact accumulators of (d, A d): slab-form K1 with the bounded-grid K2 (LGH_SLAB_EXACT=0: ticketed fold)
-   long long *limbs = (c->slab_exact && k2p && k1form == 4) ? aux->limbs : nullptr;
+   long long *limbs = (c->sw.slab_exact && k2p && k1form == 4) ? aux->limbs : nullptr;
    // rz_limbs mode: one rank, exact accumulators with the deferred fold (LGH_RZ_LIMBS=0: the ticketed fold of (r, z) in K2)
-   const char *rzenv = getenv("LGH_RZ_LIMBS");
    // (several ranks, round 5: all-pairs partitions, where the words of every rank reach every other in one exchange)
    // (a communicator of size 1 - LGH_FORCE_MULTI - has nobody to exchange with: the words are complete as they are)
-   bool rz_words = limbs && (!multi || ((halo_can_piggyback(c) || c->nranks == 1) && c->t_deg <= 8)) && !(rzenv && rzenv[0] == '0');
+   bool rz_words = limbs && (!multi || ((halo_can_piggyback(c) || c->nranks == 1) && c->t_deg <= 8)) && c->sw.rz_limbs;
    // ... and whether the energy CG can ride on this solve's exchanges (lockstep): a fourth scalar on the halo
    // messages - their LENGTH, which both ends of a message must agree on - so this too is every rank's answer or nobody's
    bool ls_mine = false;
    if (multi && rz_words)
    {
-      const char *e0 = getenv("LGH_HALO_FUSED_PACK");
       HaloPackTables hp0;
       const uint8_t *hm0 = nullptr; const int *sn0 = nullptr; int nsh0 = 0;
       comm_shared_nodes(c, &hm0, &sn0, &nsh0);
       ls_mine = k2p && c->t_deg <= 8 && l2_lockstep_possible(c) && comm_ranks_before(c) >= 0 &&
-                (nsh0 == 0 || (!(e0 && e0[0] == '0') && halo_can_piggyback(c) && comm_pack_tables(c, &hp0)));
+                (nsh0 == 0 || (c->sw.halo_fused_pack && halo_can_piggyback(c) && comm_pack_tables(c, &hp0)));
    }
    if (multi && c->nranks == 1) { aux->ls_all = ls_mine ? 1 : 0; }
    if (multi && c->nranks > 1)
@@ -2396,8 +2328,8 @@ static int vcg_prepare(lgh_ctx *c, double *B, double *X, double rel_tol, VcgPlan
       // Which exchange follows K2 - accumulator words or three doubles - must be the same on every rank, and whether a rank
       // CAN use the words depends on its own kernels (the slab K1 is dispatched by the rank's zone count): decided
       // collectively, once per set of tables (a MIN over the ranks; every rank builds its tables in its first solve)
-      // (what this rank can do depends on switches that may be flipped between solves: the answer is cached with them)
-      const int key = (rz_words ? 1 : 0) | (c->slab_exact ? 2 : 0) | ((c->vcg_variant & 0xff) << 2) | (k1form << 10);
+      // (what this rank can do may change between solves - the form of the mass data, and with it of K1: the answer is cached with it)
+      const int key = (rz_words ? 1 : 0) | (k1form << 10);
       if (aux->rz_words_key != key) { aux->rz_words_all = -1; }
       if (aux->rz_words_all < 0 && !in_solve) { rz_words = false; }
       else if (aux->rz_words_all < 0)
@@ -2417,10 +2349,7 @@ static int vcg_prepare(lgh_ctx *c, double *B, double *X, double rel_tol, VcgPlan
       rz_words = rz_words && aux->rz_words_all == 1;
    }
    long long *rzl = rz_words ? aux->rzl : nullptr;
-   {
-      const char *e0 = getenv("LGH_SLAB_DEFER");
-      if (e0 && e0[0] == '0') { rzl = nullptr; } // (needs the deferred fold of (d, A d) as well)
-   }
+   if (!c->sw.slab_defer) { rzl = nullptr; } // (needs the deferred fold of (d, A d) as well)
    // (a solve resets its scalars and accumulators in its first kernel: a.reset below; the hooks and statistics entry points,
    //  which launch single kernels on state of their own, keep the separate launch)
    if (!in_solve) { hipLaunchKernelGGL(vcg_set_tol_k, dim3(1), dim3(1), 0, c->stream, ds, rel_tol * rel_tol, limbs, rzl); }
@@ -2478,10 +2407,7 @@ static int vcg_prepare(lgh_ctx *c, double *B, double *X, double rel_tol, VcgPlan
    a.yL = c->vcg_vec + 2 * kVC * N;
    a.YE = aux->ye;
    a.ye_stride = (size_t)c->NE * c->ND + kYePad;
-   {
-      const char *w0 = getenv("LGH_SLAB_YE_WIDE"); // test hook: 1 = the per-set 64-bit store base of the slab K1 on a mesh that does not need it
-      a.ye_wide = (a.ye_stride * 8 * kVC >= 0xffffffffull || (w0 && w0[0] == '1')) ? 1 : 0;
-   }
+   a.ye_wide = (a.ye_stride * 8 * kVC >= 0xffffffffull || c->sw.slab_ye_wide) ? 1 : 0; // (LGH_SLAB_YE_WIDE=1, test hook: the per-set 64-bit store base on a mesh that does not need it)
    a.ellz = aux->ellz;
    a.essbits = aux->essbits;
    a.nstart = aux->nstart;
@@ -2506,25 +2432,18 @@ static int vcg_prepare(lgh_ctx *c, double *B, double *X, double rel_tol, VcgPlan
       if (rc) { return rc; }
    }
    a.queue = limbs ? (unsigned *)(limbs + 2 * kLimbWords) : nullptr;
-   {
-      const char *e0 = getenv("LGH_SLAB_DEFER"); // A/B: 0 = the last workgroup of K1 folds the accumulators (ticket), K2 reads the result
-      a.den_limbs = (limbs && !(e0 && e0[0] == '0')) ? (multi ? 2 : 1) : 0; // (several ranks: folded before the exchange, vcg_fold_den)
-      e0 = getenv("LGH_SLAB_STORE_WAIT"); // A/B: 1 = a wavefront waits for the stores of a pass before the next one (it paid at 64^3 while the stores were partial lines: 306 vs 370 us; with whole lines 275 vs 248)
-      a.store_wait = (e0 && e0[0] == '1') ? 1 : 0;
-   }
-   {
-      const char *e0 = getenv("LGH_K2_SKIP");
-      a.k2_skip = (e0 && e0[0] == '0') ? 0 : 1;
-   }
+   // (LGH_SLAB_DEFER=0, A/B: the last workgroup of K1 folds the accumulators (ticket), K2 reads the result)
+   a.den_limbs = (limbs && c->sw.slab_defer) ? (multi ? 2 : 1) : 0; // (several ranks: folded before the exchange, vcg_fold_den)
+   a.k2_skip = c->sw.k2_skip;
    a.s = ds;
    a.stride = c->vcg_stride;
    a.multi = multi ? 1 : 0;
    // debug: LGH_VCG_TRACE=<file> dumps "block start loop_end end (xcc<<32|hw_id)" of the
    // last K1 launch of every solve, in 10 ns ticks
-   if (!trace_asked) { trace_path = getenv("LGH_VCG_TRACE"); trace_asked = true; }
-   if (trace_path && !trace_dev) { (void)hipMalloc((void **)&trace_dev, kTraceRec * 4096 * sizeof(unsigned long long)); (void)hipMemset(trace_dev, 0, kTraceRec * 4096 * sizeof(unsigned long long)); }
-   a.trace = trace_dev;
-   if (trace_dev) { (void)hipMemsetAsync(trace_dev, 0, kTraceRec * 4096 * sizeof(unsigned long long), c->stream); }
+   const bool traced = !c->sw.vcg_trace.empty();
+   if (traced && !trace_dev) { (void)hipMalloc((void **)&trace_dev, kTraceRec * 4096 * sizeof(unsigned long long)); (void)hipMemset(trace_dev, 0, kTraceRec * 4096 * sizeof(unsigned long long)); }
+   a.trace = traced ? trace_dev : nullptr;
+   if (a.trace) { (void)hipMemsetAsync(trace_dev, 0, kTraceRec * 4096 * sizeof(unsigned long long), c->stream); }
    if (multi)
    {
       comm_shared_nodes(c, &a.hmask, &a.sh_node, &a.n_shared);
@@ -2534,10 +2453,8 @@ static int vcg_prepare(lgh_ctx *c, double *B, double *X, double rel_tol, VcgPlan
       // several ranks, bounded-grid K2: the shared-node gather fills the send buffer of the halo exchange itself (and
       // the local (d, A d) with it where the sums ride on the messages), the last workgroup of K2 the one of the
       // (r, z) exchange - two launches less per iteration (A/B: LGH_HALO_FUSED_PACK=0)
-      const char *e0 = getenv("LGH_HALO_FUSED_PACK");
-      const bool want = !(e0 && e0[0] == '0');
       const bool mixed0 = multi && c->t_deg <= 8;
-      if (want && mixed0 && k2p && a.n_shared > 0 && comm_pack_tables(c, &a.hp))
+      if (c->sw.halo_fused_pack && mixed0 && k2p && a.n_shared > 0 && comm_pack_tables(c, &a.hp))
       {
          a.pack_halo = 1;
          a.nx_den = halo_can_piggyback(c) ? (c->e_lockstep ? kVC + 1 : kVC) : 0; // (lockstep energy CG: its (d, M d) rides along, VcgScalars::den_e)
@@ -2566,8 +2483,7 @@ static void vcg_launch_k1(lgh_ctx *c, const VcgPlan &plan, const VcgArgs &a)
 {
    VcgAux *aux = plan.aux;
    const int k1form = plan.k1form;
-   const char *knenv = getenv("LGH_KRON_NEB");
-   const bool kron_small = !(knenv && knenv[0] == '0');
+   const bool kron_small = c->sw.kron_neb != 0;
    if (k1form == 5)
    {
       switch (c->D1D)
@@ -2592,12 +2508,12 @@ static void vcg_launch_k1(lgh_ctx *c, const VcgPlan &plan, const VcgArgs &a)
          else { VCG_DISPATCH(4, 6); }
          break;
       case 0x358: // LGH_VCG_VARIANT=1: the two-lanes-per-plane split at Q1D = 8 as well (A/B, tests)
-         if (c->vcg_variant == 0 || !c->b_h1_sym) { launch_vcg_apply<5, 8>(c, a); } // (the plane form uses half a table)
-         else if (c->vcg_variant == 1) { launch_vcg_plane_ho<5, 8, 2, 5>(c, a); }
+         if (c->sw.vcg_variant == 0 || !c->b_h1_sym) { launch_vcg_apply<5, 8>(c, a); } // (the plane form uses half a table)
+         else if (c->sw.vcg_variant == 1) { launch_vcg_plane_ho<5, 8, 2, 5>(c, a); }
          else { launch_vcg_plane_ho<5, 8, 1, 5>(c, a); }
          break;
       case 0x36A:
-         if (c->vcg_variant == 0 || !c->b_h1_sym) { launch_vcg_apply<6, 10>(c, a); }
+         if (c->sw.vcg_variant == 0 || !c->b_h1_sym) { launch_vcg_apply<6, 10>(c, a); }
          else { launch_vcg_plane_ho<6, 10, 2, 4>(c, a); }
          break;
    }
@@ -2608,17 +2524,10 @@ static void vcg_launch_k1(lgh_ctx *c, const VcgPlan &plan, const VcgArgs &a)
 static void vcg_launch_k2p(lgh_ctx *c, const VcgPlan &plan, const VcgArgs &a, const int it)
 {
    kt_begin(c, LGH_KERNEL_CG_UPDATE_H1);
-   const char *uenv = getenv("LGH_K2_U"); // A/B: nodes per thread and pass (2: 182 VGPRs, one workgroup per CU resident)
-   const int u2 = (uenv && uenv[0] == '2') ? 1 : 0;
-   // LGH_K2_OCC (A/B): 4 = the register budget of rounds 2-4 for both launches, 6 = at most 80 registers for both (the launch
-   // that updates x then spills 7), default: 80 for the launch without x, the old budget for the one with it
-   const char *oenv = getenv("LGH_K2_OCC"); // (per launch, like LGH_K2_U: the switch tests flip it inside one process)
-   const int occ = (oenv && oenv[0] == '4') ? 0 : (oenv && oenv[0] == '6') ? 2 : 1;
-   const int occ3 = (it & 1) ? (occ >= 1) : (occ == 2);
-#define LGH_K2P_LAUNCH(XU_, U_, MINW_) hipLaunchKernelGGL((vcg_update_p_k<XU_, U_, MINW_>), dim3(plan.aux->grid2), dim3(512), 0, c->stream, a)
-   if (it & 1) { if (u2) { LGH_K2P_LAUNCH(false, 2, 2); } else if (occ3) { LGH_K2P_LAUNCH(false, 1, 6); } else { LGH_K2P_LAUNCH(false, 1, 4); } }
-   else { if (u2) { LGH_K2P_LAUNCH(true, 2, 2); } else if (occ3) { LGH_K2P_LAUNCH(true, 1, 6); } else { LGH_K2P_LAUNCH(true, 1, 4); } }
-#undef LGH_K2P_LAUNCH
+   // the launch without x: at most 80 registers (six wavefronts per SIMD); the one that updates x would spill there and
+   // keeps the budget of rounds 2-4 (profiles/r5_k2_occupancy_grid.txt)
+   if (it & 1) { hipLaunchKernelGGL((vcg_update_p_k<false, 6>), dim3(plan.aux->grid2), dim3(512), 0, c->stream, a); }
+   else { hipLaunchKernelGGL((vcg_update_p_k<true, 4>), dim3(plan.aux->grid2), dim3(512), 0, c->stream, a); }
    kt_end(c, LGH_KERNEL_CG_UPDATE_H1);
 }
 
@@ -2673,26 +2582,6 @@ int vcg_solve(lgh_ctx *c, double *B, double *X, double rel_tol, int max_iter, in
    const int ls_limit = ls ? std::min(l2_lockstep_limit(c), max_iter) : 0;
    const int ls_before = ls ? comm_ranks_before(c) : 0;
    auto ls_words = [&](const int set_it) { return LockstepWords{a.rzl + (set_it % 3) * kLimbWords, a.rzl_peers, a.n_rz_peers, ls_before}; };
-   // ... with its kernels on the second stream (c->ls_side): `side(f)` enqueues f there; the velocity iteration and the energy
-   // iteration meet at four events - the apply after the word exchange of the iteration before (whose words it reads) and before
-   // the halo messages are packed (its (d, M d) rides on them), the update after the halo sums and before the word exchange
-   // (which carries its (r, r)).  In between the apply runs beside K1 and the update beside K2.
-   const bool ls_side = ls && c->ls_side != 0 && c->stream2 != nullptr;
-   auto side = [&](auto &&f) -> int {
-      if (!ls_side) { return f(); }
-      std::swap(c->stream, c->stream2);
-      const int r = f();
-      std::swap(c->stream, c->stream2);
-      return r;
-   };
-   // (record on `from`, wait on the other stream)
-   auto hand_over = [&](hipEvent_t ev, const bool from_side) -> int {
-      if (!ls_side) { return LGH_OK; }
-      LGH_HIP_CHECK(hipEventRecord(ev, from_side ? c->stream2 : c->stream));
-      LGH_HIP_CHECK(hipStreamWaitEvent(from_side ? c->stream : c->stream2, ev, 0));
-      return LGH_OK;
-   };
-   if (ls_side) { rc = hand_over(c->ev_fork, false); if (rc) { return rc; } } // (the energy solve's set-up and this solve's are on the main stream)
    // first chunk = iteration count of the previous velocity solve (see cg_solve)
    int chunk = c->vcg_last > 0 ? c->vcg_last : 8;
    bool first_look = true;
@@ -2746,9 +2635,7 @@ int vcg_solve(lgh_ctx *c, double *B, double *X, double rel_tol, int max_iter, in
          const bool ls_it = ls && it <= ls_limit;
          if (ls_it)
          {
-            rc = side([&] { return l2_lockstep_apply(c, it, ls_words(it - 1), &ds->den_e); });
-            if (rc) { return rc; }
-            rc = hand_over(c->ls_ev[1][it & 3], true); // (the messages are packed after this)
+            rc = l2_lockstep_apply(c, it, ls_words(it - 1), &ds->den_e); // (the messages are packed after this)
             if (rc) { return rc; }
          }
          a.partials = c->vcg_partials;
@@ -2797,16 +2684,13 @@ int vcg_solve(lgh_ctx *c, double *B, double *X, double rel_tol, int max_iter, in
                   if (rc) { return rc; }
                }
             }
-            if (ls_it) { rc = hand_over(c->ls_ev[2][it & 3], false); if (rc) { return rc; } } // (the energy update reads the summed (d, M d))
             // (the bounded-grid K2 knows the shared nodes and the owner weights from its flag bytes)
             if (mixed && k2p) { launch_k2p(); }
             else if (mixed) { hipLaunchKernelGGL((vcg_update_k<true, 8>), dim3(nb), dim3(256), 0, c->stream, a); }
             else { hipLaunchKernelGGL((vcg_update_k<false, 0>), dim3(nb), dim3(256), 0, c->stream, a); }
             if (ls_it)
             {
-               rc = side([&] { return l2_lockstep_update(c, it, &ds->den_e, a.rzl + (it % 3) * kLimbWords); });
-               if (rc) { return rc; }
-               rc = hand_over(c->ls_ev[3][it & 3], true); // (the word exchange carries its (r, r))
+               rc = l2_lockstep_update(c, it, &ds->den_e, a.rzl + (it % 3) * kLimbWords); // (reads the summed (d, M d); the word exchange carries its (r, r))
                if (rc) { return rc; }
             }
             if (multi && a.rzl)
@@ -2815,12 +2699,11 @@ int vcg_solve(lgh_ctx *c, double *B, double *X, double rel_tol, int max_iter, in
                // no pack, no combine kernel; the next K1 (or vcg_rz_finish_k) adds own and peers' words before it folds
                rc = exchange_words(c, a.rzl + (it % 3) * kLimbWords, kLimbWords);
                if (rc) { return rc; }
-               if (ls_it) { rc = hand_over(c->ls_ev[0][it & 3], false); if (rc) { return rc; } } // (the next apply, or the fold, reads these words)
                if (ls_it && (it == ls_limit || it == upto))
                {
                   // the energy CG's last interleaved iteration of this chunk: its outcome is committed now, while the peers'
                   // words of THIS exchange are still in the buffer (the next apply, if there is one, finds the same sum)
-                  rc = side([&] { return l2_lockstep_fold(c, it, ls_words(it)); });
+                  rc = l2_lockstep_fold(c, it, ls_words(it));
                   if (rc) { return rc; }
                }
             }
@@ -2833,7 +2716,6 @@ int vcg_solve(lgh_ctx *c, double *B, double *X, double rel_tol, int max_iter, in
          LGH_HIP_CHECK(hipGetLastError());
       }
    }
-   if (ls_side) { rc = hand_over(c->ev_join, true); if (rc) { return rc; } } // (lgh_solve_energy_end continues on the main stream)
    if (aux->ord)
    {
       // the solution, in the caller's numbering, into the caller's vector (with the pending update of vcg_xfix_k)
@@ -2846,11 +2728,11 @@ int vcg_solve(lgh_ctx *c, double *B, double *X, double rel_tol, int max_iter, in
       hipLaunchKernelGGL(vcg_xfix_k, dim3(nb), dim3(256), 0, c->stream, a);
       LGH_HIP_CHECK(hipGetLastError());
    }
-   if (trace_dev)
+   if (a.trace)
    {
       std::vector<unsigned long long> h(kTraceRec * 4096);
       (void)hipMemcpy(h.data(), trace_dev, h.size() * 8, hipMemcpyDeviceToHost);
-      FILE *f = fopen(trace_path, "w");
+      FILE *f = fopen(c->sw.vcg_trace.c_str(), "w");
       if (f)
       {
          for (int i = 0; i < 4096; i++)

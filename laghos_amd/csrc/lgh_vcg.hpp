@@ -233,7 +233,6 @@ struct VcgArgs
    const uint8_t *essbits;    // bit k: node essential for component k
    const int *nstart;         // node range of block w: [nstart[w], nstart[w+1]), balanced by cost
    int k2_skip;               // vcg_update_p_k: skip ELL slots no node of the wavefront uses (LGH_K2_SKIP=0: fetch all 8)
-   int store_wait;        // slab-form K1 (A/B, LGH_SLAB_STORE_WAIT): every wavefront waits for the stores of a pass before it starts the next one
    int ye_wide;           // slab-form K1: the three planes of Y_E exceed 4 GB - per-set 64-bit store base instead of 32-bit offsets from Y_E
    // slab-form K1, merged E-vector layout (round 5; LGH_SLAB_MERGE=0: nullptr): one word per set of five zones - bits 0..30 the
    // set's slice of a Y_E plane in units of 64 doubles, bit 31 set when the five zones are x-neighbours ("x-chain": zone i + 1's

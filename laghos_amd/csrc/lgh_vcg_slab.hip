@@ -199,14 +199,14 @@ static bool slab_swaps_probe(lgh_ctx *c)
 // where the general form has 1 020 + 144, no quadrature-point values at all, and (d, A d) = sum over the element's
 // nodes of d y.  Same operator in exact arithmetic; rounding differs (tests: tests/test_gpu_k1.py, 2e-12 like every
 // compact-data case).  What a pass then costs is its memory instructions: the kernel becomes bandwidth-bound.
-template <bool SYM, int WPS, int TRACE, bool WIDE, bool EXACT, bool DYN, bool RANK1, bool KRON = false>
-__global__ void __launch_bounds__(256 * WPS, WPS)
+template <bool SYM, int TRACE, bool WIDE, bool EXACT, bool DYN, bool RANK1, bool KRON = false>
+__global__ void __launch_bounds__(256, 1)
 vcg_apply_slab346(const VcgArgs a, const int nset)
 {
    static_assert(!KRON || RANK1, "the Kronecker form needs compact mass data");
    constexpr int D = 4, Q = 6, NQ = Q * Q * Q, ND = D * D * D, QD = Q * D, HB = SYM ? (QD + 1) / 2 : QD;
    constexpr int ES = 5;                     // elements of a set: 15 items on the 16 lanes of a lane group
-   constexpr int NW = 4 * WPS;               // wavefronts of the workgroup (one workgroup per CU), each on its own sets: WPS per SIMD
+   constexpr int NW = 4;                     // wavefronts of the workgroup (one workgroup per CU, one wavefront per SIMD), each on its own sets
    constexpr int NDMA = (ES * NQ * 8 + 1023) / 1024; // 1 KB LDS-DMA pieces per set of quadrature data (9)
    constexpr int SBUF = NDMA * 128;          // doubles per LDS buffer (the last piece runs past the set's 1080 values)
    // per wave two buffers: the set being contracted, the set in flight.  The loop body takes them as __restrict__
@@ -610,16 +610,13 @@ vcg_apply_slab346(const VcgArgs a, const int nset)
       __builtin_amdgcn_sched_barrier(0);
       LGH_SLAB_STAMP(2); // transpose
       // forward z, quadrature data, (d, A d), backward z; the quadrature data of pair i + 1 is read while pair i is contracted
-      // (one wavefront per SIMD: the data of pair i + 1 is read while pair i is contracted; with two the other wavefront
-      // covers the LDS latency and the 12 registers of the look-ahead are worth more)
-      constexpr bool AHEAD = (WPS == 1);
       double dcur[Q], dnxt[Q];
 #pragma unroll
       for (int qz = 0; qz < Q; qz++) { dcur[qz] = sDp[36 * qz]; }
 #pragma unroll
       for (int i = 0; i < 9; i++)
       {
-         if (AHEAD && i < 8)
+         if (i < 8)
          {
 #pragma unroll
             for (int qz = 0; qz < Q; qz++) { dnxt[qz] = sDp[i + 1 + 36 * qz]; }
@@ -642,16 +639,8 @@ vcg_apply_slab346(const VcgArgs a, const int nset)
             for (int qz = 0; qz < Q; qz++) { u = fma(Bs(qz + Q * dz), cz[qz], u); }
             w[9 * dz + i] = u;
          }
-         if (AHEAD)
-         {
 #pragma unroll
-            for (int qz = 0; qz < Q; qz++) { dcur[qz] = dnxt[qz]; }
-         }
-         else if (i < 8)
-         {
-#pragma unroll
-            for (int qz = 0; qz < Q; qz++) { dcur[qz] = sDp[i + 1 + 36 * qz]; }
-         }
+         for (int qz = 0; qz < Q; qz++) { dcur[qz] = dnxt[qz]; }
          if (i == 2) { load_gather_part(2, true); }
          if (i == 5) { load_gather_part(3, true); }
          asm volatile("" : "+v"(dset)); // the partial sum exists HERE: left alone, the compiler keeps all 54 factor pairs alive (216 registers) and forms the sum after the loop body
@@ -801,7 +790,6 @@ vcg_apply_slab346(const VcgArgs a, const int nset)
          }
          tw_cur = tw_nxt;
       }
-      if (a.store_wait) { __builtin_amdgcn_s_waitcnt(0x0F70); }
       LGH_SLAB_STAMP(7); // stores
       // (a select would let the compiler sink all 54 products of dset behind the branch: 216 live registers)
       if (EXACT) { acc_bad = acc_bad || !exact_add(acc, dset * (actf * se), accE); }
@@ -971,7 +959,7 @@ bool vcg_slab_available(lgh_ctx *c)
    return c->dim == 3 && c->kid == 0x346 && (size_t)c->N * 8 * kVC < 0xffffffffull && ((size_t)c->NE * c->ND + kYePad) * 8 * (kVC - 1) + 65536 < 0xffffffffull && slab_swaps_ok(c); // (per-lane store offsets: the last component's plane + a set)
 }
 
-template <bool SYM, int WPS, int TR, bool WIDE, bool EX, bool DYN>
+template <bool SYM, int TR, bool WIDE, bool EX, bool DYN>
 static void slab_launch(lgh_ctx *c, const VcgArgs &a, const int grid, const int nset)
 {
    if (a.dqs == 0)
@@ -979,11 +967,11 @@ static void slab_launch(lgh_ctx *c, const VcgArgs &a, const int grid, const int 
       // compact mass data; with a tensor-product rule as well (a.M1): the Kronecker form
       if constexpr (SYM)
       {
-         if (a.M1) { hipLaunchKernelGGL((vcg_apply_slab346<SYM, WPS, TR, WIDE, EX, DYN, true, true>), dim3(grid), dim3(256 * WPS), 0, c->stream, a, nset); return; }
+         if (a.M1) { hipLaunchKernelGGL((vcg_apply_slab346<SYM, TR, WIDE, EX, DYN, true, true>), dim3(grid), dim3(256), 0, c->stream, a, nset); return; }
       }
-      hipLaunchKernelGGL((vcg_apply_slab346<SYM, WPS, TR, WIDE, EX, DYN, true>), dim3(grid), dim3(256 * WPS), 0, c->stream, a, nset);
+      hipLaunchKernelGGL((vcg_apply_slab346<SYM, TR, WIDE, EX, DYN, true>), dim3(grid), dim3(256), 0, c->stream, a, nset);
    }
-   else { hipLaunchKernelGGL((vcg_apply_slab346<SYM, WPS, TR, WIDE, EX, DYN, false>), dim3(grid), dim3(256 * WPS), 0, c->stream, a, nset); }
+   else { hipLaunchKernelGGL((vcg_apply_slab346<SYM, TR, WIDE, EX, DYN, false>), dim3(grid), dim3(256), 0, c->stream, a, nset); }
 }
 
 void launch_vcg_slab(lgh_ctx *c, const VcgArgs &a)
@@ -994,26 +982,24 @@ void launch_vcg_slab(lgh_ctx *c, const VcgArgs &a)
       c->ncu = (hipGetDeviceProperties(&prop, c->device) == hipSuccess) ? prop.multiProcessorCount : 256;
    }
    const int ncu = c->ncu;
-   const int wps = c->slab_wps; // wavefronts per SIMD (workgroup of 256 or 512 threads, one per CU)
    const int nset = ceil_div(c->NE, 5);
-   const int grid = std::min(ceil_div(nset, 4 * wps), ncu); // one workgroup of 4 wps wavefronts per CU
-   const bool wide = c->slab_wide && a.map_xrows != 0;
+   const int grid = std::min(ceil_div(nset, 4), ncu); // one workgroup of four wavefronts per CU
+   const bool wide = c->sw.slab_wide && a.map_xrows != 0;
    const bool exact = a.limbs != nullptr;
    // Sets drawn from the workgroup's queue even out the wavefronts of a workgroup, which pays while a wavefront has few
    // passes (32^3: 6.4 each, 30.6 against 31.6 us); with many, the static interleaved schedule - the whole grid sweeps
    // through the mesh together - is ahead (64^3: 51 passes each, 210.8 against 222 us, profiles/r4_k1_forms.txt).
-   const bool dyn = exact && (c->slab_dyn < 0 ? nset <= 16 * grid * 4 * wps : c->slab_dyn != 0);
-#define LGH_SLAB_LAUNCH(SYM_, WPS_, TR_, WIDE_, EX_, DYN_) slab_launch<SYM_, WPS_, TR_, WIDE_, EX_, DYN_>(c, a, grid, nset)
-#define LGH_SLAB_LAUNCH2(SYM_, WPS_, TR_) do { if (wide && dyn) { LGH_SLAB_LAUNCH(SYM_, WPS_, TR_, true, true, true); } else if (wide && exact) { LGH_SLAB_LAUNCH(SYM_, WPS_, TR_, true, true, false); } \
-                                               else if (wide) { LGH_SLAB_LAUNCH(SYM_, WPS_, TR_, true, false, false); } \
-                                               else if (exact) { LGH_SLAB_LAUNCH(SYM_, WPS_, TR_, false, true, false); } else { LGH_SLAB_LAUNCH(SYM_, WPS_, TR_, false, false, false); } } while (0)
-   static const bool trace_full = getenv("LGH_VCG_TRACE_PHASES") != nullptr; // per-phase cycle counters as well (more registers: not the shipped schedule)
+   const bool dyn = exact && (c->sw.slab_dyn < 0 ? nset <= 16 * grid * 4 : c->sw.slab_dyn != 0);
+#define LGH_SLAB_LAUNCH(SYM_, TR_, WIDE_, EX_, DYN_) slab_launch<SYM_, TR_, WIDE_, EX_, DYN_>(c, a, grid, nset)
+#define LGH_SLAB_LAUNCH2(SYM_, TR_) do { if (wide && dyn) { LGH_SLAB_LAUNCH(SYM_, TR_, true, true, true); } else if (wide && exact) { LGH_SLAB_LAUNCH(SYM_, TR_, true, true, false); } \
+                                         else if (wide) { LGH_SLAB_LAUNCH(SYM_, TR_, true, false, false); } \
+                                         else if (exact) { LGH_SLAB_LAUNCH(SYM_, TR_, false, true, false); } else { LGH_SLAB_LAUNCH(SYM_, TR_, false, false, false); } } while (0)
    // (the traced instantiations exist for the mirror-symmetric table only: a context without the symmetry runs untraced)
    const bool tr = a.trace != nullptr && c->b_h1_sym;
-   if (tr && trace_full) { if (wps == 2) { LGH_SLAB_LAUNCH2(true, 2, 2); } else { LGH_SLAB_LAUNCH2(true, 1, 2); } }
-   else if (tr) { if (wps == 2) { LGH_SLAB_LAUNCH2(true, 2, 1); } else { LGH_SLAB_LAUNCH2(true, 1, 1); } } // debug (LGH_VCG_TRACE): wall-clock stamps per workgroup
-   else if (wps == 2) { if (c->b_h1_sym) { LGH_SLAB_LAUNCH2(true, 2, 0); } else { LGH_SLAB_LAUNCH2(false, 2, 0); } }
-   else { if (c->b_h1_sym) { LGH_SLAB_LAUNCH2(true, 1, 0); } else { LGH_SLAB_LAUNCH2(false, 1, 0); } }
+   if (tr && c->sw.vcg_trace_phases) { LGH_SLAB_LAUNCH2(true, 2); } // per-phase cycle counters as well (more registers: not the shipped schedule)
+   else if (tr) { LGH_SLAB_LAUNCH2(true, 1); } // debug (LGH_VCG_TRACE): wall-clock stamps per workgroup
+   else if (c->b_h1_sym) { LGH_SLAB_LAUNCH2(true, 0); }
+   else { LGH_SLAB_LAUNCH2(false, 0); }
 #undef LGH_SLAB_LAUNCH2
 #undef LGH_SLAB_LAUNCH
 }

@@ -22,7 +22,6 @@ K2_CASES = [
     ("Q3Q2-128-slab-exact-rz", "box01_hex", 1, 3, 2, {"LGH_VCG_VARIANT": "4"}, True),
     ("Q3Q2-128-slab-ticketed-rz", "box01_hex", 1, 3, 2, {"LGH_VCG_VARIANT": "4", "LGH_RZ_LIMBS": "0"}, True),
     ("Q3Q2-512-slab-exact-rz", "cube01_hex", 2, 3, 2, {"LGH_VCG_VARIANT": "4"}, True),
-    ("Q3Q2-64-two-nodes-per-thread", "cube01_hex", 1, 3, 2, {"LGH_K2_U": "2"}, True),
     ("Q3Q2-64-all-slots", "cube01_hex", 1, 3, 2, {"LGH_K2_SKIP": "0"}, True),
     ("Q3Q2-64-round-1-kernel", "cube01_hex", 1, 3, 2, {"LGH_K2P": "0"}, False),
     ("Q2Q1-64-default", "cube01_hex", 1, 2, 1, {}, True),
@@ -91,7 +90,7 @@ def _oracle_iteration(prob, o, it, deferred_x):
 def test_k2_one_launch_vs_oracle_cg(case, it, monkeypatch):
     from oracle.fem import Problem
     _, mesh, rs, ok, ot, env, bounded = case
-    for k in ("LGH_VCG_VARIANT", "LGH_RZ_LIMBS", "LGH_K2_U", "LGH_K2_SKIP", "LGH_K2P", "LGH_SLAB_MERGE"):
+    for k in ("LGH_VCG_VARIANT", "LGH_RZ_LIMBS", "LGH_K2_SKIP", "LGH_K2P", "LGH_SLAB_MERGE"):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -128,7 +127,7 @@ def test_k2_at_bench_size_vs_oracle_cg(it, monkeypatch):
     """Config 2's mesh (32^3 zones, Q3Q2) as dispatched by default: slab K1 (merged E-vector layout), exact (r, z)
     accumulators, bounded-grid K2 - the launch the bench's roofline is quoted on - against the oracle's CG iteration."""
     from oracle.fem import Problem
-    for k in ("LGH_VCG_VARIANT", "LGH_RZ_LIMBS", "LGH_K2_U", "LGH_K2_SKIP", "LGH_K2P", "LGH_SLAB_MERGE"):
+    for k in ("LGH_VCG_VARIANT", "LGH_RZ_LIMBS", "LGH_K2_SKIP", "LGH_K2P", "LGH_SLAB_MERGE"):
         monkeypatch.delenv(k, raising=False)
     prob = Problem(mesh="cube01_hex", rs=4, order_v=3, order_e=2, problem=1)
     _run_k2(prob, it, True, "slab")
@@ -145,7 +144,7 @@ def test_k2_rz_out_of_the_window(case, monkeypatch):
     as a wrong number.  The next launch with the true rz returns the bits of the first: the flag does not outlive the solve."""
     from oracle.fem import Problem
     _, mesh, rs = case
-    for k in ("LGH_VCG_VARIANT", "LGH_RZ_LIMBS", "LGH_K2_U", "LGH_K2_SKIP", "LGH_K2P", "LGH_SLAB_MERGE"):
+    for k in ("LGH_VCG_VARIANT", "LGH_RZ_LIMBS", "LGH_K2_SKIP", "LGH_K2P", "LGH_SLAB_MERGE"):
         monkeypatch.delenv(k, raising=False)
     monkeypatch.setenv("LGH_VCG_VARIANT", "4")
     prob = Problem(mesh=mesh, rs=rs, order_v=3, order_e=2, problem=1)

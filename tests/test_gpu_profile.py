@@ -130,16 +130,26 @@ def test_rows_add_up_to_the_diagnostics(cases, zones_id, order):
 @pytest.mark.parametrize("zones_id,order", BIG)
 def test_same_bits_every_time_and_on_both_atomic_paths(cases, zones_id, order, monkeypatch):
     """repeated calls, and LGH_PROFILE_FOLD = 0 (every lane sends its own atomics), 1, the default 8 and 100000 (every wavefront
-    folds its lanes row by row, whatever the range): the same bytes"""
+    folds its lanes row by row, whatever the range): the same bytes.  A context's switches are those of the environment at its
+    creation, so every other value gets a context of its own on the same data."""
+    from test_gpu_diagnostics import Case
     c = cases(zones_id, order)
-    for spec in pc.specs(c.dim)[:1] + pc.specs(c.dim)[-2:]:
-        first = run(c, spec, raw=True)
-        assert np.array_equal(first, run(c, spec, raw=True))
-        for fold in ("0", "1", "100000"):
-            monkeypatch.setenv("LGH_PROFILE_FOLD", fold)
-            assert np.array_equal(first, run(c, spec, raw=True)), (spec[0], fold)
-        monkeypatch.delenv("LGH_PROFILE_FOLD")
-        assert np.array_equal(first, run(c, spec, raw=True))
+    specs = pc.specs(c.dim)[:1] + pc.specs(c.dim)[-2:]
+    first = [run(c, spec, raw=True) for spec in specs]
+    for spec, want in zip(specs, first):
+        assert np.array_equal(want, run(c, spec, raw=True))
+    for fold in ("0", "1", "100000"):
+        monkeypatch.setenv("LGH_PROFILE_FOLD", fold)
+        other = Case(pc.ZONES[zones_id], order[0], order[1]).setup()
+        try:
+            assert np.array_equal(other.S, c.S)
+            for spec, want in zip(specs, first):
+                assert np.array_equal(want, run(other, spec, raw=True)), (spec[0], fold)
+        finally:
+            other.close()
+    monkeypatch.delenv("LGH_PROFILE_FOLD")
+    for spec, want in zip(specs, first):
+        assert np.array_equal(want, run(c, spec, raw=True))
 
 
 @pytest.mark.parametrize("renumber", ["random", "mfem"])

@@ -39,7 +39,7 @@ pytestmark = pytest.mark.gpu
 
 TOL = 1e-13
 SWITCHES = ("LGH_VCG_VARIANT", "LGH_MASS_RANK1", "LGH_MASS_KRON", "LGH_SLAB_MERGE", "LGH_SLAB_DYN", "LGH_KRON_NEB", "LGH_RZ_LIMBS",
-            "LGH_K2_U", "LGH_K2_SKIP", "LGH_K2P", "LGH_K2_GRID", "LGH_Q_FORM", "LGH_Q_OCC4", "LGH_Q_PPT", "LGH_JAC0_COMPACT",
+            "LGH_K2_SKIP", "LGH_K2P", "LGH_K2_GRID", "LGH_Q_FORM", "LGH_Q_OCC4", "LGH_Q_PPT", "LGH_JAC0_COMPACT",
             "LGH_FUSED_FTV", "LGH_FUSED_F1", "LGH_L2_PLANE", "LGH_L2_FUSED", "LGH_L2_NEB")
 
 
@@ -288,7 +288,6 @@ K2_Q3Q2 = [
     ("slab-merged-exact-rz", {"LGH_VCG_VARIANT": "4"}, True, "slab"),
     ("slab-element-local-exact-rz", {"LGH_VCG_VARIANT": "4", "LGH_SLAB_MERGE": "0"}, True, "slab"),
     ("slab-ticketed-rz", {"LGH_VCG_VARIANT": "4", "LGH_RZ_LIMBS": "0"}, True, "slab"),
-    ("two-nodes-per-thread", {"LGH_K2_U": "2"}, True, None),
     ("round-1-kernel", {"LGH_K2P": "0"}, False, None),
     ("one-range-per-cu", {"LGH_K2_GRID": "1"}, True, None),
     ("64-ranges-per-cu", {"LGH_K2_GRID": "64"}, True, None),
