@@ -80,7 +80,10 @@ void *lgh_stream(lgh_ctx *ctx);
 /* ---- QuadratureData (laghos_assembly.hpp:31-62); device arrays owned by ctx.
  *   stressJinvT[(e*NQ+q) + NE*NQ*(gd + dim*vd)]     (laghos_solver.cpp:1160-1167)
  *   Jac0inv[i + dim*(j + dim*(e*NQ+q))]              (laghos_solver.cpp:1195)
- *   rho0DetJ0w[e*NQ+q];  mass_D = w*detJ0*rho0(x_q)  (laghos_assembly.cpp:92-95)   */
+ *   rho0DetJ0w[e*NQ+q];  mass_D = w*detJ0*rho0(x_q)  (laghos_assembly.cpp:92-95)
+ * Writes: lgh_mass_D() and lgh_qdata_stressJinvT() honour them (see below). Jac0inv is a result: in 2D/3D the update reads its own
+ * plane-major and per-zone copies (1D reads the array itself); rho0DetJ0w IS read by the update, the energies and the diagnostics,
+ * but the mass data and the diagonal are not derived from it again. */
 double *lgh_qdata_stressJinvT(lgh_ctx *ctx);
 double *lgh_qdata_Jac0inv(lgh_ctx *ctx);
 double *lgh_qdata_rho0DetJ0w(lgh_ctx *ctx);
