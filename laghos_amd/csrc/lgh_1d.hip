@@ -807,8 +807,8 @@ int create_1d(const lgh_config *cfg, lgh_ctx *c)
    LGH_TRY(alloc_zero(&c->tickets, 4 * (size_t)kTicketSlot));
    LGH_TRY(alloc_zero(&c->cgs, 1));
    LGH_TRY(alloc_zero(&c->scal, 16));
-   LGH_HIP_CHECK(hipHostMalloc((void **)&c->host_pinned, 96 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-   memset(c->host_pinned, 0, 96 * sizeof(double));
+   LGH_HIP_CHECK(hipHostMalloc((void **)&c->host_pinned, kPinDoubles * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+   memset(c->host_pinned, 0, kPinDoubles * sizeof(double));
    LGH_HIP_CHECK(hipHostGetDevicePointer((void **)&c->host_pinned_dev, c->host_pinned, 0));
    LGH_HIP_CHECK(hipEventCreate(&c->timers.ev[0]));
    LGH_HIP_CHECK(hipEventCreate(&c->timers.ev[1]));
@@ -847,11 +847,11 @@ int setup_1d(lgh_ctx *c, const double *x0, const double *rho0_l2, const double *
       return LGH_OK;
    });
    if (rc) { return rc; }
-   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned + kPinResult, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
    const int rc2 = mass_changed_1d(c);
    if (rc2) { return rc2; }
    LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
-   *volume = c->host_pinned[0];
+   *volume = c->host_pinned[kPinResult];
    c->stress_current = 0;
    return LGH_OK;
 }
@@ -1048,9 +1048,9 @@ int energy_1d(lgh_ctx *c, int which, const double *vec, double *result)
       return LGH_OK;
    });
    if (rc) { return rc; }
-   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned + kPinResult, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
    LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
-   *result = (which == 0) ? c->host_pinned[0] : 0.5 * c->host_pinned[0];
+   *result = (which == 0) ? c->host_pinned[kPinResult] : 0.5 * c->host_pinned[kPinResult];
    return LGH_OK;
 }
 
@@ -1084,9 +1084,9 @@ int sedov_density_error_1d(lgh_ctx *c, const double *x_h1, const double *rho_l2,
    hipLaunchKernelGGL(sedov_err_1d_k, dim3(zone_grid(c)), dim3(256), 0, c->stream, c->NE, n1d, (const double *)rx,
                       (const double *)rh, (const double *)wd, c->partials, c->tickets, c->scal);
    LGH_HIP_CHECK(hipGetLastError());
-   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned + kPinResult, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
    LGH_HIP_CHECK(hipStreamSynchronize(c->stream)); // (the scratch is released on return)
-   *err2 = c->host_pinned[0];
+   *err2 = c->host_pinned[kPinResult];
    return LGH_OK;
 }
 

@@ -640,8 +640,8 @@ static int create_impl(const lgh_config *cfg, lgh_ctx *c, const int kid)
    LGH_TRY(dev_alloc_zero(&c->tickets, 4 * (size_t)kTicketSlot));
    LGH_TRY(dev_alloc_zero(&c->cgs, 1));
    LGH_TRY(dev_alloc_zero(&c->scal, 16));
-   LGH_HIP_CHECK(hipHostMalloc((void **)&c->host_pinned, 96 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-   memset(c->host_pinned, 0, 96 * sizeof(double));
+   LGH_HIP_CHECK(hipHostMalloc((void **)&c->host_pinned, kPinDoubles * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+   memset(c->host_pinned, 0, kPinDoubles * sizeof(double));
    LGH_HIP_CHECK(hipHostGetDevicePointer((void **)&c->host_pinned_dev, c->host_pinned, 0)); // (the one-thread kernels in front of a host look write there)
    LGH_HIP_CHECK(hipEventCreate(&c->timers.ev[0]));
    LGH_HIP_CHECK(hipEventCreate(&c->timers.ev[1]));
@@ -828,14 +828,14 @@ int lgh_get_dt_est(lgh_ctx *c, double *v)
 {
    LGH_CHECK_ARG(c && v);
    const unsigned long long token = ++c->look_token;
-   hipLaunchKernelGGL(dt_est_fold_k, dim3(1), dim3(256), 0, c->stream, c->dt_est_dev, c->dev_flags + 4, c->host_pinned_dev + 8, token);
+   hipLaunchKernelGGL(dt_est_fold_k, dim3(1), dim3(256), 0, c->stream, c->dt_est_dev, c->dev_flags + 4, c->host_pinned_dev + kPinDt, token);
    LGH_HIP_CHECK(hipGetLastError());
    {
-      const int rc = host_wait_token(c, (volatile unsigned long long *)(c->host_pinned + 10), token);
+      const int rc = host_wait_token(c, (volatile unsigned long long *)(c->host_pinned + kPinDtToken), token);
       if (rc) { return rc; }
    }
-   *v = c->host_pinned[8];
-   if (*(const int *)(c->host_pinned + 9) != 0)
+   *v = c->host_pinned[kPinDt];
+   if (*(const int *)(c->host_pinned + kPinDtFlag) != 0)
    {
       LGH_HIP_CHECK(hipMemsetAsync(c->dev_flags + 4, 0, sizeof(int), c->stream));
       set_error("lgh_solve_energy was given a velocity other than the state's while the stress was kept in registers "
@@ -1385,9 +1385,9 @@ int lgh_vec_dot(lgh_ctx *c, const double *x, const double *y, long n, double *re
    LGH_CHECK_ARG(c && x && y && result);
    int rc = vec_dot(c, x, y, nullptr, n, c->scal + 1);
    if (rc) { return rc; }
-   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned + 1, c->scal + 1, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned + kPinDot, c->scal + 1, sizeof(double), hipMemcpyDeviceToHost, c->stream));
    LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
-   *result = c->host_pinned[1];
+   *result = c->host_pinned[kPinDot];
    return LGH_OK;
 }
 

@@ -1162,13 +1162,13 @@ int lgh_allreduce(lgh_ctx *c, double *value, int op)
    if (!c->multi || !c->comm) { return LGH_OK; }
    // through the pinned staging area: an async copy from pageable memory is not ordered
    // with the stream
-   c->host_pinned[3] = *value;
-   LGH_HIP_CHECK(hipMemcpyAsync(c->scal + 2, c->host_pinned + 3, sizeof(double), hipMemcpyHostToDevice, c->stream));
+   c->host_pinned[kPinReduceIn] = *value;
+   LGH_HIP_CHECK(hipMemcpyAsync(c->scal + 2, c->host_pinned + kPinReduceIn, sizeof(double), hipMemcpyHostToDevice, c->stream));
    int rc = allreduce_dev(c, c->scal + 2, 1, op);
    if (rc) { return rc; }
-   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned + 2, c->scal + 2, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned + kPinReduceOut, c->scal + 2, sizeof(double), hipMemcpyDeviceToHost, c->stream));
    LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
-   *value = c->host_pinned[2];
+   *value = c->host_pinned[kPinReduceOut];
    return LGH_OK;
 }
 

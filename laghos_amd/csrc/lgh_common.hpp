@@ -55,6 +55,18 @@ struct CgScalars
    int pad;
 };
 
+// Layout of lgh_ctx::host_pinned in doubles.  A scalar CG stages its CgScalars over the front; between solves the first
+// slots take single results.  Everything behind has one user.
+constexpr int kPinDoubles = 96;
+constexpr int kPinResult = 0;                      // a reduction's result (volume, energy, error norm); CgScalars during a scalar CG
+constexpr int kPinDot = 1;                         // lgh_vec_dot
+constexpr int kPinReduceOut = 2, kPinReduceIn = 3; // lgh_allreduce: the value on its way back / in
+constexpr int kPinDt = 8, kPinDtFlag = 9, kPinDtToken = 10; // the dt estimate, its error word, the token of its look (dt_est_fold_k writes the three in a row)
+constexpr int kPinVcg = 32;                        // the velocity CG's scalars at a look (VcgScalars, lgh_vcg.hpp) ...
+constexpr int kPinVcgToken = 80;                   // ... and the token of that look
+static_assert(sizeof(CgScalars) <= kPinDt * sizeof(double) && kPinDtFlag == kPinDt + 1 && kPinDtToken == kPinDt + 2 && kPinDtToken < kPinVcg &&
+              kPinVcgToken < kPinDoubles, "slots of the pinned block: disjoint, inside the allocation");
+
 struct Timers
 {
    bool enabled = true;
@@ -95,7 +107,7 @@ constexpr double kJac0Tol = 1e-12;      // ... of Jac0inv inside a zone up to wh
 // Flags are 0 / 1; -1 where "not set" is an answer of its own.  Field x holds LGH_X unless noted.
 struct Switches
 {
-   // velocity CG (lgh_vcg.hip, lgh_vcg_slab.hip)
+   // velocity CG (lgh_vcg*.hip)
    int vcg_variant;      // which K1 form vcg_solve launches; -1: by kernel id and mesh size (vcg_k1_form)
    int slab_wide, slab_exact, slab_merge, slab_defer, slab_ye_wide; // slab-form K1
    int slab_dyn;         // ... sets drawn from a workgroup queue: 0 / 1, -1: by passes per wavefront (launch_vcg_slab)
@@ -203,7 +215,7 @@ struct lgh_ctx
    unsigned int *tickets;// 4 reduction slots of lgh::kTicketSlot counters (sharded tickets)
    lgh::CgScalars *cgs;  // device
    double *scal;         // small device scalar pool (16 doubles)
-   double *host_pinned;  // pinned host staging, 64 doubles: [0..7] scalar CG / misc, [8] dt, [32..] lockstep CG scalars
+   double *host_pinned;  // pinned host staging, lgh::kPinDoubles doubles; its slots: lgh::kPin*
    unsigned long long look_token; // counts the host looks that wait for a token in pinned memory (host_wait_token)
    double *host_pinned_dev; // the same memory as the device addresses it: scalars a host look needs are written there by the kernel that
                             // finishes them (no copy kernel between it and the stream synchronisation)
@@ -217,7 +229,7 @@ struct lgh_ctx
    int vcg_grid;         // persistent grid size of the K1 kernel (one resident wave)
    int b_h1_sym, b_l2_sym; // the 1-D H1 / L2 table is mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (to 1e-14: the round-off of its evaluation): kernels may hold half of it
    int ncu;              // CUs of this context's device (0: not asked yet)
-   void *vcg_aux;        // tables of the node kernel K2 (lgh_vcg.hip VcgAux), allocated on first use
+   void *vcg_aux;        // tables of the node kernel K2 (lgh_vcg.hpp VcgAux; built and dropped by lgh_vcg_tables.hip), allocated on first use
 
    lgh::Timers timers;
    lgh::KTime *ktime;
@@ -510,7 +522,7 @@ int l2_mass_form(lgh_ctx *c, int *form, int *compact); // kernel of the L2 mass 
 int vcg_solve(lgh_ctx *c, double *B, double *X, double rel_tol, int max_iter, int iters[3],
               const double *force_E = nullptr);
 bool vcg_fused_init_ok(const lgh_ctx *c);
-// tables of the node kernel K2 (lgh_vcg.hip)
+// tables of the node kernel K2 (lgh_vcg_tables.hip)
 int partition_nodes_by_cost(lgh_ctx *c, int W, int **out, const std::vector<int> *valence = nullptr);
 int make_ellz(lgh_ctx *c, unsigned **out, const int *ell = nullptr, int deg = 0);
 int vcg_test_merged_faces(lgh_ctx *c, unsigned char *mask, long *n_merged); // lgh_test_vcg_merged_faces

@@ -337,7 +337,7 @@ mass_apply_3d(const MassArgs a)
 // The quadrature data is read straight from memory, one qy row of Q values ahead of its use (each value is
 // needed by exactly one thread: LDS staging would only add traffic); rows of Q consecutive doubles.
 // MODE 0: y = M x.  MODE 3: CG K1 of the L2 solve (d = r + beta d stored in place, den = (d, M d)).
-// value of the other lane of an adjacent pair (quad_perm [1,0,3,2], as lane_pair_swap of lgh_vcg.hip)
+// value of the other lane of an adjacent pair (quad_perm [1,0,3,2], as lane_pair_swap of lgh_vcg_k1.hip)
 __device__ __forceinline__ double pair_swap(const double v)
 {
    int lo = __double2loint(v), hi = __double2hiint(v);

@@ -42,7 +42,7 @@ int setup_rho0detj0(lgh_ctx *c, const double *x0, const double *rho0_l2, const d
    a.result = c->scal;
    int rc = launch_q<QMODE_SETUP>(c, a);
    if (rc) { return rc; }
-   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned + kPinResult, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
    // Jac0inv the same at every point of a zone?  (An affine initial zone - every mesh of BASELINE.json - has ONE inverse
    // Jacobian; the 216 stored copies of it are 15.5 of the 20.5 KB the row-form update has to stream per zone at Q3Q2.)
    // Every entry of every point against the zone's first point, to kJac0Tol of the zone's largest entry; the update then
@@ -57,7 +57,7 @@ int setup_rho0detj0(lgh_ctx *c, const double *x0, const double *rho0_l2, const d
       LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
       c->jac0_compact = (h == 0 && c->sw.jac0_compact) ? 1 : 0;
    }
-   *volume = c->host_pinned[0];
+   *volume = c->host_pinned[kPinResult];
    return LGH_OK;
 }
 

@@ -62,9 +62,9 @@ int interp_energy(lgh_ctx *c, int which, const double *vec, double *result)
       rc = allreduce_dev(c, c->scal, 1, 0);
       if (rc) { return rc; }
    }
-   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned + kPinResult, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
    LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
-   *result = (which == 0) ? c->host_pinned[0] : 0.5 * c->host_pinned[0];
+   *result = (which == 0) ? c->host_pinned[kPinResult] : 0.5 * c->host_pinned[kPinResult];
    return LGH_OK;
 }
 

@@ -580,9 +580,9 @@ int lgh_sedov_density_error(lgh_ctx *c, const double *x_h1, const double *rho_l2
       const int rc = allreduce_dev(c, c->scal, 1, 0);
       if (rc) { return rc; }
    }
-   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+   LGH_HIP_CHECK(hipMemcpyAsync(c->host_pinned + kPinResult, c->scal, sizeof(double), hipMemcpyDeviceToHost, c->stream));
    LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
-   *err2 = c->host_pinned[0];
+   *err2 = c->host_pinned[kPinResult];
    return LGH_OK;
 }
 }

@@ -1,5 +1,6 @@
-// lgh_vcg.hpp — state, argument block and grid reductions shared by the kernels of the lockstep velocity solve
-// (lgh_vcg.hip: column / plane / Kronecker forms of K1 and the node kernel K2; lgh_vcg_slab.hip: the slab form of K1).
+// lgh_vcg.hpp — what the files of the lockstep velocity solve share: state, argument block and grid reductions of the kernels; on
+// the host side the tables (VcgAux), the plan of one solve (VcgPlan) and the launchers.  lgh_vcg_k1.hip / lgh_vcg_slab.hip: K1 and
+// its dispatch; lgh_vcg_tables.hip: tables; lgh_vcg.hip: node kernels, mode, argument block, vcg_solve; lgh_vcg_hooks.hip: test hooks.
 #pragma once
 #include "lgh_common.hpp"
 
@@ -7,7 +8,7 @@ namespace lgh
 {
 
 constexpr int kVC = 3; // velocity components handled in lockstep
-constexpr int kSlabMinElements = 20000;  // default dispatch of the slab-form K1 (vcg_k1_form): 39.3 against 48.5 us at 32^3, 248 against 383 at 64^3
+constexpr int kSlabMinElements = 20000;  // default dispatch of the slab-form K1 (vcg_resolve_k1): 39.3 against 48.5 us at 32^3, 248 against 383 at 64^3
 constexpr int kTraceRec = 16; // debug (LGH_VCG_TRACE): 64-bit words per workgroup record of K1
 
 struct VcgScalars
@@ -429,6 +430,117 @@ __device__ __forceinline__ long long wave_sum_i64(long long v)
    const int hi = __builtin_amdgcn_readlane((int)(v >> 32), 63);
    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo);
 }
+
+// ---- host side ---------------------------------------------------------------------------------------------------
+#define LGH_VCG_TRY(call) do { const int rc_ = (call); if (rc_) { return rc_; } } while (0) // (an LGH_* status: passed on)
+// one device allocation, freed with its owner (move-only)
+template <typename T> struct DevPtr
+{
+   T *p = nullptr;
+   DevPtr() = default;
+   DevPtr(DevPtr &&o) noexcept : p(o.p) { o.p = nullptr; } // (declaring the moves deletes the copies)
+   DevPtr &operator=(DevPtr &&o) noexcept { std::swap(p, o.p); return *this; }
+   ~DevPtr() { (void)hipFree(p); }
+   operator T *() const { return p; }
+   T **out() { return &p; }              // for the builders that allocate (make_ellz, ...)
+   int alloc(const size_t n, const bool zero = false) // n elements, uninitialised or zero
+   {
+      LGH_HIP_CHECK(hipMalloc((void **)&p, n * sizeof(T)));
+      if (zero) { LGH_HIP_CHECK(hipMemset(p, 0, n * sizeof(T))); }
+      return LGH_OK;
+   }
+   int upload(const T *host, const size_t n) // n elements, copied from the host
+   {
+      LGH_HIP_CHECK(hipMalloc((void **)&p, n * sizeof(T)));
+      LGH_HIP_CHECK(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
+      return LGH_OK;
+   }
+};
+
+// Tables and buffers of the solve that outlive a call (lgh_ctx::vcg_aux; lgh_vcg_tables.hip builds them, vcg_free drops them)
+struct VcgAux
+{
+   DevPtr<double> ye;       // kVC planes of NE*ND + kYePad doubles (slot NE*ND of each plane stays 0.0)
+   DevPtr<unsigned> ellz;
+   DevPtr<uint8_t> essbits;
+   DevPtr<int> nstart;      // cost-balanced node ranges of the grid2 workgroups of vcg_update_p_k
+   DevPtr<unsigned> ellf;   // ELL transpose as byte offsets into a force E-vector ([e][c][d] + zero slot): vcg_init_force_z_k
+   DevPtr<unsigned> mapb;   // element -> node map as byte offsets into a node vector: vcg_apply_slab346
+   int map_xrows = 0;       // the nodes of every x-row of every element are consecutive (vcg_apply_slab346 then loads rows, not nodes)
+   DevPtr<long long> limbs; // exact accumulators of (d, A d), 2 parities
+   DevPtr<long long> rzl;   // exact accumulators of (r, z), 3 sets (rz_limbs mode)
+   int grid2 = 0;
+   int rz_words_all = -1;   // several ranks: every rank can exchange (r, z) as accumulator words (-1: not asked yet)
+   int rz_words_key = -1;   // ... and the local inputs of that question at the time it was asked
+   int ls_all = 0;          // ... every rank could also run the energy CG in lockstep with this solve (asked in the same exchange)
+   int ls_ready = 0;        // the last solve exchanged (r, z) as accumulator words and packed its halo itself (or had no neighbour), here
+                            // and on every other rank: the energy CG may run in lockstep with the next one (vcg_lockstep_ready)
+   // merged E-vector layout of the slab K1 (slab_merge_layout): its set table and the tables of K2 for that layout
+   DevPtr<unsigned> settab;
+   DevPtr<int> ellm;
+   int degm = 0;
+   DevPtr<unsigned> ellzm;
+   DevPtr<int> nstartm;
+   // The library's own order (lgh_order.hip), when it differs from the caller's: the tables and vectors of the solve in the
+   // internal zone order / node numbering - everything the kernels see comes from here then, the context's own tables (the
+   // caller's numbering) serve every other entry point.  ord == nullptr: the caller's order is the solve's.
+   const MeshOrder *ord = nullptr;
+   DevPtr<int> o_map;          // NE*ND: internal node of (internal zone, local dof)
+   DevPtr<int> o_ell;          // t_deg*N: transpose of o_map, E-positions of the solve's own E-vector (internal zone order)
+   DevPtr<int> o_ellc;         // t_deg*N: per internal node, the positions in an E-vector of the CALLER's zone order (the force E-vector)
+   std::vector<int> o_valence; // contributions per internal node
+   DevPtr<uint8_t> o_ess[kVC];
+   DevPtr<double> o_dinv, o_Se, o_massD;
+   DevPtr<double> o_x;         // kVC*N: the solution in internal numbering (vcg_xout_k hands it to the caller)
+   // several ranks: owner weights, shared-node flags and the node lists of the exchanges (lgh_comm.hip) in internal numbering
+   DevPtr<double> o_owner;
+   DevPtr<uint8_t> o_hmask;
+   DevPtr<int> o_nodes, o_shnode;
+   HaloNodeAlias o_alias = {nullptr, nullptr}; // (= o_nodes, o_shnode)
+   unsigned long o_mass_gen = ~0ul;            // c->mass_gen the copies above were taken at
+   DevPtr<unsigned long long> trace;           // debug (LGH_VCG_TRACE=<file>): kTraceRec words per workgroup of K1
+};
+constexpr int kTraceBlocks = 4096; // workgroup records in VcgAux::trace
+
+// K1 as this context runs it (lgh_vcg_k1.hip): the ONE resolution of (kernel id, LGH_VCG_VARIANT, table symmetry, form of the
+// mass data, zone count) - the form for those who ask (vcg_k1_form, the tables a form needs) and the launcher for those who launch
+enum VcgK1Form { kK1None = -1, kK1Column = 0, kK1Plane = 2, kK1Slab = 4, kK1Kron = 5 };
+struct VcgK1 { VcgK1Form form; void (*launch)(lgh_ctx *, const VcgArgs &); };
+VcgK1 vcg_resolve_k1(lgh_ctx *c);
+int vcg_ncu(lgh_ctx *c); // CUs of the context's device (asked once per context)
+
+// How a solve of this context runs - decided in one place (vcg_mode, lgh_vcg.hip), read by vcg_solve and the hooks
+struct VcgMode
+{
+   bool multi;    // a communicator is attached (one rank under LGH_FORCE_MULTI included)
+   bool k2p;      // K2 is the bounded-grid kernel vcg_update_p_k (LGH_K2P=0 or a valence above 8: vcg_update_k, one node per thread)
+   bool mixed;    // several ranks, valence <= 8: K2 gathers A d itself but for the rank-shared nodes
+   bool direct;   // one rank, valence <= 8: K2 follows K1 directly (otherwise A d passes through L-vectors and, on several ranks, exchanges)
+   bool limbs;    // (d, A d) in exact accumulators: slab-form K1 with the bounded-grid K2 (LGH_SLAB_EXACT=0: ticketed fold)
+   bool rz_words; // (r, z) could travel / be folded as accumulator words - on several ranks every rank's answer, or nobody's
+   bool rzl;      // rz_limbs mode: it does (needs the deferred fold of (d, A d) as well)
+   int den_limbs; // VcgArgs::den_limbs
+   int n_shared;  // nodes shared with other ranks
+   int pack_halo, nx_den, pack_rz; // VcgArgs: the kernels fill the send buffers themselves
+   bool ls_mine;  // this rank could run the energy CG in lockstep with the solve
+   bool ls;       // ... and this solve does
+};
+
+// Everything a launch of the lockstep kernels needs (vcg_prepare): vcg_solve and the one-launch hooks
+struct VcgPlan { VcgArgs a; VcgAux *aux; VcgK1 k1; VcgMode mode; };
+int vcg_prepare(lgh_ctx *c, double *B, double *X, double rel_tol, VcgPlan &plan, bool in_solve = false);
+
+// launchers: a kernel is launched from the file that defines it (a.iter, a.partials, a.ticket set by the caller)
+void vcg_launch_k1(lgh_ctx *c, const VcgPlan &plan, const VcgArgs &a);
+void vcg_launch_k2p(lgh_ctx *c, const VcgPlan &plan, const VcgArgs &a, int it); // bounded-grid K2 of iteration it
+void vcg_launch_update(lgh_ctx *c, const VcgArgs &a, bool fused_gather);        // vcg_update_k<true, 8> / <false, 0>
+void vcg_launch_fold_den(lgh_ctx *c, const VcgArgs &a);
+void vcg_launch_rz_finish(lgh_ctx *c, const VcgArgs &a, int last, VcgScalars *host_out, unsigned long long *host_token, unsigned long long token);
+
+// lgh_vcg_tables.hip
+struct SlabLayout { std::vector<unsigned> settab; std::vector<int> pos; std::vector<uint8_t> sec; size_t n_merged = 0; };
+int slab_merge_layout(lgh_ctx *c, const VcgAux *x, SlabLayout &L); // x: the tables of the order the solve runs in
+int vcg_build_aux(lgh_ctx *c); // builds the tables and publishes them as c->vcg_aux - or leaves it null
 
 // lgh_vcg_slab.hip
 bool vcg_slab_available(lgh_ctx *c);

@@ -4,7 +4,7 @@
 // Reference math: MassPAOperator::Mult, /root/reference/laghos_assembly.cpp:117-121 (the contraction is upstream
 // MFEM's MassIntegrator::AddMultPA; restated in amr/laghos_assembly.cpp:878-963).
 //
-// Where it comes from.  The plane form (vcg_apply_plane, lgh_vcg.hip) exchanges the operands of the two x contractions
+// Where it comes from.  The plane form (vcg_apply_plane, lgh_vcg_k1.hip) exchanges the operands of the two x contractions
 // through LDS behind workgroup barriers: ~19 of the ~33 us of its loop are LDS issue.  The matrix-core form
 // (lgh_vcg_mfma.hip) removed that exchange - one tile column per (element, component) item, everything else in
 // registers - but v_mfma_f64_16x16x4_f64 runs on the fp64 FMA pipe itself (tools/ubench_f64.hip: 64 cycles per
@@ -976,12 +976,7 @@ static void slab_launch(lgh_ctx *c, const VcgArgs &a, const int grid, const int 
 
 void launch_vcg_slab(lgh_ctx *c, const VcgArgs &a)
 {
-   if (c->ncu <= 0) // (per context: contexts of one process may sit on different devices)
-   {
-      hipDeviceProp_t prop;
-      c->ncu = (hipGetDeviceProperties(&prop, c->device) == hipSuccess) ? prop.multiProcessorCount : 256;
-   }
-   const int ncu = c->ncu;
+   const int ncu = vcg_ncu(c);
    const int nset = ceil_div(c->NE, 5);
    const int grid = std::min(ceil_div(nset, 4), ncu); // one workgroup of four wavefronts per CU
    const bool wide = c->sw.slab_wide && a.map_xrows != 0;

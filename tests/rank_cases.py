@@ -2,7 +2,7 @@
 (CPU: the conditions the GPU tests rely on), tests/test_gpu_ranks_2d.py (the kernels on ranks), tests/test_host_setup.py
 and the 2D entries of tests/test_gpu_pipeline.py::MULTI_RANK_CASES.
 
-In 3D every velocity solve goes through the lockstep solver (lgh_vcg.hip); in 2D vcg_supported() is false and
+In 3D every velocity solve goes through the lockstep solver (lgh_vcg.hip); in 2D vcg_available() is false and
 lgh_solve_velocity runs the scalar cg_solve(LGH_SPACE_H1) of lgh_mass.hip once per component - whose several-rank branch
 (rank-summed (r, z) and (d, A d), looked at by the NEXT kernel of the sequence) no 3D run reaches.
 

@@ -5,15 +5,15 @@ Every other kernel-level parity test runs on 4x2x2, 4x4x4, 8x8x8, 32^3 or 64^3 z
 32 or 64 zones, NE a multiple of 16, and - problem 1 on equal zones - one mass factor s_e and one Jac0inv for all zones.
 The kernels group zones by constants such grids never stress.  Read off the dispatch code (not the comments):
 
-  slab K1           sets of ES = 5 consecutive zones      lgh_vcg_slab.hip (ES), lgh_vcg.hip::slab_merge_layout
+  slab K1           sets of ES = 5 consecutive zones      lgh_vcg_slab.hip (ES), lgh_vcg_tables.hip::slab_merge_layout
   plane K1          NEB = 256 / (3 Q) zones, one less at Q = 6: 42 (Q1Q0), 21 (Q2Q1), 13 (Q3Q2)
-                                                          lgh_vcg.hip::launch_vcg_plane
+                                                          lgh_vcg_k1.hip::launch_vcg_plane
   plane K1, D >= 5  5 zones (Q4Q3), 4 zones (Q5Q4), also with two lanes per plane
-                                                          lgh_vcg.hip::vcg_launch_k1 (launch_vcg_plane_ho<5, 8, HY, 5>, <6, 10, 2, 4>)
+                                                          lgh_vcg_k1.hip::vcg_resolve_k1 (launch_vcg_plane_ho<5, 8, HY, 5>, <6, 10, 2, 4>)
   column K1         256 / Q^2 zones: 64, 16, 7, 4, 2 for Q1Q0 ... Q5Q4
-                                                          lgh_vcg.hip::launch_vcg_apply
+                                                          lgh_vcg_k1.hip::launch_vcg_apply
   Kronecker K1      64, 32, 16 zones at D1D = 2, 3, 4; 3 (LGH_KRON_NEB=0: 8) at D1D = 5; 2 (4) at D1D = 6
-                                                          lgh_vcg.hip::vcg_launch_k1
+                                                          lgh_vcg_k1.hip::vcg_resolve_k1
   L2 Kronecker      256, 128, 64, 32 zones at L1D = 1 ... 4; 10 (LGH_L2_NEB=0: 16) at L1D = 5
                                                           lgh_mass.hip::launch_mass (LGH_L2K)
   mass column forms, force kernels, 2D point form of the quadrature update

@@ -132,7 +132,7 @@ def boxes():
 
 
 def expected_k1(order, variant, compact, h1_sym=True, tensor=True):
-    """lgh_vcg.hip::vcg_k1_form below the slab threshold of 20 000 zones"""
+    """lgh_vcg_k1.hip::vcg_resolve_k1 below the slab threshold of 20 000 zones"""
     if order == (3, 2) and variant == "4":
         return "slab"
     if ((variant is None and order[0] >= 4) or variant == "5") and tensor and compact:

@@ -722,7 +722,7 @@ def test_slab_k1_switches(switches, monkeypatch):
 
 def test_slab_merged_evector_vs_element_local(monkeypatch):
     """Round 5: where the five zones of a slab set are x-neighbours K1 sums the shared x-faces itself and stores 16 rows
-    of 16 x-nodes per component (merged E-vector layout, lgh_vcg.hip::slab_merge_layout); LGH_SLAB_MERGE=0 keeps the
+    of 16 x-nodes per component (merged E-vector layout, lgh_vcg_tables.hip::slab_merge_layout); LGH_SLAB_MERGE=0 keeps the
     element-local layout of rounds 3 and 4.  512 zones in rows of 8 (chains, sets that straddle two rows, a ragged last
     set), distorted state, CG to 1e-14: both layouts give the oracle's dv/dt to the operator tolerance and agree with
     each other to round-off (the order of the per-node sums differs); within a layout the schedule (workgroup queues or

@@ -1,4 +1,4 @@
-"""Summary of LGH_VCG_TRACE=<file> (per-workgroup stamps of the last K1 launch of a solve, lgh_vcg.hip /
+"""Summary of LGH_VCG_TRACE=<file> (per-workgroup stamps of the last K1 launch of a solve, lgh_vcg_k1.hip /
 lgh_vcg_mfma.hip): wall-clock stamps in 10 ns ticks; column 5 of the matrix-core K1 packs
 (cycles waiting for loads << 32) | cycles in the loop of wave 0."""
 import sys
