@@ -1,5 +1,6 @@
 // lgh_api.hip — C ABI of liblaghos_hip.so: context life cycle, vector helpers,
-// timers, and the operator-level entry points declared in include/laghos_hip.h.
+// timers, and the operator-level entry points declared in include/laghos_hip.h
+// (SolveEnergy and its entry points: lgh_energy.hip).
 #include <cstdarg>
 #include <cstdlib>
 #include <cmath>
@@ -126,8 +127,6 @@ __global__ void __launch_bounds__(256) dt_est_fold_k(double *p, const int *err, 
       __hip_atomic_store((unsigned long long *)(host_out + 2), token, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); // (host_wait_token)
    }
 }
-
-static int grid_for(long n) { return (int)std::min<long>(std::max<long>((n + 255) / 256, 1), 2048); }
 
 int vec_set(lgh_ctx *c, double *y, double a, long n)
 {
@@ -380,20 +379,13 @@ int host_wait_token(lgh_ctx *c, volatile unsigned long long *word, const unsigne
    return LGH_OK;
 }
 
-int energy_overlap_poll(lgh_ctx *c)
+// The stress of the current quadrature data is in memory (readers of stressJinvT call this first).
+int stress_on_hand(lgh_ctx *c, const char *who)
 {
-   if (c->e_async != 1 || c->e_polled) { return LGH_OK; }
-   int it = 0;
-   std::swap(c->stream, c->stream2);
-   c->on_stream2 = 1;
-   int rc = cg_l2_end(c, &it);
-   if (rc == LGH_OK) { rc = (hipEventRecord(c->ev_join, c->stream) == hipSuccess) ? LGH_OK : LGH_ERR_HIP; }
-   std::swap(c->stream, c->stream2);
-   c->on_stream2 = 0;
-   if (rc) { return rc; }
-   c->e_polled = 1;
-   c->e_iters = it;
-   return LGH_OK;
+   if (c->stress_current) { return LGH_OK; }
+   set_error("%s needs stressJinvT, which the last lgh_qupdate kept in registers (lgh_qupdate_store_stress(ctx, 0)): "
+             "only F.1 and F^T v of the state's own velocity are on hand; store the stress (..., 1) and update again", who);
+   return LGH_ERR_ARG;
 }
 
 } // namespace lgh
@@ -454,10 +446,8 @@ int lgh_create(const lgh_config *cfg, lgh_ctx **out)
       return LGH_ERR_UNSUPPORTED;
    }
 
-   lgh_ctx *c = new lgh_ctx();
-   memset((void *)c, 0, sizeof(lgh_ctx));
-   new (&c->timers) Timers();
-   new (&c->sw) Switches(read_switches());
+   lgh_ctx *c = new lgh_ctx(); // (value-initialised: every member zero, then the default member initialisers)
+   c->sw = read_switches();
    if (c->sw.roctx) { roctx_enable(); }
    c->device = cfg->device;
    // every failure below (HIP errors, out of memory) releases what was built so far
@@ -681,8 +671,8 @@ int lgh_destroy(lgh_ctx *c)
    {
       (void)hipStreamSynchronize(c->stream2);
       (void)hipStreamDestroy(c->stream2);
-      (void)hipEventDestroy(c->ev_fork);
-      (void)hipEventDestroy(c->ev_join);
+      if (c->ev_fork) { (void)hipEventDestroy(c->ev_fork); } // (create_stream2 may have failed between the stream and its events)
+      if (c->ev_join) { (void)hipEventDestroy(c->ev_join); }
    }
    extern void lgh_comm_free(lgh_ctx *);
    lgh_comm_free(c);
@@ -714,14 +704,6 @@ double *lgh_qdata_stressJinvT(lgh_ctx *c)
    // readers keep refusing until lgh_qupdate_store_stress(ctx, 1) and an update
    if (c->stress_store) { c->stress_current = 1; }
    return c->stressJinvT;
-}
-// The stress of the current quadrature data is in memory (readers of stressJinvT call this first).
-static int stress_on_hand(lgh_ctx *c, const char *who)
-{
-   if (c->stress_current) { return LGH_OK; }
-   set_error("%s needs stressJinvT, which the last lgh_qupdate kept in registers (lgh_qupdate_store_stress(ctx, 0)): "
-             "only F.1 and F^T v of the state's own velocity are on hand; store the stress (..., 1) and update again", who);
-   return LGH_ERR_ARG;
 }
 // Entry points with no 1D form (the 2D/3D kernel forms, the lockstep solve, E-vector test hooks) refuse a 1D context.
 static int no_1d(const lgh_ctx *c, const char *who)
@@ -1106,252 +1088,6 @@ int lgh_solve_velocity(lgh_ctx *c, const double *S, double *dS_dt, const double 
       c->timers.c[0] += it; // :392
       if (h1_iters) { *h1_iters += it; }
    }
-   return LGH_OK;
-}
-
-// ForcePA->MultTranspose(v, e_rhs) of SolveEnergy (laghos_solver.cpp:473).  The fused QUpdate has formed F^T v for the
-// velocity of the state it was called for; it stands in for the kernel exactly when the quadrature data is still that
-// of this update AND the v passed now equals that velocity element for element - compared on the device, whatever the
-// address (RK2Avg's averaged velocity, or a state changed in place since, go through the kernel, as in the reference).
-// No host look: the comparison leaves a flag, the force kernel returns at once when it is 0, the copy when it is not.
-__global__ void __launch_bounds__(256) vec_differs_k(const double *__restrict__ a, const double *__restrict__ b, const long n, int *flag)
-{
-   // (compared as bit patterns: -0.0 vs 0.0 or a NaN payload count as different - the kernel then simply runs)
-   // grid-stride, 16-byte loads where both vectors allow them (round 5: one element per thread reached 2 TB/s at 64^3)
-   const long stride = (long)gridDim.x * blockDim.x, t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-   bool diff = false;
-   if (((((uintptr_t)a) | ((uintptr_t)b)) & 15u) == 0)
-   {
-      const longlong2 *a2 = (const longlong2 *)a, *b2 = (const longlong2 *)b;
-      for (long i = t; i < n / 2; i += stride)
-      {
-         const longlong2 p = a2[i], q = b2[i];
-         diff = diff || p.x != q.x || p.y != q.y;
-      }
-      if ((n & 1) && t == 0) { diff = diff || __double_as_longlong(a[n - 1]) != __double_as_longlong(b[n - 1]); }
-   }
-   else
-   {
-      for (long i = t; i < n; i += stride) { diff = diff || __double_as_longlong(a[i]) != __double_as_longlong(b[i]); }
-   }
-   if (diff) { *flag = 1; }
-}
-// e_rhs = F^T v of the quadrature update unless the velocity differs from the one it was formed for; then (the stress being in
-// registers only) NaN and the error word (rounds 3-4: two launches, poison and copy)
-__global__ void __launch_bounds__(256) erhs_take_or_poison_k(double *__restrict__ y, const double *__restrict__ x, const long n, const int *__restrict__ flag, int *err)
-{
-   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-   if (*flag != 0)
-   {
-      if (i < n) { y[i] = __builtin_nan(""); }
-      if (i == 0) { *err = 1; }
-      return;
-   }
-   if (i < n) { y[i] = x[i]; }
-}
-__global__ void __launch_bounds__(256) copy_unless_k(double *__restrict__ y, const double *__restrict__ x, const long n, const int *__restrict__ flag)
-{
-   if (*flag != 0) { return; }
-   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-   if (i < n) { y[i] = x[i]; }
-}
-static int energy_rhs(lgh_ctx *c, const double *v_h1, double *e_rhs)
-{
-   RoctxRange range("SolveEnergy-ForcePA"); // laghos_solver.cpp:472-475
-   if (c->erhs_q && c->fused_ftv_valid)
-   {
-      int *flag = c->dev_flags + (c->on_stream2 ? 2 : 0);
-      LGH_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), c->stream));
-      hipLaunchKernelGGL(vec_differs_k, dim3(grid_for((c->H1V + 1) / 2)), dim3(256), 0, c->stream, v_h1, c->v_snap, (long)c->H1V, flag);
-      LGH_HIP_CHECK(hipGetLastError());
-      if (c->stress_current)
-      {
-         const int rc = force_mult_t_L(c, c->stressJinvT, v_h1, e_rhs, flag); // (runs only for a different v)
-         if (rc) { return rc; }
-         hipLaunchKernelGGL(copy_unless_k, dim3(ceil_div(c->L2V, 256)), dim3(256), 0, c->stream, e_rhs, c->erhs_q, (long)c->L2V, flag);
-      }
-      else
-      {
-         // the stress was kept in registers: a velocity other than the state's cannot be served - the right-hand side
-         // becomes NaN on the device (nothing downstream can look right) and the next lgh_get_dt_est reports it
-         hipLaunchKernelGGL(erhs_take_or_poison_k, dim3(ceil_div(c->L2V, 256)), dim3(256), 0, c->stream, e_rhs, c->erhs_q, (long)c->L2V, flag, c->dev_flags + 4);
-      }
-      LGH_HIP_CHECK(hipGetLastError());
-      return LGH_OK;
-   }
-   return lgh_force_mult_transpose(c, v_h1, e_rhs);
-}
-
-// SolveEnergy, PA branch (laghos_solver.cpp:442-490)
-int lgh_solve_energy(lgh_ctx *c, const double *S, const double *v_h1, double *dS_dt, double *e_rhs,
-                     const double *e_source, double rel_tol, int max_iter, int *l2_iters)
-{
-   LGH_CHECK_ARG(c && S && v_h1 && dS_dt && e_rhs);
-   (void)S;
-   double *de = dS_dt + 2 * (size_t)c->H1V;
-   if (c->dim == 1) // the FA branch: zone-local solves with the factors of Me(z), no CG (laghos_solver.cpp:491-516)
-   {
-      const int rc1 = stress_on_hand(c, "lgh_solve_energy");
-      if (rc1) { return rc1; }
-      return solve_energy_1d(c, v_h1, de, e_rhs, e_source, l2_iters);
-   }
-   timer_start(c);
-   int rc = energy_rhs(c, v_h1, e_rhs); // :473
-   timer_stop(c, 2);
-   if (rc) { return rc; }
-   if (e_source)
-   {
-      rc = vec_axpby(c, e_rhs, 1.0, e_rhs, 1.0, e_source, c->L2V); // :477
-      if (rc) { return rc; }
-   }
-   int it = 0;
-   RoctxRange range("SolveEnergy-CGEMass"); // laghos_solver.cpp:480-483
-   timer_start(c);
-   rc = cg_solve(c, LGH_SPACE_L2, e_rhs, de, rel_tol, max_iter, &it, true); // :481
-   timer_stop(c, 1);
-   if (rc) { return rc; }
-   const int counted = (it == 0) ? 1 : it; // :486
-   c->timers.c[1] += counted;
-   if (l2_iters) { *l2_iters += counted; }
-   return LGH_OK;
-}
-
-// SolveEnergy does not depend on SolveVelocity's result (it takes v from S), so
-// LagrangianHydroOperator::Mult may run the two concurrently: _begin enqueues F^T v
-// and the first chunk of the L2 CG on the second stream behind a fork event, _end
-// completes the solve and joins.  Falls back to the sequential lgh_solve_energy
-// inside _end when region timers / kernel timing are on (their semantics are
-// sequential, as in the reference), on several ranks without a second communicator
-// (one RCCL communicator must not be driven from two streams: lgh_comm_init creates a
-// second one for this), or when the velocity solve would use the scalar CG (shared
-// scratch).  LGH_OVERLAP=0 switches it off.
-// The second stream, for the energy solve beside the velocity solve - at the LOWEST priority the device offers (round 6): the
-// velocity solve is the longer of the two at every order up to Q4Q3 and its kernels fill the device; the energy solve's small
-// kernels then take what is left instead of an equal share of the dispatch slots: 8.81 -> 8.75 ms per step at C2 on one box,
-// 8.85 -> 8.78 on another; config 5, where the energy CG is the longer one, does not lose (372 -> 367 ms), the highest priority
-// gains nothing anywhere (profiles/r6_stream_priority.txt).
-static int create_stream2(lgh_ctx *c)
-{
-   int least = 0, greatest = 0;
-   if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-   {
-      LGH_HIP_CHECK(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, least));
-   }
-   else { LGH_HIP_CHECK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking)); }
-   LGH_HIP_CHECK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-   LGH_HIP_CHECK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-   return LGH_OK;
-}
-static bool energy_overlap_ok(const lgh_ctx *c)
-{
-   return c->sw.overlap && (c->multi == 0 || comm_second_channel(c)) && !c->timers.enabled && !(c->ktime && c->ktime->which >= 0) && vcg_available(c);
-}
-int lgh_solve_energy_begin(lgh_ctx *c, const double *S, const double *v_h1, double *dS_dt, double *e_rhs,
-                           const double *e_source, double rel_tol, int max_iter)
-{
-   LGH_CHECK_ARG(c && S && v_h1 && dS_dt && e_rhs);
-   c->e_args = {S, v_h1, dS_dt, e_rhs, e_source, rel_tol, max_iter};
-   c->e_lockstep = 0;
-   if (c->dim == 1) // (no overlap in 1D: _end runs the zone-local solve, after the velocity solve as in the reference)
-   {
-      c->e_async = 2;
-      return LGH_OK;
-   }
-   if (!energy_overlap_ok(c))
-   {
-      // Several ranks without a second channel (the default over real RCCL): the energy CG runs in LOCKSTEP with the velocity
-      // CG on this one stream and communicator instead of after it - its two dot products per iteration ride on exchanges the
-      // velocity iteration makes anyway.  Right-hand side and initial residual here, the iterations inside
-      // lgh_solve_velocity, what is left of them in _end.  LGH_ENERGY_LOCKSTEP=0: the solve after the velocity solve.
-      if (c->sw.energy_lockstep && c->sw.overlap && c->multi != 0 && !comm_second_channel(c) && !c->timers.enabled && !(c->ktime && c->ktime->which >= 0) && vcg_available(c) &&
-          l2_lockstep_possible(c) && vcg_lockstep_ready(c))
-      {
-         int rc = energy_rhs(c, v_h1, e_rhs); // :473
-         if (rc == LGH_OK && e_source) { rc = vec_axpby(c, e_rhs, 1.0, e_rhs, 1.0, e_source, c->L2V); } // :477
-         if (rc == LGH_OK) { rc = cg_l2_begin_lockstep(c, e_rhs, dS_dt + 2 * (size_t)c->H1V, rel_tol, max_iter); }
-         if (rc) { return rc; }
-         c->e_async = 3;
-         c->e_lockstep = 1;
-         return LGH_OK;
-      }
-      c->e_async = 2;
-      return LGH_OK;
-   }
-   if (!c->stream2)
-   {
-      const int rc2 = create_stream2(c);
-      if (rc2) { return rc2; }
-   }
-   LGH_HIP_CHECK(hipEventRecord(c->ev_fork, c->stream));
-   LGH_HIP_CHECK(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-   std::swap(c->stream, c->stream2); // everything below is enqueued on the second stream
-   c->on_stream2 = 1;
-   int rc = energy_rhs(c, v_h1, e_rhs); // :473
-   if (rc == LGH_OK && e_source) { rc = vec_axpby(c, e_rhs, 1.0, e_rhs, 1.0, e_source, c->L2V); } // :477
-   if (rc == LGH_OK)
-   {
-      RoctxRange range("SolveEnergy-CGEMass"); // laghos_solver.cpp:480-483 (first chunk, second stream)
-      rc = cg_l2_begin(c, e_rhs, dS_dt + 2 * (size_t)c->H1V, rel_tol, max_iter); // :481
-   }
-   std::swap(c->stream, c->stream2);
-   c->on_stream2 = 0;
-   if (rc) { return rc; }
-   c->e_async = 1;
-   c->e_polled = 0;
-   return LGH_OK;
-}
-int lgh_energy_lockstep_stats(lgh_ctx *c, long out[4])
-{
-   LGH_CHECK_ARG(c && out);
-   out[0] = c->ls_stats[0]; out[1] = c->ls_stats[1]; out[2] = c->ls_stats[2];
-   out[3] = (c->dim != 1 && c->multi != 0 && !comm_second_channel(c) && vcg_available(c) && l2_lockstep_possible(c) && vcg_lockstep_ready(c)) ? 1 : 0;
-   return LGH_OK;
-}
-int lgh_solve_energy_end(lgh_ctx *c, int *l2_iters)
-{
-   LGH_CHECK_ARG(c && (c->e_async == 1 || c->e_async == 2 || c->e_async == 3));
-   const int mode = c->e_async;
-   c->e_async = 0;
-   if (mode == 3)
-   {
-      // lockstep: whatever the velocity solve did not interleave (a solve that needs more iterations than last time, or than the
-      // velocity solve took) runs now, reducing its scalars itself; then the look
-      c->e_lockstep = 0;
-      int it = 0;
-      const int rc = cg_l2_end_lockstep(c, &it);
-      if (rc) { return rc; }
-      const int counted = (it == 0) ? 1 : it; // :486
-      c->timers.c[1] += counted;
-      if (l2_iters) { *l2_iters += counted; }
-      return LGH_OK;
-   }
-   if (mode == 1 && c->e_polled)
-   {
-      // completed from inside the velocity solve (energy_overlap_poll): only the join is left
-      c->e_polled = 0;
-      LGH_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-      const int counted = (c->e_iters == 0) ? 1 : c->e_iters; // :486
-      c->timers.c[1] += counted;
-      if (l2_iters) { *l2_iters += counted; }
-      return LGH_OK;
-   }
-   if (mode == 2)
-   {
-      return lgh_solve_energy(c, c->e_args.S, c->e_args.v, c->e_args.dS, c->e_args.e_rhs, c->e_args.src,
-                              c->e_args.tol, c->e_args.maxit, l2_iters);
-   }
-   int it = 0;
-   std::swap(c->stream, c->stream2);
-   c->on_stream2 = 1;
-   int rc = cg_l2_end(c, &it);
-   if (rc == LGH_OK) { rc = (hipEventRecord(c->ev_join, c->stream) == hipSuccess) ? LGH_OK : LGH_ERR_HIP; }
-   std::swap(c->stream, c->stream2);
-   c->on_stream2 = 0;
-   if (rc) { return rc; }
-   LGH_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-   const int counted = (it == 0) ? 1 : it; // :486
-   c->timers.c[1] += counted;
-   if (l2_iters) { *l2_iters += counted; }
    return LGH_OK;
 }
 

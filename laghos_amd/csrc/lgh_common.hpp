@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -115,10 +116,10 @@ struct Switches
    int k2p, k2_skip, k2_grid; // K2; k2_grid: node ranges per CU, 0: by mesh size
    long k2_node_weight;  // fixed part of a node's cost in units of half a contribution; < 0: equal counts
    int order, order_multi;
-   // several ranks (lgh_comm.hip), energy solve beside the velocity solve (lgh_api.hip), host looks
+   // several ranks (lgh_comm.hip), energy solve beside the velocity solve (lgh_energy.hip), host looks
    int comm2;            // -1: not set (the loop-back transports then have the second channel, RCCL on more than one rank does not)
    int force_multi, halo_piggyback, halo_fused_pack, overlap, energy_lockstep, spin;
-   // mass operators (lgh_mass.hip)
+   // mass operators (lgh_mass.hip) and the scalar CG on them (lgh_scg.hip)
    int mass_sep, mass_kron, mass_rank1, l2_neb, l2_plane, l2_fused;
    double mass_rank1_tol; // (default kMassRank1Tol)
    // quadrature update and set-up
@@ -133,6 +134,24 @@ struct Switches
 };
 Switches read_switches();
 
+struct ScalarCg; // one scalar CG solve: what its kernels are launched with, how far it has been enqueued (lgh_scg.hip)
+
+// The energy solve between lgh_solve_energy_begin and _end (lgh_energy.hip): which way _begin took, and what _end needs for it.
+struct EnergySolve
+{
+   enum Mode
+   {
+      Idle,       // no solve begun
+      Overlapped, // right-hand side and first chunk of the CG enqueued on the second stream, beside the velocity solve
+      Deferred,   // nothing enqueued: _end runs the whole of lgh_solve_energy with the saved arguments
+      Lockstep    // several ranks, one stream and communicator: set up on the main stream, lgh_solve_velocity interleaves the iterations
+   };
+   Mode mode = Idle;
+   bool polled = false; // Overlapped: completed from inside the velocity solve already (energy_overlap_poll) ...
+   int iters = 0;       // ... with this iteration count
+   struct { const double *S, *v; double *dS, *e_rhs; const double *src; double tol; int maxit; } args = {}; // Deferred
+};
+
 } // namespace lgh
 
 struct lgh_ctx
@@ -145,18 +164,14 @@ struct lgh_ctx
    double q_tiny_grad;   // QUpdate: threshold of the wave-uniform eigen-decomposition shortcut (lgh_qupdate.hip)
    int device;
    hipStream_t stream;
-   // second stream + fork/join events: the energy solve overlaps the velocity solve (lgh_api.hip)
+   // second stream + fork/join events: the energy solve overlaps the velocity solve (lgh_energy.hip)
    hipStream_t stream2;
    int on_stream2;       // 1 while `stream` holds the second stream (energy solve beside the velocity solve): reductions use the communicator's second channel
    hipEvent_t ev_fork, ev_join;
-   void *l2run;          // state of a split L2 solve (lgh_mass.hip)
+   lgh::ScalarCg *l2run = nullptr; // the run of a split L2 solve (lgh_scg.hip: cg_l2_begin .. cg_l2_end, cg_l2_free), allocated on first use
    const double *accel_src; // dim*N acceleration source of SolveVelocity (source_type 2) or nullptr
-   int e_async;          // 1: lgh_solve_energy_begin enqueued the solve, 2: deferred to _end
-   int e_lockstep;       // lgh_solve_energy_begin has set the energy CG up for LOCKSTEP with the velocity CG on the one stream and communicator
+   lgh::EnergySolve energy; // the energy solve lgh_solve_energy_begin has begun
    long ls_stats[3] = {0, 0, 0}; // lockstep energy solves; their iterations enqueued inside the velocity solve; ... and after it (lgh_energy_lockstep_stats)
-                         // (several ranks without a second channel; lgh_mass.hip "lockstep"): lgh_solve_velocity interleaves its iterations
-   int e_polled, e_iters; // the enqueued solve has already been completed (energy_overlap_poll, from inside the velocity solve): its iteration count
-   struct { const double *S, *v; double *dS, *e_rhs; const double *src; double tol; int maxit; } e_args;
    bool own_stream;
 
    // tables (device): B_h1/G_h1 [q + Q*d], B_l2 [q + Q*l], weights [NQ]
@@ -491,6 +506,7 @@ __device__ __forceinline__ int xcd_swizzle(const int b, const int nblocks)
 }
 
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+inline int grid_for(long n) { return (int)std::min<long>(std::max<long>((n + 255) / 256, 1), 2048); } // workgroups of 256 for a grid-stride loop over n
 
 // ---- lgh_order.hip
 int mesh_order_build(lgh_ctx *c, const int *map_host);
@@ -556,7 +572,7 @@ int host_wait_token(lgh_ctx *c, volatile unsigned long long *word, unsigned long
 constexpr int kLsWord = 50;             // (a padding word of an accumulator set: lgh_vcg.hpp checks it is one)
 constexpr int kLsWordsPerSet = 56;      // = kLimbWords (checked there): stride of the peers' sets
 struct LockstepWords { const long long *own; const long long *peers; int n_peers, before; }; // before: peers of lower rank
-bool l2_lockstep_possible(lgh_ctx *c);  // the L2 apply runs as the Kronecker kernel with the fused update (lgh_mass.hip)
+bool l2_lockstep_possible(lgh_ctx *c);  // the L2 apply runs as the Kronecker kernel with the fused update (lgh_scg.hip)
 int cg_l2_begin_lockstep(lgh_ctx *c, const double *b, double *x, double rel_tol, int max_iter); // set-up + initial residual, no iteration
 int l2_lockstep_limit(lgh_ctx *c);      // iterations worth interleaving: the previous solve's count
 int l2_lockstep_apply(lgh_ctx *c, int it, const LockstepWords &prev, double *den_mirror);
@@ -570,6 +586,7 @@ int cg_l2_end(lgh_ctx *c, int *iters);
 void cg_l2_free(lgh_ctx *c);
 int cg_solve(lgh_ctx *c, int space, const double *b, double *x, double rel_tol, int max_iter,
              int *iters, bool x_is_zero);
+int stress_on_hand(lgh_ctx *c, const char *who); // LGH_OK: the stress of the current quadrature data is in memory (lgh_api.hip)
 int qupdate(lgh_ctx *c, const double *S);
 int setup_rho0detj0(lgh_ctx *c, const double *x0, const double *rho0_l2, const double *rho0_q,
                     double *volume);

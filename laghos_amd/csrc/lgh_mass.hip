@@ -1,139 +1,14 @@
-// lgh_mass.hip — MassPAOperator action, Jacobi diagonal and the device-resident
-// CG solves for gfx950.
+// lgh_mass.hip — MassPAOperator action and Jacobi diagonal for gfx950: the element kernels and their dispatch, the mass
+// data, the node gather.  The device-resident CG solves written on them are in lgh_scg.hip.
 //
 // Replaces MassPAOperator::{Mult,MultFull,EliminateRHS}
 // (/root/reference/laghos_assembly.cpp:80-121; the contraction itself is upstream
-// MFEM MassIntegrator::AddMultPA, same math as amr/laghos_assembly.cpp:878-963),
-// OperatorJacobiSmoother (laghos_solver.cpp:266-270) and the two CGSolver
-// instances configured at laghos_solver.cpp:264-284 (algorithm: SURVEY §3.2).
-//
-// MI355X design: one CG iteration is two kernels and no host round trip.
-//   K1 (element batches): beta = rz/rz_prev; the new direction d = z + beta*d is
-//       formed on the fly inside the gather (not stored: elements sharing a node
-//       all read the old z, d); y_e = B^T D B d_e with the z contraction in
-//       registers and tables in SGPRs; den = sum_e d_e.y_e (the E-vector form of
-//       (d, A d), so no extra pass over the L-vector is needed).
-//   K2 (nodes): forms the same d = z + beta*d in place (one thread per node, no
-//       race), z = sum of element contributions (deterministic gather over an
-//       ELL-format transpose, coalesced index loads, no atomics), essential rows
-//       zeroed, alpha = rz/den, x += alpha d, r -= alpha z, z = r/diag,
-//       betanom = (r,z) with a wave64 shuffle reduction; the last block to
-//       finish folds the block partials in fixed order, updates the device
-//       scalars and the convergence flag.
-// The host only enqueues iterations in chunks and looks at the flag between
-// chunks; once `done` is set the remaining kernels of a chunk exit immediately.
-#include "lgh_common.hpp"
+// MFEM MassIntegrator::AddMultPA, same math as amr/laghos_assembly.cpp:878-963) and
+// OperatorJacobiSmoother (laghos_solver.cpp:266-270).
+#include "lgh_mass.hpp"
 
 namespace lgh
 {
-
-// ---------------------------------------------------------------------------
-// element kernel: y_e = B^T diag(D_e) B x_e
-//   MODE 0: x is an E-vector (or L2 vector), plain apply
-//   MODE 1: x gathered from an L-vector through `map`
-//   MODE 2: CG K1 (H1): d = z[map] + beta * d_old[map] (not stored); den
-//   MODE 3: CG K1 (L2, no map): d = r + beta*d_old, stored in place (element-local)
-// ---------------------------------------------------------------------------
-struct MassArgs
-{
-   int NE;
-   const double *B;   // [q + Q*d]
-   const double *Dq;  // [q + NQ*e] - mass_apply_l2_plane: value(q, e) = Dq[q + dqs e] * Se[e] (mass_data)
-   const double *Se;
-   int dqs;
-   const double *M1;  // mass_apply_l2_kron: the 1-D mass tile of the L2 basis (L x L)
-   const double *w1;  // mass_apply_l2_plane<.., SEP = true>: one-dimensional weights, value(q, e) = Se[e] w1[qx] w1[qy] w1[qz] (compact data of a tensor-product rule)
-   const double *x;   // MODE 0/1 input; MODE 2/3: z (H1) or r (L2)
-   const int *map;    // NE*ND or null
-   double *y;         // E-vector (H1) or L2 vector output
-   // CG
-   double *d;         // direction vector (read; MODE 3 also writes it in place)
-   CgScalars *cgs;
-   double *partials;
-   unsigned int *ticket;
-   int multi; // multi-GPU: den is all-reduced before any decision is taken on it
-   int iter;  // CG iteration this launch belongs to (several ranks: see cg_pending_update)
-   // mass_apply_l2_kron, fused update of the energy CG (round 6): MODE 3 with no_y does not store M d - MODE 4, the update of the
-   // same iteration, forms it again from d (the L2 mass matrix is block diagonal: M d of a zone needs that zone's d only) and
-   // updates ux (x) and ur (r) with it: ten vector passes per iteration become eight
-   int no_y;
-   double *ux, *ur;
-   // lockstep with the velocity CG on several ranks (lgh_common.hpp): the rank sums of this solve's two dot products travel with
-   // the velocity iteration's exchanges instead of in exchanges of their own
-   LockstepWords ls;        // MODE 3: the accumulator-word sets of the iteration before, own and peers': word kLsWord = that rank's (r, r)
-   int ls_on;               // 1: MODE 3 takes (r, r) from ls instead of cgs->rz; MODE 4 takes (d, M d) from ls_den_src
-   double *ls_den_mirror;   // MODE 3: the local (d, M d) also goes here (VcgScalars::den_e: behind the halo messages)
-   const double *ls_den_src;// MODE 4: the rank-summed (d, M d)
-   long long *ls_word_out;  // MODE 4: the local (r, r), as bits, into word kLsWord of the set the exchange after K2 sends
-};
-
-// lockstep: (r, r) of the iteration before = the ranks' values in rank order (own value between the lower and the higher peers)
-__device__ __forceinline__ double lockstep_rz(const LockstepWords &w)
-{
-   double rz = 0.0;
-   for (int p = 0; p < w.before; p++) { const double v = __longlong_as_double(w.peers[(size_t)p * kLsWordsPerSet + kLsWord]); rz = (p == 0) ? v : rz + v; }
-   {
-      const double v = __longlong_as_double(w.own[kLsWord]);
-      rz = (w.before == 0) ? v : rz + v;
-   }
-   for (int p = w.before; p < w.n_peers; p++) { rz += __longlong_as_double(w.peers[(size_t)p * kLsWordsPerSet + kLsWord]); }
-   return rz;
-}
-// ... and what the next kernel of the sequence does with it (cg_pending_update with the sum formed here): convergence looked at,
-// the outcome committed by one thread; returns true when the solve has converged
-__device__ __forceinline__ bool lockstep_pending_update(CgScalars *s, const int iter, const double rz, const bool commit)
-{
-   const bool conv = rz < 0.0 || rz <= s->r0;
-   if (commit)
-   {
-      __hip_atomic_store(&s->iters, iter - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (conv)
-      {
-         __hip_atomic_store(&s->done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-         __hip_atomic_store(&s->rz, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-         __hip_atomic_store(&s->den, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      else { __hip_atomic_store(&s->rz, rz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } // (the update of this iteration divides it by (d, M d))
-   }
-   return conv;
-}
-
-// Several ranks: the sums of den and (r, z) over the ranks complete outside the kernels that produce the
-// local parts, so the decisions they feed (breakdown, convergence, iteration count) are taken by the NEXT
-// kernel of the sequence instead of a single-thread kernel after every exchange: each workgroup evaluates the
-// same predicate on the same reduced values, and thread 0 of workgroup 0 also commits the outcome to the
-// state.  A commit only writes values under which the predicate stays true (done = 1, rz = den = 0: sums of
-// zeros stay zero in the exchanges of launches enqueued past convergence), so a thread that reads the
-// state after the commit decides like one that read it before.
-// K1 of iteration iter >= 2: outcome of the update of iteration iter - 1.
-__device__ __forceinline__ bool cg_pending_update(CgScalars *s, const int iter, const bool commit)
-{
-   const double rz = s->rz;
-   const bool conv = rz < 0.0 || rz <= s->r0;
-   if (commit)
-   {
-      // write-through stores: another XCD's L2 may hold the same line dirty (K1's last workgroup writes den / first)
-      __hip_atomic_store(&s->iters, iter - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (conv)
-      {
-         __hip_atomic_store(&s->done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-         __hip_atomic_store(&s->rz, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-         __hip_atomic_store(&s->den, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-   }
-   return conv;
-}
-// K2: breakdown (den == 0 after the sum over the ranks), as upstream
-__device__ __forceinline__ bool cg_pending_den(CgScalars *s, const bool commit)
-{
-   const bool brk = s->den == 0.0;
-   if (brk && commit)
-   {
-      __hip_atomic_store(&s->done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&s->rz, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-   }
-   return brk;
-}
 
 template <int D, int Q, int NEB, int MODE>
 __global__ void __launch_bounds__(Q *Q *NEB)
@@ -892,6 +767,29 @@ static int l2_mass_kernel(lgh_ctx *c, int *form, int *compact)
 }
 int l2_mass_form(lgh_ctx *c, int *form, int *compact) { return l2_mass_kernel(c, form, compact); }
 
+// The Kronecker kernel in mode M (0 / 3: launch_mass, 4: the fused update of the energy CG), zones per workgroup by L.
+// L = 5 (round 6): ten, so that every thread has ONE row of a stage (25 rows per zone) and five workgroups fit a CU's LDS,
+// instead of sixteen (400 rows: a second round with 144 of 256 threads, three workgroups per CU): 53 -> 46 us per apply at
+// config 5, the leg 501 -> 534 (profiles/r6_l2_neb.txt); at L = 3 the same choice (28 zones instead of 64) changes nothing.
+// LGH_L2_NEB=0: sixteen.
+template <int M> static void launch_l2_kron(lgh_ctx *c, const MassArgs &a)
+{
+#define LGH_L2K(L_, NEB_) hipLaunchKernelGGL((mass_apply_l2_kron<L_, NEB_, M>), dim3(ceil_div(c->NE, NEB_)), dim3(256), 0, c->stream, a)
+   if (l2_one_round(c)) { LGH_L2K(5, 10); }
+   else
+   {
+      switch (c->L1D)
+      {
+         case 1: LGH_L2K(1, 256); break;
+         case 2: LGH_L2K(2, 128); break;
+         case 3: LGH_L2K(3, 64); break;
+         case 4: LGH_L2K(4, 32); break;
+         default: LGH_L2K(5, 16); break;
+      }
+   }
+#undef LGH_L2K
+}
+
 template <int MODE> static int launch_mass(lgh_ctx *c, int space, const MassArgs &a0)
 {
    const MassArgs &a = a0;
@@ -916,30 +814,10 @@ template <int MODE> static int launch_mass(lgh_ctx *c, int space, const MassArgs
       MassArgs a = a0;
       const int rc_md = mass_data(c, &a.Dq, &a.dqs, &a.Se);
       if (rc_md) { return rc_md; }
-      {
-         constexpr int M = (MODE == 3 ? 3 : 0);
-         a.M1 = c->M1l;
-#define LGH_L2K(L_, NEB_) hipLaunchKernelGGL((mass_apply_l2_kron<L_, NEB_, M>), dim3(ceil_div(c->NE, NEB_)), dim3(256), 0, c->stream, a)
-         // zones per workgroup.  L = 5 (round 6): ten, so that every thread has ONE row of a stage (25 rows per zone) and five
-         // workgroups fit a CU's LDS, instead of sixteen (400 rows: a second round with 144 of 256 threads, three workgroups per
-         // CU): 53 -> 46 us per apply at config 5, the leg 501 -> 534 (profiles/r6_l2_neb.txt); at L = 3 the same choice (28
-         // zones instead of 64) changes nothing.  LGH_L2_NEB=0: sixteen.
-         if (l2_one_round(c)) { LGH_L2K(5, 10); }
-         else
-         {
-            switch (c->L1D)
-            {
-               case 1: LGH_L2K(1, 256); break;
-               case 2: LGH_L2K(2, 128); break;
-               case 3: LGH_L2K(3, 64); break;
-               case 4: LGH_L2K(4, 32); break;
-               default: LGH_L2K(5, 16); break;
-            }
-         }
-#undef LGH_L2K
-         LGH_HIP_CHECK(hipGetLastError());
-         return LGH_OK;
-      }
+      a.M1 = c->M1l;
+      launch_l2_kron<(MODE == 3 ? 3 : 0)>(c, a);
+      LGH_HIP_CHECK(hipGetLastError());
+      return LGH_OK;
    }
    if (l2form == 1)
    {
@@ -987,14 +865,6 @@ template <int MODE> static int launch_mass(lgh_ctx *c, int space, const MassArgs
    LGH_HIP_CHECK(hipGetLastError());
    return LGH_OK;
 }
-
-// The energy CG's update as a second launch of the Kronecker kernel (MODE 4) instead of cg_update_k: when the L2 apply runs in
-// its Kronecker form.  LGH_L2_FUSED=0: cg_update_k reads the stored product (rounds 1-5).
-static bool l2_fused_update(lgh_ctx *c)
-{
-   int form = 0, compact = 0;
-   return c->sw.l2_fused && l2_mass_kernel(c, &form, &compact) == LGH_OK && form == 2;
-}
 // D[q, e] = W[q] s_e ?  In exact arithmetic the data of laghos_assembly.cpp:92-95, w_q detJ0(x_q) rho0(x_q), has this
 // form whenever the initial element is affine and rho0 constant in it; the stored entries carry the rounding of the
 // Jacobian and density evaluation at each point (measured: 220 ulp at Q3Q2 on the 8^3 box mesh, it grows like 1 / h).
@@ -1037,7 +907,7 @@ int mass_data(lgh_ctx *c, const double **Dq, int *dqs, const double **Se)
    return LGH_OK;
 }
 
-static MassArgs base_args(lgh_ctx *c, int space)
+MassArgs base_args(lgh_ctx *c, int space)
 {
    MassArgs a;
    memset(&a, 0, sizeof(a));
@@ -1045,6 +915,30 @@ static MassArgs base_args(lgh_ctx *c, int space)
    a.B = (space == LGH_SPACE_H1) ? c->B : c->Bl;
    a.Dq = c->massD; // (every kernel but mass_apply_l2_plane reads the stored table; launch_mass fills Se / dqs)
    return a;
+}
+
+int mass_apply_cg(lgh_ctx *c, int space, const MassArgs &m)
+{
+   return (space == LGH_SPACE_H1) ? launch_mass<2>(c, space, m) : launch_mass<3>(c, space, m);
+}
+bool l2_fused_update(lgh_ctx *c)
+{
+   int form = 0, compact = 0;
+   return c->sw.l2_fused && l2_mass_kernel(c, &form, &compact) == LGH_OK && form == 2;
+}
+int mass_l2_fused_update(lgh_ctx *c, const MassArgs &m, double *ux, double *ur, double *partials, unsigned int *ticket)
+{
+   MassArgs a = m;
+   const int rc = mass_data(c, &a.Dq, &a.dqs, &a.Se);
+   if (rc) { return rc; }
+   a.M1 = c->M1l;
+   a.ux = ux;
+   a.ur = ur;
+   a.partials = partials;
+   a.ticket = ticket;
+   launch_l2_kron<4>(c, a);
+   LGH_HIP_CHECK(hipGetLastError());
+   return LGH_OK;
 }
 
 int mass_apply_E(lgh_ctx *c, int space, const double *xE, double *yE)
@@ -1083,6 +977,13 @@ mass_gather_k(const int N, const int deg, const int *__restrict__ ell,
    y[n] = s;
 }
 
+int mass_gather(lgh_ctx *c, const double *YE, const uint8_t *ess, double *y)
+{
+   hipLaunchKernelGGL(mass_gather_k, dim3(ceil_div(c->N, 256)), dim3(256), 0, c->stream, c->N, c->t_deg, c->t_ell, YE, ess, y);
+   LGH_HIP_CHECK(hipGetLastError());
+   return LGH_OK;
+}
+
 int mass_apply_h1(lgh_ctx *c, const double *x, double *y, bool eliminate)
 {
    MassArgs a = base_args(c, LGH_SPACE_H1);
@@ -1093,9 +994,8 @@ int mass_apply_h1(lgh_ctx *c, const double *x, double *y, bool eliminate)
    if (rc) { return rc; }
    const bool multi = (c->multi != 0);
    const uint8_t *ess = (eliminate && c->cur_ess >= 0 && !multi) ? c->essmask[c->cur_ess] : nullptr;
-   hipLaunchKernelGGL(mass_gather_k, dim3(ceil_div(c->N, 256)), dim3(256), 0, c->stream, c->N,
-                      c->t_deg, c->t_ell, c->YE, ess, y);
-   LGH_HIP_CHECK(hipGetLastError());
+   rc = mass_gather(c, c->YE, ess, y);
+   if (rc) { return rc; }
    if (multi)
    {
       rc = halo_sum(c, y, 1);
@@ -1173,12 +1073,11 @@ int mass_assemble_diag(lgh_ctx *c)
                          c->D1D, c->Q1D, c->B, c->massD, c->YE);
    }
    LGH_HIP_CHECK(hipGetLastError());
-   hipLaunchKernelGGL(mass_gather_k, dim3(ceil_div(c->N, 256)), dim3(256), 0, c->stream, c->N,
-                      c->t_deg, c->t_ell, c->YE, (const uint8_t *)nullptr, c->diagV);
-   LGH_HIP_CHECK(hipGetLastError());
+   int rc = mass_gather(c, c->YE, nullptr, c->diagV);
+   if (rc) { return rc; }
    if (c->multi != 0)
    {
-      int rc = halo_sum(c, c->diagV, 1);
+      rc = halo_sum(c, c->diagV, 1);
       if (rc) { return rc; }
    }
    hipLaunchKernelGGL(reciprocal_k, dim3(ceil_div(c->N, 256)), dim3(256), 0, c->stream, c->N,
@@ -1187,561 +1086,5 @@ int mass_assemble_diag(lgh_ctx *c)
    c->mass_gen++; // (the velocity solve keeps 1/diag in its own node numbering: lgh_vcg.hip)
    return LGH_OK;
 }
-
-// ---------------------------------------------------------------------------
-// CG node / vector kernels
-// ---------------------------------------------------------------------------
-struct CgVecArgs
-{
-   int n;              // N (H1) or L2V
-   const int *ell;     // H1 fused gather (ELL transpose; null: y already an L-vector)
-   int deg;
-   const double *YE;   // E-vector from K1 (H1) ...
-   double *yL;         // ... or the operator result as an L-vector (L2, multi-GPU H1, atomics)
-   int d_in_place;     // 1: d already holds the new direction (L2); 0: form z + beta d here
-   const uint8_t *ess; // essential mask or null
-   const double *dinv; // Jacobi (null: no preconditioner)
-   const double *owner;// ownership weights or null
-   const double *b;
-   double *d;
-   double *x, *r, *z;
-   CgScalars *cgs;
-   double *partials;
-   unsigned int *ticket;
-   int iter;
-   int allreduce_pending; // multi-GPU: the scalar fold is finished by a later kernel
-};
-
-// init: r = b - A x (A x supplied in yL/YE, or absent when x == 0), z = M^-1 r,
-// nom = (z, r); sets r0, done, rz.
-template <bool HAVE_AX>
-__global__ void __launch_bounds__(256)
-cg_init_k(const CgVecArgs a)
-{
-   __shared__ double red[16];
-   const int n = blockIdx.x * blockDim.x + threadIdx.x;
-   double part = 0.0;
-   if (n < a.n)
-   {
-      double rv = a.b[n];
-      if (HAVE_AX) { rv -= a.yL[n]; }
-      a.r[n] = rv;
-      double zv = rv;
-      if (a.dinv)
-      {
-         zv = rv * a.dinv[n];
-         a.z[n] = zv;
-      }
-      part = (a.owner ? a.owner[n] : 1.0) * zv * rv;
-   }
-   const double bsum = block_sum(part, red);
-   double total;
-   if (grid_sum_last_block(bsum, a.partials, a.ticket, red, total))
-   {
-      if (threadIdx.x == 0)
-      {
-         CgScalars *s = a.cgs;
-         s->rz = total;
-         s->rz_prev = total;
-         s->nom0 = total;
-         s->iters = 0;
-         s->first = 1;
-         if (!a.allreduce_pending)
-         {
-            s->r0 = fmax(total * s->rel_tol2, 0.0);
-            s->done = (total < 0.0 || total <= s->r0) ? 1 : 0;
-         }
-      }
-   }
-}
-
-// multi-GPU: after the all-reduce of rz (init) finish the scalar bookkeeping
-__global__ void cg_init_finish_k(CgScalars *s)
-{
-   s->rz_prev = s->rz;
-   s->nom0 = s->rz;
-   s->r0 = fmax(s->rz * s->rel_tol2, 0.0);
-   s->done = (s->rz < 0.0 || s->rz <= s->r0) ? 1 : 0;
-}
-
-// K2: see file header.
-// U nodes per thread with every load of all U nodes issued before first use: the
-// kernel is pure memory latency (PMC: 90 % of wave cycles waiting), so the number
-// of independent loads in flight per lane is what sets its speed.
-constexpr int kUpdU = 2;
-template <bool FUSED_GATHER, int DEG>
-__global__ void __launch_bounds__(256)
-cg_update_k(const CgVecArgs a)
-{
-   __shared__ double red[16];
-   if (a.cgs->done) { return; }
-   if (a.allreduce_pending && cg_pending_den(a.cgs, blockIdx.x == 0 && threadIdx.x == 0)) { return; }
-   const double alpha = a.cgs->rz / a.cgs->den;
-   // `first` was cleared by K1 of this iteration: iteration 1 is recognised by iter
-   const bool it1 = (a.iter == 1);
-   const double beta = it1 ? 0.0 : a.cgs->rz / a.cgs->rz_prev;
-   const int base = blockIdx.x * (256 * kUpdU) + threadIdx.x;
-   int n[kUpdU];
-   bool ok[kUpdU];
-#pragma unroll
-   for (int k = 0; k < kUpdU; k++)
-   {
-      n[k] = base + 256 * k;
-      ok[k] = n[k] < a.n;
-      if (!ok[k]) { n[k] = a.n - 1; }
-   }
-   // ---- phase 1: issue all independent loads
-   int pidx[kUpdU][DEG > 0 ? DEG : 1];
-   if (FUSED_GATHER)
-   {
-#pragma unroll
-      for (int k = 0; k < kUpdU; k++)
-#pragma unroll
-         for (int j = 0; j < DEG; j++) { pidx[k][j] = (j < a.deg) ? a.ell[(size_t)j * a.n + n[k]] : -1; }
-   }
-   double zold[kUpdU], dold[kUpdU], xo[kUpdU], ro[kUpdU], di[kUpdU], ow[kUpdU], zv[kUpdU];
-   bool es[kUpdU];
-#pragma unroll
-   for (int k = 0; k < kUpdU; k++)
-   {
-      ro[k] = a.r[n[k]];
-      xo[k] = a.x[n[k]];
-      di[k] = a.dinv ? a.dinv[n[k]] : 1.0;
-      zold[k] = a.dinv ? a.z[n[k]] : ro[k];
-      dold[k] = (a.d_in_place || !it1) ? a.d[n[k]] : 0.0;
-      ow[k] = a.owner ? a.owner[n[k]] : 1.0;
-      es[k] = a.ess ? (a.ess[n[k]] != 0) : false;
-      if (!FUSED_GATHER) { zv[k] = a.yL[n[k]]; }
-   }
-   // ---- phase 2: dependent E-vector reads
-   if (FUSED_GATHER)
-   {
-      double ye[kUpdU][DEG > 0 ? DEG : 1];
-#pragma unroll
-      for (int k = 0; k < kUpdU; k++)
-#pragma unroll
-         for (int j = 0; j < DEG; j++) { ye[k][j] = (pidx[k][j] >= 0) ? a.YE[pidx[k][j]] : 0.0; }
-#pragma unroll
-      for (int k = 0; k < kUpdU; k++)
-      {
-         // ascending contribution order, skipping absent slots (same sum as the CSR loop)
-         double s = 0.0;
-#pragma unroll
-         for (int j = 0; j < DEG; j++) { if (pidx[k][j] >= 0) { s += ye[k][j]; } }
-         zv[k] = s;
-      }
-   }
-   // ---- phase 3: updates
-   double part = 0.0;
-#pragma unroll
-   for (int k = 0; k < kUpdU; k++)
-   {
-      if (!ok[k]) { continue; }
-      const double z_ = es[k] ? 0.0 : zv[k];
-      double dv;
-      if (a.d_in_place) { dv = dold[k]; }
-      else
-      {
-         // same expression as K1's gather: d = z_old + beta * d_old
-         dv = zold[k];
-         if (!it1) { dv += beta * dold[k]; }
-         a.d[n[k]] = dv;
-      }
-      const double xv = xo[k] + alpha * dv;
-      const double rv = ro[k] - alpha * z_;
-      a.x[n[k]] = xv;
-      a.r[n[k]] = rv;
-      double pz = rv;
-      if (a.dinv)
-      {
-         pz = rv * di[k];
-         a.z[n[k]] = pz;
-      }
-      part += ow[k] * rv * pz;
-   }
-   const double bsum = block_sum(part, red);
-   double total;
-   if (grid_sum_last_block(bsum, a.partials, a.ticket, red, total))
-   {
-      if (threadIdx.x == 0)
-      {
-         CgScalars *s = a.cgs;
-         s->rz_prev = s->rz;
-         s->rz = total; // betanom
-         if (!a.allreduce_pending)
-         {
-            s->iters = a.iter;
-            if (total < 0.0 || total <= s->r0) { s->done = 1; }
-         }
-      }
-   }
-}
-// (several ranks) a finished solve leaves rz = den = 0: the exchanges of the launches the host enqueued past
-// convergence then sum zeros instead of multiplying the global values by the number of ranks each time
-__global__ void cg_update_finish_k(CgScalars *s, int iter)
-{
-   if (s->done) { s->rz = 0.0; s->den = 0.0; return; }
-   s->iters = iter;
-   if (s->rz < 0.0 || s->rz <= s->r0) { s->done = 1; s->rz = 0.0; s->den = 0.0; }
-}
-
-__global__ void cg_set_tol_k(CgScalars *s, double rel_tol2)
-{
-   s->rel_tol2 = rel_tol2;
-   s->done = 0;
-   s->first = 1;
-   s->iters = 0;
-}
-
-static int launch_l2_update(lgh_ctx *c, const MassArgs &m, const CgVecArgs &v)
-{
-   MassArgs a = m;
-   const int rc = mass_data(c, &a.Dq, &a.dqs, &a.Se);
-   if (rc) { return rc; }
-   a.M1 = c->M1l;
-   a.ux = v.x;
-   a.ur = v.r;
-   a.partials = v.partials;
-   a.ticket = v.ticket;
-   a.iter = v.iter;
-#define LGH_L2U(L_, NEB_) hipLaunchKernelGGL((mass_apply_l2_kron<L_, NEB_, 4>), dim3(ceil_div(c->NE, NEB_)), dim3(256), 0, c->stream, a)
-   if (l2_one_round(c)) { LGH_L2U(5, 10); }
-   else
-   {
-      switch (c->L1D)
-      {
-         case 1: LGH_L2U(1, 256); break;
-         case 2: LGH_L2U(2, 128); break;
-         case 3: LGH_L2U(3, 64); break;
-         case 4: LGH_L2U(4, 32); break;
-         default: LGH_L2U(5, 16); break;
-      }
-   }
-#undef LGH_L2U
-   LGH_HIP_CHECK(hipGetLastError());
-   return LGH_OK;
-}
-
-int cg_solve(lgh_ctx *c, int space, const double *b, double *x, double rel_tol, int max_iter,
-             int *iters, bool x_is_zero)
-{
-   const bool h1 = (space == LGH_SPACE_H1);
-   const int n = h1 ? c->N : c->L2V;
-   const bool multi = (c->multi != 0);
-   int rc;
-   hipLaunchKernelGGL(cg_set_tol_k, dim3(1), dim3(1), 0, c->stream, c->cgs, rel_tol * rel_tol);
-
-   CgVecArgs v;
-   memset(&v, 0, sizeof(v));
-   v.n = n;
-   v.b = b;
-   v.x = x;
-   v.r = c->cg_r;
-   v.z = h1 ? c->cg_z : c->cg_r; // no preconditioner: z aliases r
-   v.dinv = h1 ? c->dinvV : nullptr;
-   v.owner = (h1 && multi) ? c->owner : nullptr;
-   v.cgs = c->cgs;
-   v.partials = c->partials;
-   v.ticket = c->tickets;
-   v.allreduce_pending = multi ? 1 : 0;
-   const uint8_t *ess = (h1 && c->cur_ess >= 0) ? c->essmask[c->cur_ess] : nullptr;
-   const int nb = ceil_div(n, 256);
-   const int nbu = ceil_div(n, 256 * kUpdU);
-
-   // --- r = b - A x  (iterative_mode for H1; L2 starts from x = 0: solvers.cpp)
-   if (!h1) { rc = vec_set(c, x, 0.0, n); if (rc) { return rc; } x_is_zero = true; }
-   if (!x_is_zero)
-   {
-      rc = mass_apply_h1(c, x, c->cg_y, true);
-      if (rc) { return rc; }
-      v.yL = c->cg_y;
-      hipLaunchKernelGGL(cg_init_k<true>, dim3(nb), dim3(256), 0, c->stream, v);
-   }
-   else { hipLaunchKernelGGL(cg_init_k<false>, dim3(nb), dim3(256), 0, c->stream, v); }
-   LGH_HIP_CHECK(hipGetLastError());
-   if (multi)
-   {
-      rc = allreduce_dev(c, &c->cgs->rz, 1, 0);
-      if (rc) { return rc; }
-      hipLaunchKernelGGL(cg_init_finish_k, dim3(1), dim3(1), 0, c->stream, c->cgs);
-   }
-
-   MassArgs m = base_args(c, space);
-   m.x = h1 ? c->cg_z : c->cg_r;
-   m.map = h1 ? c->h1map : nullptr;
-   m.y = h1 ? c->YE : c->cg_y;
-   m.cgs = c->cgs;
-   m.partials = c->partials + c->part_stride;
-   m.ticket = c->tickets + 1 * kTicketSlot;
-   m.multi = multi ? 1 : 0;
-
-   m.d = c->cg_d0;
-   v.d = c->cg_d0;
-   v.d_in_place = h1 ? 0 : 1;
-   m.no_y = (!h1 && l2_fused_update(c)) ? 1 : 0;
-   int it = 0;
-   CgScalars *hs = (CgScalars *)c->host_pinned;
-   // chunk = iterations enqueued between two looks at the convergence flag.  The
-   // iteration count of a mass solve barely changes from one RK stage to the next,
-   // so the first chunk is the previous count for this (space, component): the
-   // common case costs two host round trips and no wasted launches; kernels
-   // enqueued past convergence exit on the device-side `done` flag.
-   int &last = c->cg_last_iters[h1 ? 0 : 1][(h1 && c->cur_ess >= 0) ? c->cur_ess : 0];
-   int chunk = last > 0 ? last : 8;
-   bool done = false;
-   bool first_look = true;
-   int looks = 0;
-   while (!done)
-   {
-      // several ranks: the outcome of the last enqueued update is still pending (cg_pending_update) - commit it
-      if (multi && it > 0) { hipLaunchKernelGGL(cg_update_finish_k, dim3(1), dim3(1), 0, c->stream, c->cgs, it); }
-      LGH_HIP_CHECK(hipMemcpyAsync(hs, c->cgs, sizeof(CgScalars), hipMemcpyDeviceToHost, c->stream));
-      LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
-      if (hs->done || it >= max_iter) { break; }
-      // after the first chunk (the previous solve's count): two more iterations per look while the count only creeps, then
-      // doubling - a solve whose count jumps (the unpreconditioned L2 CG of the first steps at order 4: 225 -> 300) must not pay
-      // a host look every two iterations (round 6: 149 looks per RK step at config 5); launches past convergence return at once
-      if (!first_look) { chunk = (++looks <= 2) ? 2 : std::min(64, 2 * chunk); }
-      first_look = false;
-      const int upto = std::min(max_iter, it + chunk);
-      for (; it < upto;)
-      {
-         ++it;
-         m.iter = it;
-         kt_begin(c, h1 ? LGH_KERNEL_MASS_CG_H1 : LGH_KERNEL_MASS_CG_L2);
-         rc = h1 ? launch_mass<2>(c, space, m) : launch_mass<3>(c, space, m);
-         kt_end(c, h1 ? LGH_KERNEL_MASS_CG_H1 : LGH_KERNEL_MASS_CG_L2);
-         if (rc) { return rc; }
-         v.iter = it;
-         v.ess = ess;
-         if (h1 && !multi)
-         {
-            v.ell = c->t_ell;
-            v.deg = c->t_deg;
-            v.YE = c->YE;
-            kt_begin(c, LGH_KERNEL_CG_UPDATE_H1);
-            if (c->t_deg <= 4) { hipLaunchKernelGGL((cg_update_k<true, 4>), dim3(nbu), dim3(256), 0, c->stream, v); }
-            else if (c->t_deg <= 8) { hipLaunchKernelGGL((cg_update_k<true, 8>), dim3(nbu), dim3(256), 0, c->stream, v); }
-            else
-            {
-               // unusual valence (not a tensor-product mesh): unfused gather, then update
-               hipLaunchKernelGGL(mass_gather_k, dim3(nb), dim3(256), 0, c->stream, c->N, c->t_deg,
-                                  c->t_ell, c->YE, (const uint8_t *)nullptr, c->cg_y);
-               v.yL = c->cg_y;
-               hipLaunchKernelGGL((cg_update_k<false, 0>), dim3(nbu), dim3(256), 0, c->stream, v);
-            }
-            kt_end(c, LGH_KERNEL_CG_UPDATE_H1);
-         }
-         else
-         {
-            if (h1)
-            {
-               // multi-GPU: assemble the L-vector, sum shared nodes, reduce den
-               hipLaunchKernelGGL(mass_gather_k, dim3(nb), dim3(256), 0, c->stream, c->N, c->t_deg,
-                                  c->t_ell, c->YE, (const uint8_t *)nullptr, c->cg_y);
-               rc = halo_sum(c, c->cg_y, 1);
-               if (rc) { return rc; }
-            }
-            if (multi)
-            {
-               rc = allreduce_dev(c, &c->cgs->den, 1, 0); // breakdown is looked at by cg_update_k (cg_pending_den)
-               if (rc) { return rc; }
-            }
-            v.yL = c->cg_y;
-            if (!h1 && m.no_y) { rc = launch_l2_update(c, m, v); if (rc) { return rc; } } // (the update forms M d of its zones itself)
-            else { hipLaunchKernelGGL((cg_update_k<false, 0>), dim3(nbu), dim3(256), 0, c->stream, v); }
-            if (multi)
-            {
-               rc = allreduce_dev(c, &c->cgs->rz, 1, 0); // convergence is looked at by the next K1 (cg_pending_update)
-               if (rc) { return rc; }
-            }
-         }
-         LGH_HIP_CHECK(hipGetLastError());
-      }
-   }
-   // upstream: final_iter = max_iter when the loop runs out without converging
-   int fin = hs->iters;
-   if (!hs->done && it >= max_iter) { fin = max_iter; }
-   last = fin;
-   if (iters) { *iters = fin; }
-   return LGH_OK;
-}
-
-// ---- the L2 (energy) solve split into an enqueue-only half and a completing half -----
-// SolveEnergy (laghos_solver.cpp:400-493) needs only the quadrature data and the
-// velocity block of S - not the result of SolveVelocity.  lgh_solve_energy_begin
-// enqueues F^T v and the first chunk of CG iterations on the context's second stream
-// (the caller swaps the stream in), the velocity solve then runs on the main stream
-// with its host round trips, and lgh_solve_energy_end looks at the convergence flag.
-// Same kernels, same order and same scalars as cg_solve(LGH_SPACE_L2): the iterates
-// are identical, only the initial look (rhs == 0) is folded into the first one.
-struct L2Run
-{
-   CgVecArgs v;
-   MassArgs m;
-   int it, max_iter, nbu;
-   bool active;
-};
-
-static int l2_enqueue(lgh_ctx *c, L2Run *r, int upto)
-{
-   for (; r->it < upto;)
-   {
-      ++r->it;
-      r->m.iter = r->it;
-      int rc = launch_mass<3>(c, LGH_SPACE_L2, r->m);
-      if (rc) { return rc; }
-      if (r->m.multi) { rc = allreduce_dev(c, &c->cgs->den, 1, 0); if (rc) { return rc; } } // as cg_solve
-      r->v.iter = r->it;
-      if (r->m.no_y) { rc = launch_l2_update(c, r->m, r->v); if (rc) { return rc; } }
-      else { hipLaunchKernelGGL((cg_update_k<false, 0>), dim3(r->nbu), dim3(256), 0, c->stream, r->v); }
-      LGH_HIP_CHECK(hipGetLastError());
-      if (r->m.multi) { rc = allreduce_dev(c, &c->cgs->rz, 1, 0); if (rc) { return rc; } }
-   }
-   return LGH_OK;
-}
-
-static int cg_l2_begin_impl(lgh_ctx *c, const double *b, double *x, double rel_tol, int max_iter, const bool enqueue)
-{
-   const bool multi = c->multi != 0; // several ranks: the caller has checked that the second stream has a communicator
-   if (!c->l2run) { c->l2run = new L2Run(); }
-   L2Run *r = (L2Run *)c->l2run;
-   const int n = c->L2V;
-   hipLaunchKernelGGL(cg_set_tol_k, dim3(1), dim3(1), 0, c->stream, c->cgs, rel_tol * rel_tol);
-   CgVecArgs &v = r->v;
-   memset(&v, 0, sizeof(v));
-   v.n = n;
-   v.b = b;
-   v.x = x;
-   v.r = c->cg_r;
-   v.z = c->cg_r; // no preconditioner: z aliases r
-   v.cgs = c->cgs;
-   v.partials = c->partials;
-   v.ticket = c->tickets;
-   v.allreduce_pending = multi ? 1 : 0;
-   int rc = vec_set(c, x, 0.0, n); // the L2 solve starts from x = 0
-   if (rc) { return rc; }
-   hipLaunchKernelGGL(cg_init_k<false>, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, v);
-   LGH_HIP_CHECK(hipGetLastError());
-   if (multi)
-   {
-      rc = allreduce_dev(c, &c->cgs->rz, 1, 0);
-      if (rc) { return rc; }
-      hipLaunchKernelGGL(cg_init_finish_k, dim3(1), dim3(1), 0, c->stream, c->cgs);
-   }
-   MassArgs &m = r->m;
-   m = base_args(c, LGH_SPACE_L2);
-   m.x = c->cg_r;
-   m.map = nullptr;
-   m.y = c->cg_y;
-   m.cgs = c->cgs;
-   m.partials = c->partials + c->part_stride;
-   m.ticket = c->tickets + 1 * kTicketSlot;
-   m.multi = multi ? 1 : 0;
-   m.d = c->cg_d0;
-   v.d = c->cg_d0;
-   v.d_in_place = 1;
-   v.yL = c->cg_y;
-   m.no_y = l2_fused_update(c) ? 1 : 0;
-   r->it = 0;
-   r->max_iter = max_iter;
-   r->nbu = ceil_div(n, 256 * kUpdU);
-   r->active = true;
-   const int last = c->cg_last_iters[1][0];
-   if (!enqueue) { return LGH_OK; } // (lockstep: the velocity solve interleaves the iterations)
-   return l2_enqueue(c, r, std::min(max_iter, last > 0 ? last : 8));
-}
-int cg_l2_begin(lgh_ctx *c, const double *b, double *x, double rel_tol, int max_iter) { return cg_l2_begin_impl(c, b, x, rel_tol, max_iter, true); }
-
-// ---- lockstep with the velocity CG (lgh_common.hpp): set-up and initial residual here, one iteration per velocity
-// iteration from inside vcg_solve (apply behind K1, update behind K2), the rest - if any - by cg_l2_end as before
-bool l2_lockstep_possible(lgh_ctx *c) { return l2_fused_update(c); }
-int l2_lockstep_limit(lgh_ctx *c)
-{
-   const L2Run *r = (const L2Run *)c->l2run;
-   const int last = c->cg_last_iters[1][0];
-   const int want = last > 0 ? last : 8;
-   return (r && r->active) ? std::min(want, r->max_iter) : 0; // (never past the cap this solve was given)
-}
-int cg_l2_begin_lockstep(lgh_ctx *c, const double *b, double *x, double rel_tol, int max_iter) { return cg_l2_begin_impl(c, b, x, rel_tol, max_iter, false); }
-int l2_lockstep_apply(lgh_ctx *c, int it, const LockstepWords &prev, double *den_mirror)
-{
-   L2Run *r = (L2Run *)c->l2run;
-   if (!r || !r->active || !r->m.no_y || it != r->it + 1 || it > r->max_iter) { set_error("l2_lockstep_apply: no energy solve set up for iteration %d", it); return LGH_ERR_ARG; }
-   ++r->it;
-   r->m.iter = r->it;
-   r->m.ls = prev;
-   r->m.ls_on = 1;
-   r->m.ls_den_mirror = den_mirror;
-   return launch_mass<3>(c, LGH_SPACE_L2, r->m);
-}
-int l2_lockstep_update(lgh_ctx *c, int it, const double *den_src, long long *word_out)
-{
-   L2Run *r = (L2Run *)c->l2run;
-   if (!r || !r->active || it != r->it) { set_error("l2_lockstep_update: iteration %d has no apply", it); return LGH_ERR_ARG; }
-   r->v.iter = r->it;
-   MassArgs m = r->m;
-   m.ls_on = 1;
-   m.ls_den_src = den_src;
-   m.ls_word_out = word_out;
-   return launch_l2_update(c, m, r->v);
-}
-__global__ void l2_lockstep_fold_k(CgScalars *s, const int it, const LockstepWords w)
-{
-   if (s->done) { return; }
-   (void)lockstep_pending_update(s, it + 1, lockstep_rz(w), true); // what the apply of iteration it + 1 would commit
-}
-int l2_lockstep_fold(lgh_ctx *c, int it, const LockstepWords &last)
-{
-   L2Run *r = (L2Run *)c->l2run;
-   if (!r || !r->active || it != r->it) { set_error("l2_lockstep_fold: iteration %d is not the last one enqueued", it); return LGH_ERR_ARG; }
-   hipLaunchKernelGGL(l2_lockstep_fold_k, dim3(1), dim3(1), 0, c->stream, c->cgs, it, last);
-   LGH_HIP_CHECK(hipGetLastError());
-   return LGH_OK;
-}
-int cg_l2_end(lgh_ctx *c, int *iters);
-int cg_l2_end_lockstep(lgh_ctx *c, int *iters)
-{
-   L2Run *r = (L2Run *)c->l2run;
-   if (!r || !r->active) { return LGH_ERR_ARG; }
-   r->m.ls_on = 0; // (from here on the solve reduces its scalars itself: the sequence of cg_solve)
-   r->m.ls_den_mirror = nullptr;
-   const int inside = r->it;
-   const int rc = cg_l2_end(c, iters);
-   c->ls_stats[0] += 1;
-   c->ls_stats[1] += inside;
-   c->ls_stats[2] += r->it - inside;
-   return rc;
-}
-
-int cg_l2_end(lgh_ctx *c, int *iters)
-{
-   L2Run *r = (L2Run *)c->l2run;
-   if (!r || !r->active) { return LGH_ERR_ARG; }
-   CgScalars *hs = (CgScalars *)c->host_pinned;
-   int looks = 0, chunk = 2;
-   while (true)
-   {
-      if (r->m.multi && r->it > 0) { hipLaunchKernelGGL(cg_update_finish_k, dim3(1), dim3(1), 0, c->stream, c->cgs, r->it); } // as cg_solve
-      LGH_HIP_CHECK(hipMemcpyAsync(hs, c->cgs, sizeof(CgScalars), hipMemcpyDeviceToHost, c->stream));
-      LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
-      if (hs->done || r->it >= r->max_iter) { break; }
-      chunk = (++looks <= 2) ? 2 : std::min(64, 2 * chunk); // (as cg_solve: a count that jumps is not chased two iterations at a time)
-      const int rc = l2_enqueue(c, r, std::min(r->max_iter, r->it + chunk));
-      if (rc) { return rc; }
-   }
-   int fin = hs->iters;
-   if (!hs->done && r->it >= r->max_iter) { fin = r->max_iter; }
-   c->cg_last_iters[1][0] = fin;
-   if (iters) { *iters = fin; }
-   r->active = false;
-   return LGH_OK;
-}
-void cg_l2_free(lgh_ctx *c)
-{
-   delete (L2Run *)c->l2run;
-   c->l2run = nullptr;
-}
-
 
 } // namespace lgh

@@ -890,7 +890,7 @@ static int vcg_mode(lgh_ctx *c, VcgAux *aux, const VcgK1 &k1, const bool in_solv
    if (c->sw.halo_fused_pack && m.mixed && m.k2p && m.n_shared > 0 && comm_pack_tables(c, &hp))
    {
       m.pack_halo = 1;
-      m.nx_den = halo_can_piggyback(c) ? (c->e_lockstep ? kVC + 1 : kVC) : 0; // (lockstep energy CG: its (d, M d) rides along, VcgScalars::den_e)
+      m.nx_den = halo_can_piggyback(c) ? (c->energy.mode == EnergySolve::Lockstep ? kVC + 1 : kVC) : 0; // (lockstep energy CG: its (d, M d) rides along, VcgScalars::den_e)
       m.pack_rz = (halo_can_piggyback(c) && !m.rzl) ? 1 : 0; // (rz_limbs mode: (r, z) travels as accumulator words, exchange_words)
    }
    if (in_solve)
@@ -899,7 +899,7 @@ static int vcg_mode(lgh_ctx *c, VcgAux *aux, const VcgK1 &k1, const bool in_solv
       aux->ls_ready = (m.multi && aux->ls_all == 1 && m.ls_mine && m.rzl && (m.n_shared == 0 || (m.pack_halo && halo_can_piggyback(c)))) ? 1 : 0;
    }
    // the energy CG in lockstep (lgh_solve_energy_begin set it up on this stream): see vcg_iterate_exchange
-   m.ls = c->e_lockstep == 1 && m.multi && m.rzl && aux->ls_ready && (m.n_shared == 0 || m.nx_den == kVC + 1);
+   m.ls = c->energy.mode == EnergySolve::Lockstep && m.multi && m.rzl && aux->ls_ready && (m.n_shared == 0 || m.nx_den == kVC + 1);
    return LGH_OK;
 }
 
@@ -1099,7 +1099,7 @@ static int vcg_look(lgh_ctx *c, const VcgPlan &plan, VcgRun &r, bool &stop)
       LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
    }
    stop = r.hs->all_done || r.it >= r.max_iter;
-   if (!stop) { r.chunk = (++r.looks <= 2) ? 2 : std::min(64, 2 * r.chunk); } // (as cg_solve, lgh_mass.hip)
+   if (!stop) { r.chunk = (++r.looks <= 2) ? 2 : std::min(64, 2 * r.chunk); } // (as scg_finish, lgh_scg.hip)
    return LGH_OK;
 }
 
@@ -1130,7 +1130,7 @@ static int vcg_iterate_direct(lgh_ctx *c, const VcgPlan &plan, VcgArgs &a)
 // One iteration with A d as L-vectors between K1 and K2 - several ranks (only at the nodes shared with other ranks when K2
 // can gather the rest itself: mode.mixed), or one rank with an unusual valence: gather, (d, A d) folded, shared nodes and
 // (d, A d) summed across ranks, K2, (r, z) summed across ranks - as accumulator words or by an all-reduce.  The energy CG in
-// lockstep (mode.ls; lgh_mass.hip) runs one of its iterations per velocity iteration while it has some left of the count it
+// lockstep (mode.ls; lgh_scg.hip) runs one of its iterations per velocity iteration while it has some left of the count it
 // needed last time: apply behind K1, update behind K2, its (d, M d) on the halo messages (den_e), its (r, r) in a word of the
 // word exchange, and in its last interleaved iteration of a chunk (upto: where the chunk ends) its fold behind that exchange.
 static int vcg_iterate_exchange(lgh_ctx *c, const VcgPlan &plan, VcgArgs &a, const VcgRun &r, const int upto)
@@ -1239,7 +1239,7 @@ int vcg_solve(lgh_ctx *c, double *B, double *X, double rel_tol, int max_iter, in
    r.hs = (VcgScalars *)(c->host_pinned + kPinVcg);
    r.alias = (plan.aux->ord && plan.aux->o_alias.nodes) ? &plan.aux->o_alias : nullptr;
    r.max_iter = max_iter;
-   r.chunk = c->vcg_last > 0 ? c->vcg_last : 8; // first chunk = iteration count of the previous velocity solve (see cg_solve)
+   r.chunk = c->vcg_last > 0 ? c->vcg_last : 8; // first chunk = iteration count of the previous velocity solve (see cg_solve, lgh_scg.hip)
    r.ls_limit = m.ls ? std::min(l2_lockstep_limit(c), max_iter) : 0;
    r.ls_before = m.ls ? comm_ranks_before(c) : 0;
    LGH_VCG_TRY(vcg_start(c, plan, B, force_E));

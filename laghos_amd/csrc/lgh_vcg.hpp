@@ -14,7 +14,7 @@ constexpr int kTraceRec = 16; // debug (LGH_VCG_TRACE): 64-bit words per workgro
 struct VcgScalars
 {
    double rz[kVC], rz_prev[kVC], den[kVC];
-   double den_e;   // lockstep energy CG (lgh_mass.hip): its (d, M d), a fourth scalar right behind den[] - it rides on the halo messages with them
+   double den_e;   // lockstep energy CG (lgh_scg.hip): its (d, M d), a fourth scalar right behind den[] - it rides on the halo messages with them
    double r0[kVC];
    double rel_tol2;
    double alpha_last[kVC]; // vcg_update_p_k: alpha of the latest completed update of component c
@@ -26,7 +26,7 @@ struct VcgScalars
    double rzh[2][kVC];        // rz_limbs mode: (r, z) after iteration j in [j & 1], written by workgroup 0 of K1(j + 1)
 };
 
-// Several ranks (see cg_pending_update, lgh_mass.hip): the sums of den and (r, z) over the ranks complete between
+// Several ranks (see cg_pending_update, lgh_mass.hpp): the sums of den and (r, z) over the ranks complete between
 // the kernels, and the decisions they feed are taken by the next kernel of the sequence - every workgroup evaluates
 // the same predicate on the same reduced values, thread 0 of workgroup 0 also commits the outcome (write-through
 // stores; a commit only writes values under which the predicate stays true).

@@ -3,7 +3,7 @@
 and the 2D entries of tests/test_gpu_pipeline.py::MULTI_RANK_CASES.
 
 In 3D every velocity solve goes through the lockstep solver (lgh_vcg.hip); in 2D vcg_available() is false and
-lgh_solve_velocity runs the scalar cg_solve(LGH_SPACE_H1) of lgh_mass.hip once per component - whose several-rank branch
+lgh_solve_velocity runs the scalar cg_solve(LGH_SPACE_H1) of lgh_scg.hip once per component - whose several-rank branch
 (rank-summed (r, z) and (d, A d), looked at by the NEXT kernel of the sequence) no 3D run reaches.
 
 Every rank holds a block of 13 x 5 zones.  65 is ragged against the 2D batches of 16, 7 and 4 zones (Q2Q1, Q3Q2, Q4Q3);

@@ -360,7 +360,7 @@ def test_multi_rank_code_path_on_one_gpu():
 
 
 def test_multi_rank_code_path_on_one_gpu_2d():
-    """... and in 2D (data/square01_quad.mesh -rs 2 -ok 2 -ot 1), where the velocity solve is the scalar CG of lgh_mass.hip, one
+    """... and in 2D (data/square01_quad.mesh -rs 2 -ok 2 -ot 1), where the velocity solve is the scalar CG of lgh_scg.hip, one
     component after the other: its several-rank sequencing over real RCCL, on a communicator of size 1."""
     _force_multi_parity("'-m','data/square01_quad.mesh','-rs',2,'-ok',2,'-ot',1")
 
@@ -543,7 +543,7 @@ MULTI_RANK_CASES = [
     (3, (15, 2, 2), 1, 1, (3, 2), {"LGH_VCG_VARIANT": "4"}),
     (2, (10, 3, 2), 1, 0, (3, 2), {"LGH_VCG_VARIANT": "4", "LGH_COMM2": "0", "_lockstep": "1"}),
 ]
-# 2D (a zone tuple of two): the velocity solve is the scalar CG of lgh_mass.hip, once per component, with its own several-rank
+# 2D (a zone tuple of two): the velocity solve is the scalar CG of lgh_scg.hip, once per component, with its own several-rank
 # sequencing - no lockstep solver, hence no energy solve in lockstep and no "_lockstep" with LGH_COMM2=0.  Blocks of 13 x 5 zones
 # on the six rank grids of tests/rank_cases.py (tests/test_rank_cases.py: laghos::Partition picks exactly these grids), region
 # timers off and on; Q2Q1 (the order of BASELINE config 1) and Q4Q3; problem 0 (the one configuration with an energy source),

@@ -1,7 +1,7 @@
 """The kernels on several ranks in 2D (tests/rank_cases.py: the rank grids; tests/rank_threads.py: one host thread per rank
 over the in-process loopback communicator), each against the CPU oracle on the GLOBAL one-rank problem in float64.
 
-A 2D velocity solve is the scalar cg_solve(LGH_SPACE_H1) of lgh_mass.hip, once per component (lgh_k1_form reports -1: no
+A 2D velocity solve is the scalar cg_solve(LGH_SPACE_H1) of lgh_scg.hip, once per component (lgh_k1_form reports -1: no
 lockstep solver).  Its several-rank branch - cg_init_k with the fold left pending and cg_init_finish_k, mass_gather_k and
 the halo sum every iteration, the all-reduce of (d, A d) looked at by cg_update_k (cg_pending_den), the all-reduce of
 (r, z) looked at by the NEXT mass kernel (cg_pending_update), cg_update_finish_k before every host look, owner-weighted
