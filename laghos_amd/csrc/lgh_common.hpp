@@ -41,6 +41,30 @@ void set_error(const char *fmt, ...);
 
 constexpr int kWave = 64;          // gfx950 wavefront
 
+// one device allocation, freed with its owner (move-only)
+template <typename T> struct DevPtr
+{
+   T *p = nullptr;
+   DevPtr() = default;
+   DevPtr(DevPtr &&o) noexcept : p(o.p) { o.p = nullptr; } // (declaring the moves deletes the copies)
+   DevPtr &operator=(DevPtr &&o) noexcept { std::swap(p, o.p); return *this; }
+   ~DevPtr() { (void)hipFree(p); }
+   operator T *() const { return p; }
+   T **out() { return &p; }              // for the builders that allocate (make_ellz, ...)
+   int alloc(const size_t n, const bool zero = false) // n elements, uninitialised or zero
+   {
+      LGH_HIP_CHECK(hipMalloc((void **)&p, n * sizeof(T)));
+      if (zero) { LGH_HIP_CHECK(hipMemset(p, 0, n * sizeof(T))); }
+      return LGH_OK;
+   }
+   int upload(const T *host, const size_t n) // n elements, copied from the host
+   {
+      LGH_HIP_CHECK(hipMalloc((void **)&p, n * sizeof(T)));
+      LGH_HIP_CHECK(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
+      return LGH_OK;
+   }
+};
+
 // Device-resident scalars of one CG solve (SURVEY §3.2 names).
 struct CgScalars
 {
@@ -83,7 +107,7 @@ struct KTime
    std::vector<hipEvent_t> ev; // 2 per sample
 };
 
-struct Comm; // RCCL state (lgh_comm.hip)
+struct Comm; // several ranks: the transport and the neighbour tables (lgh_comm_transport.hpp)
 
 // The library's own order of the zones and numbering of the nodes (lgh_order.hip): found from the element -> node map at
 // lgh_create by face adjacency, nothing about the caller's numbering is assumed.  identity: the caller's order already is
@@ -103,7 +127,7 @@ constexpr double kJac0Tol = 1e-12;      // ... of Jac0inv inside a zone up to wh
 
 // Every environment switch of the library (DESIGN.md "Environment switches"), read ONCE per context: a context's switches
 // are those of the environment at its lgh_create (read_switches, lgh_api.hip - the only place that asks the environment,
-// but for the two properties of the shared-memory transport, LGH_SHM_MB and LGH_SHM_TIMEOUT, read where it is opened).
+// but for the two properties of the shared-memory transport, LGH_SHM_MB and LGH_SHM_TIMEOUT, read where it is opened: ShmGroup::open, lgh_comm_transport.hip).
 // Changing the environment afterwards changes nothing for a context that exists; contexts of one process may differ.
 // Flags are 0 / 1; -1 where "not set" is an answer of its own.  Field x holds LGH_X unless noted.
 struct Switches

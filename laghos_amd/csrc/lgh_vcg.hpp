@@ -433,30 +433,6 @@ __device__ __forceinline__ long long wave_sum_i64(long long v)
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 #define LGH_VCG_TRY(call) do { const int rc_ = (call); if (rc_) { return rc_; } } while (0) // (an LGH_* status: passed on)
-// one device allocation, freed with its owner (move-only)
-template <typename T> struct DevPtr
-{
-   T *p = nullptr;
-   DevPtr() = default;
-   DevPtr(DevPtr &&o) noexcept : p(o.p) { o.p = nullptr; } // (declaring the moves deletes the copies)
-   DevPtr &operator=(DevPtr &&o) noexcept { std::swap(p, o.p); return *this; }
-   ~DevPtr() { (void)hipFree(p); }
-   operator T *() const { return p; }
-   T **out() { return &p; }              // for the builders that allocate (make_ellz, ...)
-   int alloc(const size_t n, const bool zero = false) // n elements, uninitialised or zero
-   {
-      LGH_HIP_CHECK(hipMalloc((void **)&p, n * sizeof(T)));
-      if (zero) { LGH_HIP_CHECK(hipMemset(p, 0, n * sizeof(T))); }
-      return LGH_OK;
-   }
-   int upload(const T *host, const size_t n) // n elements, copied from the host
-   {
-      LGH_HIP_CHECK(hipMalloc((void **)&p, n * sizeof(T)));
-      LGH_HIP_CHECK(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
-      return LGH_OK;
-   }
-};
-
 // Tables and buffers of the solve that outlive a call (lgh_ctx::vcg_aux; lgh_vcg_tables.hip builds them, vcg_free drops them)
 struct VcgAux
 {

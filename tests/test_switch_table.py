@@ -32,13 +32,13 @@ def library_switches():
 
 def test_getenv_only_where_the_switches_are_read():
     """read_switches and the parsers in front of it (lgh_api.hip) - and the two properties of the shared-memory transport,
-    read where it is opened (lgh_comm.hip)"""
+    read where it is opened (lgh_comm_transport.hip)"""
     for base, text in CSRC.items():
         if base == "lgh_api.hip":
             head, tail = text.split("Switches read_switches()")
             assert "getenv(" not in tail[tail.index("\n}\n"):], "lgh_api.hip reads the environment behind read_switches"
             assert set(re.findall(r"getenv\(([^)]*)\)", head)) == {"name"}, "only the parsers call getenv in front of it"
-        elif base == "lgh_comm.hip":
+        elif base == "lgh_comm_transport.hip":
             assert sorted(re.findall(r"getenv\(([^)]*)\)", text)) == ['"LGH_SHM_MB"', '"LGH_SHM_TIMEOUT"']
         else:
             assert "getenv(" not in text, f"{base} reads the environment itself"
