@@ -149,7 +149,10 @@ int lgh_l2_mass_solve_local(lgh_ctx *ctx, const double *b, double *x);
 
 /* ---- QUpdate::UpdateQuadratureData (laghos_solver.cpp:1354-1411): fused
  * E-restriction + reference-gradient + QKernel; updates stressJinvT and folds the
- * point-wise dt estimate into qdata.dt_est (device side, no host sync). */
+ * point-wise dt estimate into qdata.dt_est (device side, no host sync).
+ * Work whose result the kernel can prove unused is not done (lgh_qupdate_discard below): dt candidates that cannot
+ * lower the folded minimum, F.1 rows that the flush below eps^2 would zero.  Which wavefronts skip their candidates
+ * depends on timing; the results - stressJinvT, F.1, F^T v, the folded estimate - do not, to the last bit. */
 int lgh_qupdate(lgh_ctx *ctx, const double *S);
 /* The viscosity branch of QUpdateBody (laghos_solver.cpp:1086-1134) eigen-decomposes sym(grad v) at every
  * point.  When all 64 points of a wavefront have |sym grad v|_max <= tiny_grad (units 1/time) the kernel takes
@@ -157,6 +160,18 @@ int lgh_qupdate(lgh_ctx *ctx, const double *S);
  * identical for exact zeros; for values below the threshold the stress differs by < visc_coeff * tiny_grad.
  * Default 1e-30 (LGH_Q_TINY_GRAD overrides); 0 = exact zeros only; negative = always decompose. */
 int lgh_qupdate_set_tiny_grad(lgh_ctx *ctx, double tiny_grad);
+/* lgh_qupdate skips two pieces of work whose result it can PROVE unused before computing it; every output keeps every
+ * bit (LGH_Q_DISCARD=0 switches both off, for A/B and tests; 2 / 3: only the first / the second):
+ *   - the dt candidate of a wavefront (smallest singular value of J, three divisions).  Its only reader is a global
+ *     minimum.  From det J and |J|_F the kernel bounds every candidate of the wavefront from below; where that bound lies
+ *     above a value the minimum already holds - the row form keeps one hint word beside the estimate, which only ever
+ *     receives deposited values - or the candidate is +inf, the candidates are not computed (contexts with viscosity);
+ *   - the F.1 rows of a zone (row form).  |output| <= C_F max|stressJinvT w detJ| over the zone, C_F = 3 cG cB^2 from the
+ *     absolute column sums of the basis tables; where 2 C_F max|..| < eps^2 every output would be flushed to +0.0
+ *     (laghos_assembly.cpp:495-512), and +0.0 is written without the three contractions.
+ * Which wavefronts skip their candidates depends on when they read the hint word, that is on timing; the folded
+ * estimate, F.1, F^T v and stressJinvT do not.  mode: bit 0 the dt candidate, bit 1 the F.1 rows. */
+int lgh_qupdate_discard(lgh_ctx *ctx, int *mode, double *C_F);
 /* lgh_qupdate also forms the two force products of the state it is called for - F.1 as E-vector (3D) and
  * F^T v for the state's own velocity - from the stress values it has in registers; lgh_solve_velocity and
  * lgh_solve_energy use them instead of a pass over stressJinvT each.  When they are used (no address is ever
@@ -193,6 +208,8 @@ int lgh_reset_quadrature_data(lgh_ctx *ctx);
  * L2 vector.  LGH_ERR_ARG when the product is not on hand. */
 int lgh_fused_force_mult(lgh_ctx *ctx, double *y_h1);
 int lgh_fused_force_mult_transpose(lgh_ctx *ctx, double *y_l2);
+/* F.1 as lgh_qupdate left it, before the sum over shared nodes: the E-vector [ND][dim][NE] (tests compare its bits). */
+int lgh_fused_force_e(lgh_ctx *ctx, double *y_e);
 /* *gen counts lgh_qupdate calls and invalidations; *f1_valid / *ftv_valid: a fused F.1 / F^T v is on hand (tests). */
 int lgh_quadrature_generation(lgh_ctx *ctx, unsigned long *gen, int *f1_valid, int *ftv_valid);
 /* *f1 / *ftv = 1 when lgh_qupdate forms F.1 / F^T v (what the region timers then see: the "Forces" region of

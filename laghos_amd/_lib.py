@@ -112,6 +112,7 @@ SYMBOLS = {
     "lgh_mass_data_changed": (_I, [_P]),
     "lgh_comm_stats": (_I, [_P, c_int_p, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_long), c_int_p, c_int_p]),
     "lgh_qupdate_set_tiny_grad": (_I, [_P, _D]),
+    "lgh_qupdate_discard": (_I, [_P, c_int_p, c_dbl_p]),
     "lgh_set_fused_forces": (_I, [_P, _I]),
     "lgh_qupdate_store_stress": (_I, [_P, _I]),
     "lgh_qupdate_stores_stress": (_I, [_P, c_int_p]),
@@ -119,6 +120,7 @@ SYMBOLS = {
     "lgh_reset_quadrature_data": (_I, [_P]),
     "lgh_fused_force_mult": (_I, [_P, _P]),
     "lgh_fused_force_mult_transpose": (_I, [_P, _P]),
+    "lgh_fused_force_e": (_I, [_P, _P]),
     "lgh_quadrature_generation": (_I, [_P, ctypes.POINTER(ctypes.c_ulong), c_int_p, c_int_p]),
     "lgh_get_fused_forces": (_I, [_P, c_int_p, c_int_p]),
     "lgh_comm_unique_id": (_I, [ctypes.c_char_p]),

@@ -276,6 +276,13 @@ class Context:
     def qupdate_set_tiny_grad(self, v):
         check(self.lib.lgh_qupdate_set_tiny_grad(self.h, float(v)))
 
+    def qupdate_discard(self):
+        """(mode, C_F) of lgh_qupdate_discard: which provably unused work the update skips (bit 0 the dt candidate, bit 1 the
+        F.1 rows) and the bound constant of the F.1 rows."""
+        m, cf = ctypes.c_int(-1), ctypes.c_double(0.0)
+        check(self.lib.lgh_qupdate_discard(self.h, ctypes.byref(m), ctypes.byref(cf)))
+        return m.value, cf.value
+
     def table_symmetry(self):
         """(h1, l2): whether lgh_create found the 1-D tables mirror symmetric (plane-form mass kernels need it)."""
         a, b = ctypes.c_int(-1), ctypes.c_int(-1)
@@ -388,6 +395,10 @@ class Context:
     def fused_force_mult(self, y_h1):
         """F.1 formed by the last qupdate, summed to the H1 L-vector; False when it is not on hand"""
         return self.lib.lgh_fused_force_mult(self.h, _ptr(y_h1)) == 0
+
+    def fused_force_e(self, y_e):
+        """F.1 formed by the last qupdate as E-vector (dim * NE * ND values); False when it is not on hand"""
+        return self.lib.lgh_fused_force_e(self.h, _ptr(y_e)) == 0
 
     def fused_force_mult_transpose(self, y_l2):
         return self.lib.lgh_fused_force_mult_transpose(self.h, _ptr(y_l2)) == 0

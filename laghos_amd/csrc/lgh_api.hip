@@ -100,7 +100,11 @@ __global__ void set_double_k(double *p, double v) { *p = v; }
 // qdata.dt_est = v: the estimate itself and, behind it, the partial minima the row-form update folds its candidates into
 __global__ void __launch_bounds__(256) dt_est_set_k(double *p, double v)
 {
-   if (threadIdx.x == 0) { p[0] = v; }
+   if (threadIdx.x == 0)
+   {
+      p[0] = v;
+      p[kDtHint] = (v >= 0.0) ? fabs(v) : __builtin_inf(); // (the hint is compared as an unsigned bit pattern: +0.0 and up; anything else is "no hint")
+   }
    for (int s = threadIdx.x; s < kDtSlots; s += blockDim.x) { p[kDtSlotStride * (1 + s)] = __builtin_inf(); }
 }
 // ... and the fold in front of every read: estimate = min(estimate, partial minima) in a fixed tree (a minimum does not
@@ -121,6 +125,7 @@ __global__ void __launch_bounds__(256) dt_est_fold_k(double *p, const int *err, 
    {
       const double est = fmin(p[0], m);
       p[0] = est;
+      p[kDtHint] = __builtin_inf(); // (the hint word goes back with the slots it summarised)
       host_out[0] = est;
       ((int *)(host_out + 1))[0] = *err;
       __threadfence_system();
@@ -313,6 +318,7 @@ Switches read_switches()
    s.q_ppt = env_flag("LGH_Q_PPT", 0);
    s.q_swz = (int)env_long("LGH_Q_SWZ", -1);
    s.q_occ4 = env_flag("LGH_Q_OCC4", -1);
+   s.q_discard = (int)env_long("LGH_Q_DISCARD", 1);
    s.q_tiny_grad = env_double("LGH_Q_TINY_GRAD", 1e-30); // 0: exact zeros only; -1: off
    s.fused_ftv = env_flag("LGH_FUSED_FTV", 1);
    s.fused_f1 = env_flag("LGH_FUSED_F1", 1);
@@ -461,6 +467,28 @@ int lgh_create(const lgh_config *cfg, lgh_ctx **out)
    return LGH_OK;
 }
 
+// C_F = 3 cG cB^2, cB = max_d sum_q |B[q, d]|, cG likewise from G.  An output of F.1 is the sum over the three reference
+// directions gd and the points q of stressJinvT w detJ (q, gd, c) * T_z[qz, dz] T_y[qy, dy] T_x[qx, dx], T = G in direction gd
+// and B in the other two: its absolute value is at most max_q|stressJinvT w detJ| times the sum of the three products of
+// absolute column sums, each <= cG cB^2.  The row form of the update flushes a zone's outputs without computing them where
+// that bound lies below eps^2 (lgh_qrows.hpp).
+static double q_force_bound(const lgh_config *cfg)
+{
+   double cB = 0.0, cG = 0.0;
+   for (int d = 0; d < cfg->D1D; d++)
+   {
+      double sb = 0.0, sg = 0.0;
+      for (int q = 0; q < cfg->Q1D; q++)
+      {
+         sb += std::fabs(cfg->B_h1[q + cfg->Q1D * d]);
+         sg += std::fabs(cfg->G_h1[q + cfg->Q1D * d]);
+      }
+      cB = std::max(cB, sb);
+      cG = std::max(cG, sg);
+   }
+   return 3.0 * cG * (cB * cB);
+}
+
 static int create_impl(const lgh_config *cfg, lgh_ctx *c, const int kid)
 {
    c->dim = cfg->dim; c->NE = cfg->NE; c->D1D = cfg->D1D; c->Q1D = cfg->Q1D; c->L1D = cfg->L1D;
@@ -477,6 +505,8 @@ static int create_impl(const lgh_config *cfg, lgh_ctx *c, const int kid)
    c->cfl = cfg->cfl;
    c->h1order = (double)cfg->order_v;
    c->q_tiny_grad = c->sw.q_tiny_grad;
+   c->q_discard = (c->sw.q_discard == 1) ? (kQDiscardDt | kQDiscardF1) : (c->sw.q_discard == 2) ? kQDiscardDt : (c->sw.q_discard == 3) ? kQDiscardF1 : 0;
+   c->q_cF = q_force_bound(cfg);
    c->stress_store = 1; // (the reference's behaviour: UpdateQuadratureData leaves stressJinvT in memory)
    c->stress_current = 0;
    c->h0 = 0.0;
@@ -718,6 +748,13 @@ int lgh_qupdate_form(lgh_ctx *c, int *form)
    *form = qupdate_form(c);
    return LGH_OK;
 }
+int lgh_qupdate_discard(lgh_ctx *c, int *mode, double *C_F)
+{
+   LGH_CHECK_ARG(c && mode && C_F);
+   *mode = c->q_discard;
+   *C_F = c->q_cF;
+   return LGH_OK;
+}
 int lgh_qupdate_stores_stress(lgh_ctx *c, int *on)
 {
    LGH_CHECK_ARG(c && on);
@@ -752,6 +789,13 @@ int lgh_fused_force_mult(lgh_ctx *c, double *y_h1)
    int rc = h1_transpose_gather(c, c->dim, c->force_e_q, y_h1);
    if (rc == LGH_OK && c->multi != 0) { rc = halo_sum(c, y_h1, c->dim); }
    return rc;
+}
+int lgh_fused_force_e(lgh_ctx *c, double *y_e)
+{
+   LGH_CHECK_ARG(c && y_e);
+   if (!(c->force_e_q && c->fused_f1_valid)) { set_error("lgh_fused_force_e: no fused F.1 on hand"); return LGH_ERR_ARG; }
+   LGH_HIP_CHECK(hipMemcpyAsync(y_e, c->force_e_q, sizeof(double) * (size_t)c->dim * c->NE * c->ND, hipMemcpyDeviceToDevice, c->stream));
+   return LGH_OK;
 }
 int lgh_fused_force_mult_transpose(lgh_ctx *c, double *y_l2)
 {

@@ -149,6 +149,7 @@ struct Switches
    // quadrature update and set-up
    int q_form, q_ppt, q_swz, fused_ftv, fused_f1, b_sym, jac0_compact;
    int q_occ4;           // -1: not set (by viscosity and the form of Jac0inv, launch_qrows)
+   int q_discard;        // 1 (default): the update skips work whose result is provably discarded; 0: off; A/B: 2 the dt candidate only, 3 the F.1 rows only
    double q_tiny_grad;   // the threshold a context starts with (lgh_ctx::q_tiny_grad)
    double jac0_tol;      // (default kJac0Tol; at most 1e-10)
    int profile_fold;
@@ -186,6 +187,8 @@ struct lgh_ctx
    bool visc, vort;
    double cfl, h0, h1order;
    double q_tiny_grad;   // QUpdate: threshold of the wave-uniform eigen-decomposition shortcut (lgh_qupdate.hip)
+   int q_discard;        // QUpdate: which provably unused work is skipped (kQDiscardDt | kQDiscardF1, lgh_qpoint.hpp; LGH_Q_DISCARD)
+   double q_cF;          // ... C_F = 3 cG cB^2: |F.1 output| <= C_F max|stressJinvT w detJ| of the zone (q_force_bound, lgh_api.hip)
    int device;
    hipStream_t stream;
    // second stream + fork/join events: the energy solve overlaps the velocity solve (lgh_energy.hip)
@@ -570,6 +573,11 @@ int vcg_layout_stats(lgh_ctx *c, long out[4]); // lgh_vcg_layout_stats
 int make_essbits(lgh_ctx *c, uint8_t **out);
 void vcg_free(lgh_ctx *c);
 constexpr int kDtSlots = 256, kDtSlotStride = 16; // doubles; slot s at dt_est_dev[kDtSlotStride * (1 + s)]
+// dt_est_dev[kDtHint], one of the padding doubles behind the estimate: the hint word of the row-form update.  It only ever
+// holds +inf, the estimate itself (lgh_set_dt_est) or a value that was also deposited in a slot, so the folded estimate is
+// never above it; a wavefront whose candidates provably lie above it skips them (qpoint_body).  The fold resets it to +inf.
+constexpr int kDtHint = 1;
+enum { kQDiscardDt = 1, kQDiscardF1 = 2 }; // lgh_ctx::q_discard
 constexpr int kYePad = 16; // doubles behind every Y_E plane of the CG; the first one (slot NE*ND) stays 0.0
 bool vcg_available(const lgh_ctx *c);
 int vcg_test_k1(lgh_ctx *c, const double *r, const double *d_old, const double rz[3], const double rz_prev[3], int first,

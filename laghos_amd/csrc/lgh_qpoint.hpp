@@ -53,6 +53,9 @@ struct QArgs
    const int *zorder; // row form of the update: workgroup i takes the caller's zone zorder[i] - the library's own zone order (lgh_order.hip:
                       // neighbours close on one XCD whatever order the caller numbers its zones in); nullptr: zone i
    double tiny_grad; // wave-uniform shortcut of the eigen-decomposition below this |sym grad v| (see qpoint_body); < 0: off
+   int discard;      // LGH_Q_DISCARD: kQDiscardDt - skip a dt candidate that provably cannot win (qpoint_body); kQDiscardF1 - skip the
+                     // F.1 contractions of a zone whose outputs are provably flushed (lgh_qrows.hpp)
+   double f1_quiet;  // row form: every |F.1| output of a zone is below eps^2 when every |stressJinvT w detJ| of it is below this
 };
 
 // Smooth transition between 0 and 1 for x in [-eps, eps] (laghos_solver.cpp:799-805)
@@ -68,11 +71,14 @@ __device__ __forceinline__ double smooth_step_01(double x, double eps)
 // column-major [c + DIM*d] = d u_c / d xi_d.  Returns this point's dt candidate.
 // VISC = false: instantiation without the artificial-viscosity branch (problems that run with visc off: 3D
 // Taylor-Green) - no eigen-decomposition in the code, a register budget of its own (lgh_qrows.hpp)
+// dt_ref: a value the folded estimate is known not to exceed (the row form's hint word, lgh_qrows.hpp); +inf: none known.
+// dt_skipped (trace only): whether this wavefront proved its candidates unused and skipped them.
 template <int DIM, bool VISC = true>
 __device__ __forceinline__ double qpoint_body(const QArgs &a, const int e, const size_t eq,
                                               const double weight, const double *J, const double *dV,
                                               const double e_val, const size_t plane,
-                                              const double *J0i, const double rho0DetJ0w, double &ftv, double *sjw)
+                                              const double *J0i, const double rho0DetJ0w, double &ftv, double *sjw,
+                                              const double dt_ref, bool *dt_skipped = nullptr)
 {
    constexpr int DIM2 = DIM * DIM;
    double Jinv[DIM2], stress[DIM2], sgrad_v[DIM2], stressJiT[DIM2];
@@ -157,14 +163,51 @@ __device__ __forceinline__ double qpoint_body(const QArgs &a, const int e, const
          for (int d = 0; d < DIM; d++) { divv += dV[i + DIM * d] * Jinv[d + DIM * i]; }
       s_dot_g = -P * divv;
    }
-   const double sv = sm::min_singular<DIM>(J);
-   const double h_min = sv / a.h1order;
-   const double ih_min = 1. / h_min;
-   const double irho_ih_min_sq = ih_min * ih_min / R;
-   const double idt = S * ih_min + 2.5 * visc_coeff * irho_ih_min_sq;
+   // The only reader of the dt candidate is a global MINIMUM.  A candidate that provably is not below a value the
+   // minimum already holds cannot change it, so the smallest singular value of J (150 instructions and two roots) and
+   // the three divisions behind it need not be computed.  The proof, per lane, with sigma_1 >= sigma_2 >= sigma_3 > 0:
+   //   3D: sigma_1 sigma_2 <= (sigma_1^2 + sigma_2^2) / 2 <= |J|_F^2 / 2, so sigma_min = det J / (sigma_1 sigma_2) >= 2 det J / |J|_F^2;
+   //   2D: sigma_min = det J / sigma_1 >= det J / |J|_F.
+   //   Hence 1 / h_min <= ih_ub = ihn / ihd (ihn = h1order |J|_F^2, ihd = 2 det J; 2D: h1order |J|_F, det J), and as S,
+   //   visc_coeff >= 0 and R > 0, inv_dt <= idt_ub = S ih_ub + 2.5 visc_coeff ih_ub^2 / R.  Multiplied by R ihd^2 > 0:
+   //   cfl R ihd^2 > dt_ref (1 + 1e-9) (S R ihn ihd + 2.5 visc_coeff ihn^2)  =>  candidate >= cfl / idt_ub > dt_ref.
+   //   dt_ref is a value that was deposited in the minimum (or the estimate itself): dt_ref >= the final minimum.
+   //   Therefore the skipped candidate cannot lower the minimum, and +inf (never deposited) stands for it.
+   // The margin 1e-9 covers the rounding of both sides (a dozen operations) and what the COMPUTED candidate may lie below
+   // the true one: the divisions of this file (<= 2 ulp each) and min_singular, whose error in sigma_min^2 is a few ulp of
+   // |J|_F^2 - relative to sigma_min^2 that is small only for a matrix that is not close to singular, so a lane qualifies only
+   // if its bound on sigma_min^2 is at least 1e-4 |J|_F^2 (aspect ratios up to about 50; the error is then below 1e-11).  The sum
+   // on the right is kept from underflowing by a floor of 1e-290, which only raises it.  S == 0 and visc_coeff == 0: inv_dt is
+   // exactly 0 (or NaN), the candidate +inf bit for bit whatever dt_ref is.  A lane with det J <= 0 never qualifies (its
+   // candidate is the 0.0 that stops the run), nor does one with a NaN anywhere (every comparison is false).  The wavefront
+   // skips only if ALL its lanes qualify: no divergence.  Which wavefronts skip depends on when they read dt_ref, that is on
+   // timing; the folded minimum does not.  Behind the wave-uniform a.visc: a context without viscosity executes none of it.
+   bool skip_dt = false;
+   if (VISC && a.visc && (a.discard & kQDiscardDt))
+   {
+      double f2 = J[0] * J[0];
+#pragma unroll
+      for (int k = 1; k < DIM2; k++) { f2 = fma(J[k], J[k], f2); }
+      const double ihn = a.h1order * ((DIM == 3) ? f2 : sm::fsqrt(f2));
+      const double ihd = (DIM == 3) ? 2.0 * detJ : detJ;
+      const bool regular = (DIM == 3) ? (ihd * ihd >= 1e-4 * (f2 * f2 * f2)) : (detJ * detJ >= 1e-4 * (f2 * f2));
+      const double w = ihn * (S * R * ihd + 2.5 * visc_coeff * ihn);
+      const double lhs = a.cfl * R * (ihd * ihd);
+      const bool cannot_win = (S == 0.0 && visc_coeff == 0.0) || lhs > dt_ref * (1.0 + 1e-9) * ((w < 1e-290) ? 1e-290 : w);
+      skip_dt = __all((detJ > 0.0 && R > 0.0 && regular && cannot_win) ? 1 : 0) != 0;
+   }
+   if (dt_skipped) { *dt_skipped = skip_dt; }
    double dt_cand = INFINITY;
-   if (detJ < 0.0) { dt_cand = 0.0; }
-   else if (idt > 0.0) { dt_cand = a.cfl / idt; }
+   if (!skip_dt)
+   {
+      const double sv = sm::min_singular<DIM>(J);
+      const double h_min = sv / a.h1order;
+      const double ih_min = 1. / h_min;
+      const double irho_ih_min_sq = ih_min * ih_min / R;
+      const double idt = S * ih_min + 2.5 * visc_coeff * irho_ih_min_sq;
+      if (detJ < 0.0) { dt_cand = 0.0; }
+      else if (idt > 0.0) { dt_cand = a.cfl / idt; }
+   }
    sm::matmul_abt<DIM>(stress, Jinv, stressJiT);
    const double wd = weight * detJ;
    ftv = s_dot_g * wd;
@@ -508,7 +551,8 @@ qpoint_kernel(const QArgs a)
       for (int k = 0; k < DIM * DIM; k++) { sjw[k] = 0.0; }
       if constexpr (PPT == 1)
       {
-         if (active) { cand = qpoint_body<DIM>(a, e, eq, weight, J, dV, e_val, plane, J0i, rdw, ftv, sjw); }
+         // (no hint word in this form, dt_ref = +inf: only a candidate that is +inf itself is skipped)
+         if (active) { cand = qpoint_body<DIM>(a, e, eq, weight, J, dV, e_val, plane, J0i, rdw, ftv, sjw, INFINITY); }
       }
       else
       {
@@ -529,8 +573,8 @@ qpoint_kernel(const QArgs a)
                }
             if (active)
             {
-               const double c_p = (p == 0) ? qpoint_body<DIM>(a, e, eq, weight, J, dV, ev, plane, J0i, rdw, ftv, sjw)
-                                           : qpoint_body<DIM>(a, e, eq + NTE, a.W[lt + NTE], J, dV, ev, plane, J0i_b, rdw_b, ftv_b, sjw_b);
+               const double c_p = (p == 0) ? qpoint_body<DIM>(a, e, eq, weight, J, dV, ev, plane, J0i, rdw, ftv, sjw, INFINITY)
+                                           : qpoint_body<DIM>(a, e, eq + NTE, a.W[lt + NTE], J, dV, ev, plane, J0i_b, rdw_b, ftv_b, sjw_b, INFINITY);
                cand = fmin(cand, c_p);
             }
             __builtin_amdgcn_sched_barrier(0); // (one point after the other: interleaved, the two bodies need twice the registers)
@@ -892,6 +936,9 @@ static QArgs q_base(lgh_ctx *c)
    a.visc = c->visc;
    a.vort = c->vort;
    a.tiny_grad = c->q_tiny_grad;
+   a.discard = c->q_discard;
+   // 2 C_F max|sjw| < eps^2: C_F max|sjw| bounds every F.1 output of the zone, the factor 2 the rounding of its <= 648 terms
+   a.f1_quiet = (c->q_cF > 0.0) ? (2.220446049250313e-16 * 2.220446049250313e-16) / (2.0 * c->q_cF) : 0.0;
    a.q_swz = c->sw.q_swz; // A/B: -1 contiguous eighths, 0 none, n: runs of 2^n elements
    a.erhs_q = c->fused_forces_off ? nullptr : c->erhs_q;
    a.force_e = (c->dim == 3 && !c->fused_forces_off) ? c->force_e_q : nullptr;

@@ -164,6 +164,16 @@ qrows_kernel(const QArgs a, unsigned long long *trace = nullptr)
    }
    const double rdw = a.rho0DetJ0w_in[eq];
    const double weight = a.W[lt];
+   // the hint word of the dt estimate (kDtHint, lgh_common.hpp): a value the folded estimate cannot exceed, read once per
+   // wavefront and kept wave-uniform.  An agent-scope atomic load, not a cached scalar one: a value from before the last
+   // fold's reset would be unsound (a later, lower one is merely a better hint).  +inf: no hint, or the feature is off.
+   const bool hint_on = a.visc && (a.discard & kQDiscardDt);
+   double dt_ref = __builtin_inf();
+   if (hint_on)
+   {
+      dt_ref = uniform_f64(__longlong_as_double((long long)__hip_atomic_load((const unsigned long long *)(a.result + kDtHint), __ATOMIC_RELAXED,
+                                                                            __HIP_MEMORY_SCOPE_AGENT)));
+   }
    LGH_QSTAMP(1); // loads issued
    __syncthreads();
    LGH_QSTAMP(2); // gathers, tables in LDS
@@ -258,11 +268,25 @@ qrows_kernel(const QArgs a, unsigned long long *trace = nullptr)
    }
    LGH_QSTAMP(5); // Z stage (this wavefront)
    double ftv = 0.0, sjw[9];
-   const double cand = qpoint_body<3>(a, e, eq, weight, J, dV, e_val, plane, J0i, rdw, ftv, sjw);
+   bool dt_skipped = false;
+   const double cand = qpoint_body<3>(a, e, eq, weight, J, dV, e_val, plane, J0i, rdw, ftv, sjw, dt_ref, TRACE ? &dt_skipped : nullptr);
    LGH_QSTAMP(6); // point body (this wavefront)
    tstamp[7] = tstamp[8] = tstamp[9] = tstamp[10] = 0;
 
    const bool do_f = (a.force_e != nullptr), do_t = (a.erhs_q != nullptr);
+   // F.1 of a zone whose outputs are provably flushed.  P7 replaces every output with |v| < eps^2 by +0.0.  An output is a
+   // sum of at most 648 terms sjw * (product of three table entries), so |v| <= C_F max|sjw| over the zone (C_F:
+   // q_force_bound, lgh_api.hip), and with a factor 2 for the rounding of the sum: if every |sjw| of the zone is below
+   // a.f1_quiet = eps^2 / (2 C_F), all 3 D^3 outputs are +0.0 whatever P5 - P7 compute - they store the zeros and skip the
+   // three contractions.  A comparison per value rather than a maximum: a NaN fails it (a maximum would drop it), and a
+   // zone with a NaN in its stress keeps computing NaN outputs as before.  Every wavefront writes its verdict to a word of
+   // its own before the barrier that stands here anyway, and every thread reads all of them behind it: the decision is
+   // workgroup-uniform.  The F^T v parts run as before: erhs_q is not flushed and keeps the bits of its tiny values.
+   // Like the dt candidate's skip, only in a context with viscosity.
+   constexpr int NW = (NT + 63) / 64;
+   __shared__ int sQuiet[NW];
+   const bool f1_discard = a.visc && (a.discard & kQDiscardF1);
+   bool f1_quiet = false;
    if (do_f || do_t)
    {
       // the x-contracted arrays are dead since the barrier above: the stress goes straight to its place
@@ -271,13 +295,28 @@ qrows_kernel(const QArgs a, unsigned long long *trace = nullptr)
       {
 #pragma unroll
          for (int k = 0; k < 9; k++) { sF[k * NQ + pq] = sjw[k]; } // sjw[gd + 3*c]
+         if (f1_discard)
+         {
+            bool lq = true;
+#pragma unroll
+            for (int k = 0; k < 9; k++) { lq = lq && (fabs(sjw[k]) < a.f1_quiet); }
+            const int wq = (__all(lq ? 1 : 0) != 0) ? 1 : 0;
+            if ((lt & 63) == 0) { sQuiet[lt >> 6] = wq; }
+         }
       }
       if (do_t) { sS[pq] = ftv; }
       __syncthreads();
       LGH_QSTAMP(7); // every wavefront's body done, stress in LDS
+      if (do_f && f1_discard)
+      {
+         int q = 1;
+#pragma unroll
+         for (int w = 0; w < NW; w++) { q &= sQuiet[w]; }
+         f1_quiet = __builtin_amdgcn_readfirstlane(q) != 0;
+      }
 
       // ---- P5: contraction over qz, rows (k, qy, qx); F^T v: rows (qy, qx)
-      if (do_f)
+      if (do_f && !f1_quiet)
       {
          for (int i = lt; i < 9 * QQ; i += NT)
          {
@@ -308,7 +347,7 @@ qrows_kernel(const QArgs a, unsigned long long *trace = nullptr)
       LGH_QSTAMP(8); // qz contraction
 
       // ---- P6: contraction over qy, rows (k, dz, qx); F^T v: rows (lz, qx)
-      if (do_f)
+      if (do_f && !f1_quiet)
       {
          for (int i = lt; i < 9 * D * Q; i += NT)
          {
@@ -342,7 +381,18 @@ qrows_kernel(const QArgs a, unsigned long long *trace = nullptr)
 
       // ---- P7: contraction over qx and the sum over the three reference directions, rows (c, dz, dy) -> E-vector;
       //          F^T v: rows (lz, ly) -> L2 vector
-      if (do_f)
+      if (do_f && f1_quiet)
+      {
+         // every output proved below eps^2 in absolute value: the +0.0 the flush below would put there
+         for (int i = lt; i < 3 * DD; i += NT)
+         {
+            const int c = i / DD, r = i - c * DD;
+            double *dst = a.force_e + (size_t)ND * (c + 3 * (size_t)e) + D * r;
+#pragma unroll
+            for (int d = 0; d < D; d++) { dst[d] = 0.0; }
+         }
+      }
+      else if (do_f)
       {
          const double eps2 = 2.220446049250313e-16 * 2.220446049250313e-16;
          for (int i = lt; i < 3 * DD; i += NT)
@@ -398,7 +448,17 @@ qrows_kernel(const QArgs a, unsigned long long *trace = nullptr)
          const double w0 = (wmin > 0.0) ? wmin : 0.0;
          unsigned long long *slot = (unsigned long long *)(a.result + kDtSlotStride * (1 + (blockIdx.x % kDtSlots)));
          (void)__hip_atomic_fetch_min(slot, (unsigned long long)__double_as_longlong(w0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+         // ... and, only where it improves on the hint this wavefront read, to the hint word: it receives nothing that is
+         // not in a slot as well, so the folded estimate never exceeds it.  Improving deposits are rare (the word would
+         // not stand one atomic per wavefront, see above).
+         if (hint_on && w0 < dt_ref)
+         {
+            (void)__hip_atomic_fetch_min((unsigned long long *)(a.result + kDtHint), (unsigned long long)__double_as_longlong(w0), __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT);
+         }
       }
+      // (the record's word 14 is zeroed before the launch: the number of this workgroup's wavefronts that skipped their dt candidates)
+      if (TRACE && trace && lane == 0 && dt_skipped) { atomicAdd(trace + (size_t)kQTraceRec * blockIdx.x + 14, 1ull); }
    }
    if (TRACE && lt == 0 && trace)
    {
@@ -410,6 +470,7 @@ qrows_kernel(const QArgs a, unsigned long long *trace = nullptr)
       for (int k = 0; k < 12; k++) { rec[k] = tstamp[k]; }
       rec[12] = ((unsigned long long)xcc << 32) | hwid;
       rec[13] = (unsigned long long)e;
+      rec[15] = f1_quiet ? 1ull : 0ull; // whether the F.1 rows were written as zeros without the contractions
    }
 #undef LGH_QSTAMP
 }
@@ -439,7 +500,8 @@ static void qrows_trace_dump(lgh_ctx *c)
    for (int i = 0; i < c->q_trace_n; i++)
    {
       fprintf(f, "%d", i);
-      for (int k = 0; k < 14; k++) { fprintf(f, " %llu", h[(size_t)kQTraceRec * i + k]); }
+      // 12 stamps, xcc << 32 | hw_id, the zone, then what was proved unused: wavefronts that skipped their dt candidates, F.1 rows skipped (0 / 1)
+      for (int k = 0; k < kQTraceRec; k++) { fprintf(f, " %llu", h[(size_t)kQTraceRec * i + k]); }
       fprintf(f, "\n");
    }
    fclose(f);
@@ -454,6 +516,7 @@ template <int MINW6> static int launch_qrows_w(lgh_ctx *c, const QArgs &a)
          LGH_HIP_CHECK(hipMalloc((void **)&c->q_trace_dev, (size_t)kQTraceRec * c->NE * 8));
          c->q_trace_n = c->NE;
       }
+      LGH_HIP_CHECK(hipMemsetAsync(c->q_trace_dev, 0, (size_t)kQTraceRec * c->NE * 8, c->stream)); // (word 14 of a record is a counter)
       if (a.Jac0inv_e) { hipLaunchKernelGGL((qrows_kernel<4, 6, 3, MINW6, true, true>), dim3(c->NE), dim3(216), 0, c->stream, a, c->q_trace_dev); }
       else { hipLaunchKernelGGL((qrows_kernel<4, 6, 3, MINW6, true, false>), dim3(c->NE), dim3(216), 0, c->stream, a, c->q_trace_dev); }
       LGH_HIP_CHECK(hipGetLastError());

@@ -6,6 +6,7 @@ import numpy as np
 
 STAGES = ["issue loads", "wait loads (barrier)", "X stage", "Y stage", "Z stage (wave 0)", "point body (wave 0)",
           "wait other waves' bodies", "qz contraction", "qy contraction", "qx contraction + stores", "dt reduction / exit"]
+WAVES_PER_WORKGROUP = 4  # the traced instantiation is the Q3Q2 one: 216 threads
 
 
 def main(path):
@@ -26,6 +27,13 @@ def main(path):
             continue
         dur = t[:, b] - t[:, a]
         print("  %-28s mean %7.3f us  (%4.1f %% of a life)" % (name, dur.mean() * 1e-3, 100 * dur.mean() / life.mean()))
+    # work proved unused and skipped (LGH_Q_DISCARD): per workgroup the number of its wavefronts that skipped their dt
+    # candidates, and whether its F.1 rows were written as zeros (a file of an older library has no such columns)
+    if d.shape[1] >= 17:
+        nskip, f1 = d[ok, 15].astype(np.int64), d[ok, 16].astype(np.int64)
+        print("discard: dt candidate skipped by %d of %d wavefronts (%.1f %%), F.1 rows skipped in %d of %d workgroups (%.1f %%)" %
+              (nskip.sum(), WAVES_PER_WORKGROUP * len(t), 100.0 * nskip.sum() / (WAVES_PER_WORKGROUP * len(t)),
+               f1.sum(), len(t), 100.0 * f1.sum() / len(t)))
     # residency per CU: (xcc, se, sh, cu)
     xcc = (hw >> np.uint64(32)).astype(np.int64) & 0xF
     hwid = (hw & np.uint64(0xFFFFFFFF)).astype(np.int64)
