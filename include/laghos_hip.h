@@ -418,6 +418,35 @@ typedef struct lgh_profile_spec {
 } lgh_profile_spec;
 int lgh_profile(lgh_ctx *ctx, const double *S, const lgh_profile_spec *spec, double *out, long *n_excluded);
 
+/* ---- the flow binned onto a fixed Cartesian grid (the driver's `-map`): the point quantities of lgh_profile above - x_q,
+ * v_q, e_q, detJ_q, m_q, rho_q, p_q, NON-FINITE and INVERTED as there; a component of x_q below dim that is not finite also
+ * makes the point non-finite - deposited into the cells of a box that stays where it is while the mesh moves.  lgh_profile
+ * is the one-axis case.  Per axis c < dim: b_c = floor((x_q[c] - lo_c) * inv_w_c), inv_w_c = n_c / (hi_c - lo_c) formed once
+ * on the host.  A point with some b_c < 0 or b_c >= n_c goes to row 0 ("outside"), every other one to row
+ * 1 + b_0 + n_0 (b_1 + n_1 b_2).  Excluded points enter no row and are counted in *n_excluded (summed over the ranks).
+ * Columns of a row: 0 n | 1 vol = sum w detJ | 2 mass = sum m | 3 ie = sum m e | 4 ke = 1/2 sum m |v|^2 |
+ *   5-7 mom_c = sum m v_c (exactly +0.0 for c >= dim) | 8 pv = sum w detJ p | 9 rho_min | 10 rho_max (+inf / -inf: empty row).
+ * Columns 1-8 go through the two-set exact accumulators of lgh_profile (pass 0 for the column maxima and the windows, hi / lo
+ * limbs, non-returning 64-bit integer atomics, the NaN flag per (row, column) for an addend that is not finite), counts and
+ * extremes through integer atomics: no floating-point atomic, and the same bits for every zone order, node numbering, launch
+ * grid and rank count.  The rows add up to the totals of lgh_diagnostics less the excluded points.
+ * out: HOST, (ncells + 1) rows of LGH_MAP_COLS doubles, row-major, ncells = n[0] n[1] n[2].  Synchronous; collective over the
+ * ranks of the context.  Reads what lgh_profile reads and writes its outputs only.  All dimensions.
+ * LGH_ERR_ARG without a launch: before lgh_setup_rho0detj0, a NULL argument, n[c] < 1, n[c] != 1 for c >= dim, ncells above
+ * LGH_MAP_MAX_CELLS, and on an axis below dim lo, hi or hi - lo not finite or lo >= hi.  The scratch memory (about 1.4 KB per
+ * cell) is allocated at the first call and regrown only when the cell count grows; when it cannot be had the call returns
+ * LGH_ERR_HIP with the byte count in the message and the context stays usable.
+ * LGH_MAP_FOLD=n (default 8, at most 64): a wavefront folds the lanes of up to n distinct cells before it sends one atomic
+ * per non-zero limb of a cell; the lanes left after that send their own (0: always); the same bits either way. */
+#define LGH_MAP_COLS 11
+#define LGH_MAP_MAX_CELLS (1 << 20)
+typedef struct lgh_map_spec {
+   int n[3];               /* cells per axis, >= 1; n[c] must be 1 for c >= dim */
+   double lo[3], hi[3];    /* finite, lo < hi, for c < dim; ignored above */
+} lgh_map_spec;
+int lgh_map(lgh_ctx *ctx, const double *S, const lgh_map_spec *spec,
+            double *out /* HOST, (ncells + 1) x LGH_MAP_COLS, row-major */, long *n_excluded);
+
 /* ---- timing data (TimingData, laghos_solver.hpp:39-56): seconds measured with
  * HIP events around the same regions as the reference stopwatches.
  * t[0..3] = cgH1, cgL2, force, qdata; c[0..2] = H1iter, L2iter, quad_tstep */
@@ -442,6 +471,7 @@ int lgh_enable_timers(lgh_ctx *ctx, int on);
 #define LGH_KERNEL_DIAG 10        /* the zone kernel of lgh_diagnostics_zones / lgh_diagnostics */
 #define LGH_KERNEL_PROFILE 11     /* lgh_profile: both passes over the zones and the kernels between and behind them */
 #define LGH_KERNEL_DERIVED 12     /* lgh_sample_derived */
+#define LGH_KERNEL_MAP 13         /* lgh_map: as LGH_KERNEL_PROFILE */
 int lgh_ktime_begin(lgh_ctx *ctx, int which, int max_samples);
 int lgh_ktime_end(lgh_ctx *ctx, int *launches, double *mean_seconds);
 /* Whether lgh_create found the 1-D H1 / L2 tables mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (any nodal or

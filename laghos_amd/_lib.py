@@ -40,6 +40,11 @@ class LghProfileSpec(ctypes.Structure):
                 ("origin", ctypes.c_double * 3)]
 
 
+class LghMapSpec(ctypes.Structure):
+    """struct lgh_map_spec (include/laghos_hip.h)."""
+    _fields_ = [("n", ctypes.c_int * 3), ("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3)]
+
+
 # every symbol include/laghos_hip.h declares: name -> (restype, argtypes)
 _I, _D, _P, _L = ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_long
 SYMBOLS = {
@@ -95,6 +100,7 @@ SYMBOLS = {
     "lgh_diagnostics_zones": (_I, [_P, _P, _P]),
     "lgh_diagnostics": (_I, [_P, _P, c_dbl_p]),
     "lgh_profile": (_I, [_P, _P, ctypes.POINTER(LghProfileSpec), c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
+    "lgh_map": (_I, [_P, _P, ctypes.POINTER(LghMapSpec), c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
     "lgh_get_timers": (_I, [_P, c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
     "lgh_reset_timers": (_I, [_P]),
     "lgh_enable_timers": (_I, [_P, _I]),

@@ -85,6 +85,42 @@ def profile_dict(rows, n_excluded, lo, hi):
                 p=ratio(col["pv"], col["vol"]), xi=ratio(col["mxi"], col["mass"]))
 
 
+# lgh_map: the columns of a row (include/laghos_hip.h)
+MAP_COLS = ("n", "vol", "mass", "ie", "ke", "mom_x", "mom_y", "mom_z", "pv", "rho_min", "rho_max")
+MAP_MAX_CELLS = 1 << 20
+
+
+def map_spec(cells, lo, hi):
+    """cells, lo, hi of a map - a number, or one per axis - as three lists of 3 (1 cell over [0, 1] on an axis not given) and
+    the number of rows a buffer for the call needs (1 for a grid the library refuses)"""
+    n = [int(k) for k in np.atleast_1d(cells)][:3]
+    a = [float(x) for x in np.atleast_1d(lo)][:3]
+    b = [float(x) for x in np.atleast_1d(hi)][:3]
+    n, a, b = n + [1] * (3 - len(n)), a + [0.0] * (3 - len(a)), b + [1.0] * (3 - len(b))
+    ncells = 1
+    for k in n:
+        ncells = ncells * k if 1 <= k and 1 <= ncells * k <= MAP_MAX_CELLS else 0
+    return n, a, b, ncells + 1
+
+
+def map_dict(rows, n_excluded, dim, n, lo, hi):
+    """what Context.map returns, from the (ncells + 1, 11) rows of lgh_map: the raw rows, `outside` (row 0), `grid` (the other
+    rows as (n2, n1, n0, 11)), the cell edges per used axis and the derived rho = mass / vol, e = ie / mass, v = mom / mass
+    ((n2, n1, n0, dim)) and p = pv / vol of the cells, NaN where the divisor is 0"""
+    grid = rows[1:].reshape(n[2], n[1], n[0], len(MAP_COLS))
+    col = {k: grid[..., i] for i, k in enumerate(MAP_COLS)}
+
+    def ratio(a, b):
+        b = b.reshape(b.shape + (1,) * (a.ndim - b.ndim))   # (one divisor for the components of a vector)
+        out = np.full(a.shape, np.nan)
+        np.divide(a, b, out=out, where=(b != 0))
+        return out
+    return dict(rows=rows, outside=rows[0], grid=grid, n_excluded=int(n_excluded),
+                edges=[lo[c] + (hi[c] - lo[c]) * np.arange(n[c] + 1) / n[c] for c in range(dim)],
+                rho=ratio(col["mass"], col["vol"]), e=ratio(col["ie"], col["mass"]), v=ratio(grid[..., 5:5 + dim], col["mass"]),
+                p=ratio(col["pv"], col["vol"]))
+
+
 def diagnostics_dict(out):
     """the 20 doubles of lgh_diagnostics by name"""
     return {k: (int(out[i]) if k in _DIAG_INTS else float(out[i])) for i, k in enumerate(DIAG_NAMES)}
@@ -505,6 +541,21 @@ class Context:
         n_excl = ctypes.c_long(-1)
         check(self.lib.lgh_profile(self.h, _ptr(S), ctypes.byref(spec), _dbl(rows), ctypes.byref(n_excl)))
         return profile_dict(rows, n_excl.value, spec.lo, spec.hi)
+
+    def map(self, S, cells, lo, hi):
+        """lgh_map: the flow binned onto a fixed Cartesian grid - `cells` per axis over the box [lo, hi) (a number or one per
+        axis of the dimension): a dict with `rows` ((ncells + 1, 11), MAP_COLS), `outside` (row 0: the points beside the box),
+        `grid` (the cells as (n2, n1, n0, 11)), `edges`, `n_excluded` and the derived rho, e, v, p of the cells (map_dict).
+        Exact, order-free sums: the same bits for every numbering, launch grid and rank count.  Synchronous."""
+        from ._lib import LghMapSpec
+        n, a, b, n_rows = map_spec(cells, lo, hi)
+        spec = LghMapSpec()
+        for k in range(3):
+            spec.n[k], spec.lo[k], spec.hi[k] = n[k], a[k], b[k]
+        rows = np.full((n_rows, len(MAP_COLS)), np.nan)   # (an entry the library did not write would show)
+        n_excl = ctypes.c_long(-1)
+        check(self.lib.lgh_map(self.h, _ptr(S), ctypes.byref(spec), _dbl(rows), ctypes.byref(n_excl)))
+        return map_dict(rows, n_excl.value, self.dim, n, a, b)
 
     def solve_energy_begin(self, S, v, dS, e_rhs, rel_tol, max_iter, e_source=None):
         check(self.lib.lgh_solve_energy_begin(self.h, _ptr(S), _ptr(v), _ptr(dS), _ptr(e_rhs),

@@ -327,6 +327,7 @@ Switches read_switches()
    // (a tolerance above 1e-10 would turn curved zones into affine ones: clamped - round-5 advisor)
    s.jac0_tol = std::min(std::max(env_double("LGH_JAC0_TOL", kJac0Tol), 0.0), 1e-10);
    s.profile_fold = (int)std::max(0L, env_long("LGH_PROFILE_FOLD", 8));
+   s.map_fold = (int)std::min(std::max(0L, env_long("LGH_MAP_FOLD", 8)), 64L); // (a wavefront has 64 lanes: no more cells than that)
    s.roctx = env_flag("LGH_ROCTX", 0);
    s.vcg_trace = env_string("LGH_VCG_TRACE");
    s.vcg_trace_phases = getenv("LGH_VCG_TRACE_PHASES") != nullptr;
@@ -683,7 +684,7 @@ int lgh_destroy(lgh_ctx *c)
                    c->stressJinvT, c->Jac0inv, c->Jac0inv_soa, c->Jac0inv_e, c->rho0DetJ0w, c->massD, c->diagV, c->dinvV,
                    c->dt_est_dev, c->erhs_q, c->v_snap, c->dev_flags, c->ones_l2, c->massS, c->ones_ne, c->force_e_q, c->XE, c->YE, c->cg_r, c->cg_z, c->cg_d0, c->cg_d1, c->cg_y,
                    c->partials, c->tickets, c->cgs, c->scal, c->vcg_s, c->vcg_vec, c->vcg_partials,
-                   c->vcg_tickets, c->me_fac, c->fp_dev, c->diag_dev, c->prof_dev};
+                   c->vcg_tickets, c->me_fac, c->fp_dev, c->diag_dev, c->prof_dev, c->map_dev};
    for (void *p : ptrs) { if (p) { (void)hipFree(p); } }
    if (c->host_pinned) { (void)hipHostFree(c->host_pinned); }
    if (c->timers.ev[0]) { (void)hipEventDestroy(c->timers.ev[0]); }

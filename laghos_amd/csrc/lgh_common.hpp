@@ -153,6 +153,7 @@ struct Switches
    double q_tiny_grad;   // the threshold a context starts with (lgh_ctx::q_tiny_grad)
    double jac0_tol;      // (default kJac0Tol; at most 1e-10)
    int profile_fold;
+   int map_fold;
    // debug
    int roctx, vcg_trace_phases, q_trace_call;
    std::string vcg_trace, q_trace; // files; empty: no trace
@@ -288,6 +289,8 @@ struct lgh_ctx
    double *diag_dev;     // lgh_diagnostics (lgh_diag.hip): 32 doubles of folded values, then the 17 zone arrays; allocated on first use
    void *prof_dev = nullptr; // lgh_profile (lgh_profile.hip): accumulator words, flags, maxima and the packed rows for prof_rows rows;
    int prof_rows = 0;        // allocated at the first call, regrown only when nbins grows
+   void *map_dev = nullptr;  // lgh_map (lgh_map.hip): the same for map_rows rows of eight sum columns; regrown only when the cell count grows
+   int map_rows = 0;
    unsigned long long *fp_dev; // lgh_vec_fingerprint (lgh_fingerprint.hip): the two words of the result and the workgroups' partial words, allocated on first use
 };
 

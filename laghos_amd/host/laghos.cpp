@@ -29,6 +29,7 @@
 #include "vtk_output.hpp"
 #include "checkpoint.hpp"
 #include "history.hpp"
+#include "map_output.hpp"
 #include "profile.hpp"
 
 using namespace laghos;
@@ -89,6 +90,12 @@ struct Options
    bool prof_range_set = false;    // -prof-range LO HI (default: from the initial mesh, at cycle 0)
    double prof_lo = 0, prof_hi = 0;
    double prof_origin[3] = {0, 0, 0}; // -prof-origin X [Y [Z]] (default: the blast position of -err, the origin)
+   // -map N: the flow binned onto a fixed Cartesian grid (lgh_map) in <basename>_map/cycle_<cycle>.vti at cycle 0, after every
+   // accepted step with ti % N == 0 and after the last one (0: none); map_output.hpp, DESIGN.md §7g
+   int map_steps = 0;
+   int map_cells_n = 0, map_cells[3] = {64, 64, 64}; // -map-cells NX [NY [NZ]] (default: 64 per axis of the mesh)
+   int map_box_n = 0;                                // -map-box X0 X1 [Y0 Y1 [Z0 Z1]] (default: the extent of the initial mesh)
+   double map_box[6] = {0, 0, 0, 0, 0, 0};
    bool fingerprint = false;       // -fp: rank 0 prints the state fingerprint after the last step and per checkpoint
 };
 
@@ -197,6 +204,47 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
          if (n == 0) { err = "-prof-origin needs one to three numbers"; return false; }
          continue;
       }
+      if (a == "-map" || a == "--map-steps")
+      {
+         if (!(v = need(i))) { return false; }
+         o.map_steps = std::atoi(v);
+         if (o.map_steps < 1) { err = "-map / --map-steps must be at least 1, got " + std::string(v); return false; }
+         continue;
+      }
+      if (a == "-map-cells" || a == "--map-cells")
+      {
+         o.map_cells_n = 0;
+         while (o.map_cells_n < 3 && i + 1 < argc) // one to three counts
+         {
+            char *end = nullptr;
+            const long k = std::strtol(argv[i + 1], &end, 10);
+            if (end == argv[i + 1] || *end) { break; }
+            if (k < 1 || k > LGH_MAP_MAX_CELLS) { err = "-map-cells needs counts between 1 and " + std::to_string(LGH_MAP_MAX_CELLS) + ", got " + std::string(argv[i + 1]); return false; }
+            o.map_cells[o.map_cells_n++] = (int)k;
+            i++;
+         }
+         if (o.map_cells_n == 0) { err = "-map-cells needs one to three counts"; return false; }
+         continue;
+      }
+      if (a == "-map-box" || a == "--map-box")
+      {
+         o.map_box_n = 0;
+         while (o.map_box_n < 6 && i + 1 < argc) // one pair per axis
+         {
+            char *end = nullptr;
+            const double x = std::strtod(argv[i + 1], &end);
+            if (end == argv[i + 1] || *end) { break; }
+            o.map_box[o.map_box_n++] = x;
+            i++;
+         }
+         if (o.map_box_n == 0 || o.map_box_n % 2) { err = "-map-box needs a pair LO HI per axis, got " + std::to_string(o.map_box_n) + " numbers"; return false; }
+         for (int k = 0; k < o.map_box_n; k += 2)
+         {
+            const double lo = o.map_box[k], hi = o.map_box[k + 1];
+            if (!(std::isfinite(lo) && std::isfinite(hi) && std::isfinite(hi - lo) && lo < hi)) { err = "-map-box needs finite LO < HI on every axis"; return false; }
+         }
+         continue;
+      }
       if (a == "-restart" || a == "--restart")
       {
          if (!(v = need(i))) { return false; }
@@ -277,6 +325,11 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
    if (o.pv_fields_set && !o.paraview)
    {
       err = "-pv-fields adds fields to the -paraview dumps: it needs -paraview";
+      return false;
+   }
+   if ((o.map_cells_n > 0 || o.map_box_n > 0) && o.map_steps == 0)
+   {
+      err = std::string(o.map_cells_n > 0 ? "-map-cells" : "-map-box") + " describes the -map files: it needs -map";
       return false;
    }
    return true;
@@ -434,6 +487,10 @@ struct laghos_sim
    char prof_axis = 'x';
    int prof_last = -1, prof_files = 0;
    std::vector<double> prof_rows;
+   // -map: the grid (fixed at the start, from the initial mesh), the last cycle that has its file, the files of this run
+   lgh_map_spec map_spec = {};
+   int map_last = -1, map_files = 0;
+   std::vector<double> map_rows;
    bool prof_exact = false;
    double prof_par[21] = {};
    int steps_at_start = 0;             // RK steps the checkpoint of a restart had taken: timing / FOM cover the restarted segment
@@ -761,6 +818,53 @@ static bool ProfileRecord(laghos_sim *s, int cycle)
    return true;
 }
 
+// -map: the grid.  The default box is the extent of the INITIAL mesh S0 per axis over all ranks (as ProfileSetup takes its
+// default range: a restart rebuilds S0 as every run does and so reproduces it).
+static void MapSetup(laghos_sim *s, const std::vector<double> &S0)
+{
+   const Options &o = s->opt;
+   const Discretization &d = *s->disc;
+   lgh_map_spec &sp = s->map_spec;
+   size_t ncells = 1;
+   for (int c = 0; c < 3; c++)
+   {
+      sp.n[c] = (c < d.dim) ? o.map_cells[c] : 1;
+      sp.lo[c] = 0.0; sp.hi[c] = 1.0;
+      ncells *= (size_t)sp.n[c];
+      if (c >= d.dim) { continue; }
+      if (o.map_box_n > 0) { sp.lo[c] = o.map_box[2 * c]; sp.hi[c] = o.map_box[2 * c + 1]; continue; }
+      double lo = INFINITY, hi = -INFINITY;
+      for (long n = 0; n < d.N; n++)
+      {
+         const double x = S0[(size_t)c * d.N + n];
+         lo = std::min(lo, x); hi = std::max(hi, x);
+      }
+      sp.lo[c] = s->hydro->AllReduce(lo, 1);
+      sp.hi[c] = -s->hydro->AllReduce(-hi, 1);
+   }
+   s->map_rows.assign((ncells + 1) * LGH_MAP_COLS, 0.0);
+}
+
+// The `-map` file of the state as it stands, cycle `cycle`: the rows on the GPU (collective), the file by rank 0.  Every rank
+// learns whether it was written.
+static bool MapRecord(laghos_sim *s, int cycle)
+{
+   const Options &o = s->opt;
+   auto &hydro = *s->hydro;
+   const lgh_map_spec &sp = s->map_spec;
+   long n_excl = 0;
+   hydro.Map(s->S, sp, s->map_rows.data(), &n_excl);
+   bool ok = true;
+   std::string err;
+   if (o.rank == 0) { ok = WriteVti(MapDir(o.basename), s->disc->dim, sp.n, sp.lo, sp.hi, s->map_rows.data(), n_excl, cycle, s->t, err); }
+   const bool all_ok = hydro.AllReduce(ok ? 1.0 : 0.0, 1) == 1.0;
+   if (!ok) { return SimFail(s, "cannot write the -map file: " + err); }
+   if (!all_ok) { return SimFail(s, "rank 0 could not write the -map file"); }
+   s->map_last = cycle;
+   s->map_files++;
+   return true;
+}
+
 extern "C"
 {
 
@@ -821,6 +925,26 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
       {
          std::fprintf(stderr, "laghos: -prof-axis %s needs a mesh of %d dimensions, this one has %d\n", o.prof_axis.c_str(), o.prof_axis[0] - 'x' + 1, o.dim);
          return nullptr;
+      }
+      if (o.map_steps > 0)
+      {
+         if (o.map_cells_n > 0 && o.map_cells_n != o.dim)
+         {
+            std::fprintf(stderr, "laghos: -map-cells has %d counts, the mesh has %d dimensions\n", o.map_cells_n, o.dim);
+            return nullptr;
+         }
+         if (o.map_box_n > 0 && o.map_box_n != 2 * o.dim)
+         {
+            std::fprintf(stderr, "laghos: -map-box has %d numbers, a mesh of %d dimensions needs %d\n", o.map_box_n, o.dim, 2 * o.dim);
+            return nullptr;
+         }
+         double ncells = 1.0;
+         for (int c = 0; c < o.dim; c++) { ncells *= (double)o.map_cells[c]; }
+         if (ncells > (double)LGH_MAP_MAX_CELLS)
+         {
+            std::fprintf(stderr, "laghos: -map-cells asks for %.0f cells, at most %d fit\n", ncells, LGH_MAP_MAX_CELLS);
+            return nullptr;
+         }
       }
       if (!o.p_assembly && o.dim != 1)
       {
@@ -925,6 +1049,7 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
       if (keep_in_registers) { LGH_VERIFY(lgh_qupdate_store_stress(s->hydro->Context(), 0)); }
    }
    if (o.prof_steps > 0) { ProfileSetup(s.get(), S0); }
+   if (o.map_steps > 0) { MapSetup(s.get(), S0); }
    if (restarting)
    {
       // the set-up data came from S0 as in every run; the state now comes from the file and must have arrived in HBM intact
@@ -973,6 +1098,7 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
       }
       if (o.hist_steps > 0 && !HistoryOpen(s.get(), h.ti)) { return nullptr; } // (no row for the checkpoint's own state: the run that wrote it has)
       s->prof_last = h.ti;                                                     // (nor a profile)
+      s->map_last = h.ti;                                                      // (nor a map)
       // a checkpoint written after the last step: nothing is left to do
       if (s->t >= o.t_final || (o.max_tsteps >= 0 && s->steps > o.max_tsteps)) { s->last_step = true; }
       return s.release();
@@ -987,6 +1113,7 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
    if (o.paraview && !DumpParaview(s.get(), 0)) { return nullptr; }                   // :691-701
    if (o.hist_steps > 0 && !(HistoryOpen(s.get(), -1) && HistoryRecord(s.get(), 0))) { return nullptr; }
    if (o.prof_steps > 0 && !ProfileRecord(s.get(), 0)) { return nullptr; }
+   if (o.map_steps > 0 && !MapRecord(s.get(), 0)) { return nullptr; }
    return s.release();
 }
 
@@ -1037,6 +1164,7 @@ int laghos_sim_step(laghos_sim *s)
          // ... and the row "after the last step", unless that step has its row already (repeated steps themselves write none)
          if (s->last_step && o.hist_steps > 0 && s->ti - 1 > s->hist_last && !HistoryRecord(s, s->ti - 1)) { return -1; }
          if (s->last_step && o.prof_steps > 0 && s->ti - 1 > s->prof_last && !ProfileRecord(s, s->ti - 1)) { return -1; } // (the same rule)
+         if (s->last_step && o.map_steps > 0 && s->ti - 1 > s->map_last && !MapRecord(s, s->ti - 1)) { return -1; }        // (and here)
          continue;
       }
       else if (dt_est > 1.25 * s->dt) { s->dt *= 1.02; }
@@ -1077,6 +1205,7 @@ int laghos_sim_step(laghos_sim *s)
       if (o.ckpt_steps > 0 && (s->last_step || (s->ti % o.ckpt_steps) == 0) && !PeriodicCheckpoint(s, s->ti)) { return -1; }
       if (o.hist_steps > 0 && (s->last_step || (s->ti % o.hist_steps) == 0) && !HistoryRecord(s, s->ti)) { return -1; }
       if (o.prof_steps > 0 && (s->last_step || (s->ti % o.prof_steps) == 0) && !ProfileRecord(s, s->ti)) { return -1; }
+      if (o.map_steps > 0 && (s->last_step || (s->ti % o.map_steps) == 0) && !MapRecord(s, s->ti)) { return -1; }
       s->ti++;
       return 1;
    }
@@ -1143,6 +1272,17 @@ int laghos_sim_profile(laghos_sim *s, int axis, int nbins, double lo, double hi,
    sp.axis = axis; sp.nbins = nbins; sp.lo = lo; sp.hi = hi;
    for (int k = 0; k < 3; k++) { sp.origin[k] = origin ? origin[k] : 0.0; }
    const int rc = lgh_profile(s->hydro->Context(), s->S.Read(), &sp, rows, n_excluded);
+   if (rc != 0) { s->error = lgh_last_error(); }
+   return rc;
+}
+// lgh_map of the state as it stands (collective on several ranks): n, lo, hi = 3 values each, rows = (n[0] n[1] n[2] + 1) x
+// LGH_MAP_COLS doubles.  0 = ok; otherwise laghos_sim_error() has the library's message and nothing was written.
+int laghos_sim_map(laghos_sim *s, const int *n, const double *lo, const double *hi, double *rows, long *n_excluded)
+{
+   if (!n || !lo || !hi) { s->error = "laghos_sim_map: NULL grid"; return LGH_ERR_ARG; }
+   lgh_map_spec sp = {};
+   for (int k = 0; k < 3; k++) { sp.n[k] = n[k]; sp.lo[k] = lo[k]; sp.hi[k] = hi[k]; }
+   const int rc = lgh_map(s->hydro->Context(), s->S.Read(), &sp, rows, n_excluded);
    if (rc != 0) { s->error = lgh_last_error(); }
    return rc;
 }
@@ -1249,6 +1389,14 @@ int laghos_host_write_vtu(const char *dir, int dim, int NE, int R1, const double
                           const double *rho, const double *p, int cycle, double time, int rank, int nranks)
 {
    return WriteVtu(dir, dim, NE, R1, x, v, e, rho, p, cycle, time, rank, nranks) ? 0 : -1;
+}
+// host-only: the writer of the `-map` files (map_output.hpp); 0 = written.  rows: the (n[0] n[1] n[2] + 1) x LGH_MAP_COLS doubles of
+// lgh_map; the file goes to <dir>/cycle_<6 digits>.vti
+int laghos_host_write_vti(const char *dir, int dim, const int *n, const double *lo, const double *hi, const double *rows, long n_excluded,
+                          int cycle, double time)
+{
+   std::string err;
+   return WriteVti(dir, dim, n, lo, hi, rows, n_excluded, cycle, time, err) ? 0 : -1;
 }
 int laghos_host_write_pvtu(const char *dir, int cycle, double time, int nranks) { return WritePvtu(dir, cycle, time, nranks) ? 0 : -1; }
 // ... with n_extra further PointData arrays behind the four standing ones (WriteVtuFields): names[k], comps[k] values per point,
@@ -1488,6 +1636,7 @@ int laghos_main(int argc, const char *const *argv)
    }
    if (o.hist_steps > 0 && !o.quiet) { std::cout << "History: " << s->hist.path << ", " << s->hist.rows << " rows" << std::endl; }
    if (o.prof_steps > 0 && !o.quiet) { std::cout << "Profiles: " << s->prof_files << " files, " << o.basename << "_profile_*.csv" << std::endl; }
+   if (o.map_steps > 0 && !o.quiet) { std::cout << "Maps: " << s->map_files << " files, " << MapDir(o.basename) << "/cycle_*.vti" << std::endl; }
    int ret = 0;
    if (o.check_exact_sedov)
    {

@@ -286,6 +286,11 @@ void LagrangianHydroOperator::Profile(const Vector &S, const lgh_profile_spec &s
    LGH_VERIFY(lgh_profile(ctx, S.Read(), &spec, rows, n_excluded));
 }
 
+void LagrangianHydroOperator::Map(const Vector &S, const lgh_map_spec &spec, double *rows, long *n_excluded) const
+{
+   LGH_VERIFY(lgh_map(ctx, S.Read(), &spec, rows, n_excluded));
+}
+
 void LagrangianHydroOperator::SedovEval(const double par[21], double t, const std::vector<double> &r, std::vector<double> &rho,
                                         std::vector<double> &v, std::vector<double> &p) const
 {

@@ -109,6 +109,9 @@ public:
    // The state S binned along a coordinate (lgh_profile; the driver's `-prof` files): rows = (nbins + 2) x LGH_PROFILE_COLS host
    // doubles.  Synchronous, collective on several ranks; reads what Diagnostics reads and leaves alone what it leaves alone.
    void Profile(const Vector &S, const lgh_profile_spec &spec, double *rows, long *n_excluded) const;
+   // The state S binned onto a fixed Cartesian grid (lgh_map; the driver's `-map` files): rows = (ncells + 1) x LGH_MAP_COLS host
+   // doubles.  Collective over the ranks.
+   void Map(const Vector &S, const lgh_map_spec &spec, double *rows, long *n_excluded) const;
    // The exact Sedov solution `par` at time t at n radii (host arrays in and out; lgh_sedov_eval on the GPU)
    void SedovEval(const double par[21], double t, const std::vector<double> &r, std::vector<double> &rho, std::vector<double> &v,
                   std::vector<double> &p) const;

@@ -36,34 +36,6 @@ std::string PvtuName(int cycle) { return CycleTag(cycle) + ".pvtu"; }
 namespace
 {
 
-// the arrays of the appended block, in file order: a DataArray element in the header, UInt64 byte count + data behind it
-struct Appended
-{
-   struct Block { const void *data; uint64_t bytes; };
-   std::vector<Block> blocks;
-   uint64_t offset = 0;
-   std::string Array(const char *type, const char *name, int ncomp, const void *data, uint64_t bytes, const char *extra = "")
-   {
-      std::ostringstream os;
-      os << "<DataArray type=\"" << type << "\" Name=\"" << name << "\"";
-      if (ncomp > 0) { os << " NumberOfComponents=\"" << ncomp << "\""; }
-      os << extra << " format=\"appended\" offset=\"" << offset << "\"/>\n";
-      blocks.push_back({data, bytes});
-      offset += sizeof(uint64_t) + bytes;
-      return os.str();
-   }
-   void Write(std::ostream &f) const
-   {
-      f << "<AppendedData encoding=\"raw\">\n_";
-      for (const Block &b : blocks)
-      {
-         f.write(reinterpret_cast<const char *>(&b.bytes), sizeof(uint64_t));
-         f.write(reinterpret_cast<const char *>(b.data), (std::streamsize)b.bytes);
-      }
-      f << "\n</AppendedData>\n";
-   }
-};
-
 // c-th component of point pt of a dim-component structure of arrays, zero above dim
 std::vector<double> Interleave3(const double *soa, int dim, size_t NP)
 {

@@ -4,6 +4,9 @@
 // code, no MFEM: a high-order zone becomes R^dim linear cells on its (R+1)^dim lattice points, points duplicated zone
 // by zone so that the discontinuous fields are exact.  DESIGN.md §7b.
 #pragma once
+#include <cstdint>
+#include <ostream>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -12,6 +15,34 @@ namespace laghos
 
 // mkdir -p
 void MakeDirs(const std::string &dir);
+
+// the arrays of the appended block, in file order: a DataArray element in the header, UInt64 byte count + data behind it
+struct Appended
+{
+   struct Block { const void *data; uint64_t bytes; };
+   std::vector<Block> blocks;
+   uint64_t offset = 0;
+   std::string Array(const char *type, const char *name, int ncomp, const void *data, uint64_t bytes, const char *extra = "")
+   {
+      std::ostringstream os;
+      os << "<DataArray type=\"" << type << "\" Name=\"" << name << "\"";
+      if (ncomp > 0) { os << " NumberOfComponents=\"" << ncomp << "\""; }
+      os << extra << " format=\"appended\" offset=\"" << offset << "\"/>\n";
+      blocks.push_back({data, bytes});
+      offset += sizeof(uint64_t) + bytes;
+      return os.str();
+   }
+   void Write(std::ostream &f) const
+   {
+      f << "<AppendedData encoding=\"raw\">\n_";
+      for (const Block &b : blocks)
+      {
+         f.write(reinterpret_cast<const char *>(&b.bytes), sizeof(uint64_t));
+         f.write(reinterpret_cast<const char *>(b.data), (std::streamsize)b.bytes);
+      }
+      f << "\n</AppendedData>\n";
+   }
+};
 
 // "cycle_<6 digits>.vtu", with ".<rank>" in front of the extension on several ranks
 std::string VtuName(int cycle, int nranks, int rank);

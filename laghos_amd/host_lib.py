@@ -91,6 +91,10 @@ def load():
         L.laghos_sim_diagnostics.argtypes = [P, P]
         L.laghos_sim_profile.restype = I
         L.laghos_sim_profile.argtypes = [P, I, I, D, D, P, P, ctypes.POINTER(Lg)]
+        L.laghos_sim_map.restype = I
+        L.laghos_sim_map.argtypes = [P, P, P, P, P, ctypes.POINTER(Lg)]
+        L.laghos_host_write_vti.restype = I
+        L.laghos_host_write_vti.argtypes = [ctypes.c_char_p, I, P, P, P, P, Lg, I, D]
         L.laghos_host_history_header.restype = ctypes.c_char_p
         L.laghos_host_history_header.argtypes = []
         L.laghos_host_history_row.restype = I
@@ -182,6 +186,19 @@ class Sim:
         if rc != 0:
             raise RuntimeError(f"laghos_sim_profile: error {rc}: {self.L.laghos_sim_error(self.h).decode()}")
         return profile_dict(rows, n_excl.value, float(lo), float(hi))
+
+    def map(self, cells, lo, hi):
+        """The state as it stands binned onto a fixed Cartesian grid of `cells` per axis over the box [lo, hi) (lgh_map; what a
+        `-map` file is made of): the dict of Context.map; every rank calls it."""
+        from .context import MAP_COLS, map_dict, map_spec
+        n, a, b, n_rows = map_spec(cells, lo, hi)
+        rows = np.full((n_rows, len(MAP_COLS)), np.nan)
+        n_excl = ctypes.c_long(-1)
+        na, la, ha = np.asarray(n, dtype=np.int32), np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        rc = self.L.laghos_sim_map(self.h, na.ctypes.data, la.ctypes.data, ha.ctypes.data, rows.ctypes.data, ctypes.byref(n_excl))
+        if rc != 0:
+            raise RuntimeError(f"laghos_sim_map: error {rc}: {self.L.laghos_sim_error(self.h).decode()}")
+        return map_dict(rows, n_excl.value, self.sizes()["dim"], n, a, b)
 
     def derived_fields(self, R):
         """The derived fields of the state as it stands on the lattice of R cells per zone and direction (lgh_sample_derived;
@@ -315,6 +332,21 @@ def host_write_vtu(directory, dim, NE, R1, x, v, e, rho, p, cycle, time, rank=0,
         raise RuntimeError(f"cannot write a .vtu under {directory}")
     tag = f"cycle_{cycle:06d}" + (f".{rank}" if nranks > 1 else "")
     return os.path.join(str(directory), tag + ".vtu")
+
+
+def host_write_vti(directory, dim, cells, lo, hi, rows, n_excluded, cycle, time):
+    """One `-map` file from the (ncells + 1, 11) rows of lgh_map (Context.map's `rows`) on the grid of `cells` over [lo, hi)
+    (map_spec's forms); returns the path written, <directory>/cycle_<6 digits>.vti."""
+    from .context import MAP_COLS, map_spec
+    L = load()
+    n, a, b, n_rows = map_spec(cells, lo, hi)
+    rows = _f64(rows)
+    assert rows.size == n_rows * len(MAP_COLS) and all(k == 1 for k in n[dim:])
+    na, la, ha = np.asarray(n, dtype=np.int32), _f64(a), _f64(b)
+    if L.laghos_host_write_vti(str(directory).encode(), dim, na.ctypes.data, la.ctypes.data, ha.ctypes.data, rows.ctypes.data, int(n_excluded),
+                               cycle, time) != 0:
+        raise RuntimeError(f"cannot write a .vti under {directory}")
+    return os.path.join(str(directory), f"cycle_{cycle:06d}.vti")
 
 
 def _extra_args(extra, NP=None):

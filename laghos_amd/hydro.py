@@ -86,6 +86,11 @@ class HydroOperator:
         the curves derived from them.  Reads S and the set-up data only; the quadrature data stays as it is."""
         return self.ctx.profile(S, axis, nbins, lo, hi, origin)
 
+    def map(self, S, cells, lo, hi):
+        """The state S binned onto a fixed Cartesian grid of `cells` per axis over the box [lo, hi) (Context.map): exact,
+        order-free cell sums and the fields derived from them.  Reads S and the set-up data only."""
+        return self.ctx.map(S, cells, lo, hi)
+
     def derived_fields(self, S, R):
         """The derived fields of the state S on the lattice of R cells per zone and direction (Context.sample_derived; what
         `-pv-fields` adds to a dump): a dict of numpy arrays detj, div_v, sound_speed (NP), grad_v (dim^2, NP; entry i*dim + j =
