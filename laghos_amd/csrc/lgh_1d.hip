@@ -724,99 +724,28 @@ __global__ void __launch_bounds__(256) cg1d_k(const Cg1dArgs a)
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-template <typename T> static int alloc_copy(T **dst, const T *src, size_t n)
-{
-   LGH_HIP_CHECK(hipMalloc((void **)dst, std::max<size_t>(n, 1) * sizeof(T)));
-   if (src && n) { LGH_HIP_CHECK(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice)); }
-   return LGH_OK;
-}
-template <typename T> static int alloc_zero(T **dst, size_t n)
-{
-   LGH_HIP_CHECK(hipMalloc((void **)dst, std::max<size_t>(n, 1) * sizeof(T)));
-   LGH_HIP_CHECK(hipMemset(*dst, 0, std::max<size_t>(n, 1) * sizeof(T)));
-   LGH_HIP_CHECK(hipStreamSynchronize(nullptr)); // (the fill runs on the null stream; the context's stream does not wait for it)
-   return LGH_OK;
-}
-
-// lgh_create for dim == 1 (the arguments have been checked there; `c` is zeroed).  What a 2D/3D context builds beyond this
+// lgh_create for dim == 1 (the arguments have been checked there).  What a 2D/3D context builds beyond this
 // (lockstep solve tables, fused force products, second stream) has no 1D use.
 int create_1d(const lgh_config *cfg, lgh_ctx *c)
 {
-   const int D = cfg->D1D, Q = cfg->Q1D, L = cfg->L1D, NE = cfg->NE, N = cfg->N;
-   c->dim = 1; c->NE = NE; c->D1D = D; c->Q1D = Q; c->L1D = L;
-   c->ND = D; c->NQ = Q; c->NL = L;
-   c->N = N; c->H1V = N; c->L2V = NE * L;
-   c->kid = (1 << 8) | (D << 4) | Q;
-   c->visc = cfg->use_viscosity != 0;
-   c->vort = cfg->use_vorticity != 0;
-   c->cfl = cfg->cfl;
-   c->h1order = (double)cfg->order_v;
-   c->stress_store = 1;
-   c->device = cfg->device;
-   c->cur_ess = -1;
-   c->nranks = 1;
-   c->rank = 0;
-   c->mass_rank1 = -1;
-   if (cfg->stream) { c->stream = (hipStream_t)cfg->stream; c->own_stream = false; }
-   else { LGH_HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
-   int rc;
-#define LGH_TRY(x) do { rc = (x); if (rc) { return rc; } } while (0)
-   LGH_TRY(alloc_copy(&c->B, cfg->B_h1, (size_t)Q * D));
-   LGH_TRY(alloc_copy(&c->G, cfg->G_h1, (size_t)Q * D));
-   LGH_TRY(alloc_copy(&c->Bl, cfg->B_l2, (size_t)Q * L));
-   LGH_TRY(alloc_copy(&c->W, cfg->weights, (size_t)Q));
-   LGH_TRY(alloc_copy(&c->gamma, cfg->gamma, (size_t)NE));
-   const size_t nmap = (size_t)NE * D;
-   LGH_TRY(alloc_copy(&c->h1map, cfg->h1_map, nmap));
-   LGH_TRY(mesh_order_build(c, cfg->h1_map)); // (the identity below 3D: lgh_mesh_order reports the caller's order)
-   {
-      // transpose of the restriction (CSR, ascending E-vector position per node): the fixed order of every node sum
-      std::vector<int> off((size_t)N + 1, 0), idx(nmap);
-      for (size_t i = 0; i < nmap; i++) { off[(size_t)cfg->h1_map[i] + 1]++; }
-      for (int n = 0; n < N; n++) { off[(size_t)n + 1] += off[n]; }
-      std::vector<int> pos(off.begin(), off.end() - 1);
-      for (size_t i = 0; i < nmap; i++) { idx[pos[cfg->h1_map[i]]++] = (int)i; }
-      LGH_TRY(alloc_copy(&c->t_off, off.data(), off.size()));
-      LGH_TRY(alloc_copy(&c->t_idx, idx.data(), idx.size()));
-   }
-   {
-      c->ess_count[0] = cfg->ess_count[0];
-      std::vector<uint8_t> mask((size_t)N, 0);
-      for (int i = 0; i < c->ess_count[0]; i++) { mask[cfg->ess[0][i]] = 1; }
-      LGH_TRY(alloc_copy(&c->essmask[0], mask.data(), mask.size()));
-      LGH_TRY(alloc_copy(&c->ess[0], c->ess_count[0] ? cfg->ess[0] : nullptr, (size_t)c->ess_count[0]));
-   }
-   const size_t nq = (size_t)NE * Q;
-   LGH_TRY(alloc_zero(&c->stressJinvT, nq));
-   LGH_TRY(alloc_zero(&c->Jac0inv, nq));
-   LGH_TRY(alloc_zero(&c->rho0DetJ0w, nq));
-   LGH_TRY(alloc_zero(&c->massD, nq));
-   LGH_TRY(alloc_zero(&c->me_fac, (size_t)NE * L * L));
-   LGH_TRY(alloc_zero(&c->diagV, (size_t)N));
-   LGH_TRY(alloc_zero(&c->dinvV, (size_t)N));
-   LGH_TRY(alloc_zero(&c->dt_est_dev, (size_t)kDtSlotStride * (1 + kDtSlots)));
-   LGH_TRY(alloc_zero(&c->dev_flags, (size_t)8));
-   LGH_TRY(alloc_zero(&c->YE, std::max(nmap, (size_t)c->L2V)));
+   std::vector<int> off, idx; // (the transpose of the restriction on the host: no use here)
+   LGH_PASS(create_common(cfg, c, off, idx));
+   const int L = c->L1D, NE = c->NE, N = c->N;
+   const size_t nq = (size_t)NE * c->Q1D;
+   LGH_PASS(ctx_buffer(c->stressJinvT, nq));
+   LGH_PASS(ctx_buffer(c->Jac0inv, nq));
+   LGH_PASS(ctx_buffer(c->rho0DetJ0w, nq));
+   LGH_PASS(ctx_buffer(c->massD, nq));
+   LGH_PASS(ctx_buffer(c->me_fac, (size_t)NE * L * L));
+   LGH_PASS(ctx_buffer(c->diagV, (size_t)N));
+   LGH_PASS(ctx_buffer(c->dinvV, (size_t)N));
+   LGH_PASS(ctx_buffer(c->dev_flags, (size_t)8));
+   LGH_PASS(ctx_buffer(c->YE, std::max((size_t)NE * c->D1D, (size_t)c->L2V)));
    const size_t nv = std::max<size_t>((size_t)N, (size_t)c->L2V);
-   LGH_TRY(alloc_zero(&c->cg_r, nv));
-   LGH_TRY(alloc_zero(&c->cg_z, nv));
-   LGH_TRY(alloc_zero(&c->cg_d0, nv));
-   LGH_TRY(alloc_zero(&c->cg_y, nv));
-   c->part_stride = (int)std::max<size_t>(std::max<size_t>((size_t)NE, (nv + 255) / 256), 2048) + (int)kShards;
-   LGH_TRY(alloc_zero(&c->partials, 4 * (size_t)c->part_stride));
-   LGH_TRY(alloc_zero(&c->tickets, 4 * (size_t)kTicketSlot));
-   LGH_TRY(alloc_zero(&c->cgs, 1));
-   LGH_TRY(alloc_zero(&c->scal, 16));
-   LGH_HIP_CHECK(hipHostMalloc((void **)&c->host_pinned, kPinDoubles * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-   memset(c->host_pinned, 0, kPinDoubles * sizeof(double));
-   LGH_HIP_CHECK(hipHostGetDevicePointer((void **)&c->host_pinned_dev, c->host_pinned, 0));
-   LGH_HIP_CHECK(hipEventCreate(&c->timers.ev[0]));
-   LGH_HIP_CHECK(hipEventCreate(&c->timers.ev[1]));
-   {
-      const std::vector<double> infs((size_t)kDtSlotStride * (1 + kDtSlots), std::numeric_limits<double>::infinity());
-      LGH_HIP_CHECK(hipMemcpy(c->dt_est_dev, infs.data(), infs.size() * sizeof(double), hipMemcpyHostToDevice));
-   }
-#undef LGH_TRY
+   LGH_PASS(ctx_buffer(c->cg_r, nv));
+   LGH_PASS(ctx_buffer(c->cg_z, nv));
+   LGH_PASS(ctx_buffer(c->cg_d0, nv));
+   LGH_PASS(ctx_buffer(c->cg_y, nv));
    return LGH_OK;
 }
 
@@ -1065,9 +994,8 @@ int sedov_density_error_1d(lgh_ctx *c, const double *x_h1, const double *rho_l2,
    tab.insert(tab.end(), B_h1, B_h1 + (size_t)n1d * D);
    tab.insert(tab.end(), G_h1, G_h1 + (size_t)n1d * D);
    tab.insert(tab.end(), B_l2, B_l2 + (size_t)n1d * L);
-   double *buf = nullptr; // [tables | r | rho_h | w detJ | rho_exact | v | P]
-   LGH_HIP_CHECK(hipMalloc((void **)&buf, (tab.size() + 6 * np) * sizeof(double)));
-   struct Release { double *p; ~Release() { (void)hipFree(p); } } release{buf};
+   DevPtr<double> buf; // [tables | r | rho_h | w detJ | rho_exact | v | P]
+   LGH_PASS(buf.alloc(tab.size() + 6 * np));
    LGH_HIP_CHECK(hipMemcpy(buf, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
    const double *dw = buf, *dB = dw + n1d, *dG = dB + (size_t)n1d * D, *dBl = dG + (size_t)n1d * D;
    double *r = buf + tab.size(), *rh = r + np, *wd = rh + np, *rx = wd + np, *vx = rx + np, *px = vx + np;

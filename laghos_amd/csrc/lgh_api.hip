@@ -7,7 +7,8 @@
 #include <algorithm>
 #include <limits>
 
-#include "lgh_common.hpp"
+#include "lgh_comm_transport.hpp"
+#include "lgh_vcg.hpp"
 
 #include <atomic>
 #include <chrono>
@@ -336,20 +337,74 @@ Switches read_switches()
    return s;
 }
 
-template <typename T> static int dev_alloc_copy(T **dst, const T *src, size_t n)
+CtxHandles::~CtxHandles()
 {
-   LGH_HIP_CHECK(hipMalloc((void **)dst, std::max<size_t>(n, 1) * sizeof(T)));
-   if (src && n) { LGH_HIP_CHECK(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice)); }
-   return LGH_OK;
+   if (stream2) { (void)hipStreamDestroy(stream2); }
+   if (ev_fork) { (void)hipEventDestroy(ev_fork); } // (create_stream2 may have failed between the stream and its events)
+   if (ev_join) { (void)hipEventDestroy(ev_join); }
+   if (host_pinned) { (void)hipHostFree(host_pinned); }
+   if (own_stream) { (void)hipStreamDestroy(stream); }
 }
-template <typename T> static int dev_alloc_zero(T **dst, size_t n)
+
+// What a context of any dimension starts with: the header fields, the stream, the tables, the restriction and its transpose
+// (handed back as t_off / t_idx: the 2D/3D context forms its ELL copy from them), the essential masks, the reduction scratch,
+// the pinned block, the timer events and the dt slots at +inf.  The arguments have been checked by lgh_create.
+int create_common(const lgh_config *cfg, lgh_ctx *c, std::vector<int> &t_off, std::vector<int> &t_idx)
 {
-   LGH_HIP_CHECK(hipMalloc((void **)dst, std::max<size_t>(n, 1) * sizeof(T)));
-   LGH_HIP_CHECK(hipMemset(*dst, 0, std::max<size_t>(n, 1) * sizeof(T)));
-   // hipMemset of device memory returns before the fill has run (null stream) and the
-   // context's stream does not synchronise with the null stream
-   LGH_HIP_CHECK(hipStreamSynchronize(nullptr));
-   return LGH_OK;
+   const int dim = cfg->dim;
+   auto ipow = [dim](const int n) { return dim == 1 ? n : dim == 2 ? n * n : n * n * n; };
+   c->dim = dim; c->NE = cfg->NE; c->D1D = cfg->D1D; c->Q1D = cfg->Q1D; c->L1D = cfg->L1D;
+   c->ND = ipow(c->D1D); c->NQ = ipow(c->Q1D); c->NL = ipow(c->L1D);
+   c->N = cfg->N;
+   c->H1V = dim * c->N;
+   c->L2V = c->NE * c->NL;
+   c->kid = (dim << 8) | (c->D1D << 4) | c->Q1D;
+   c->visc = cfg->use_viscosity != 0;
+   c->vort = cfg->use_vorticity != 0;
+   c->cfl = cfg->cfl;
+   c->h1order = (double)cfg->order_v;
+   if (cfg->stream) { c->stream = (hipStream_t)cfg->stream; }
+   else { LGH_HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
+
+   LGH_PASS(ctx_buffer(c->B, (size_t)c->Q1D * c->D1D, cfg->B_h1));
+   LGH_PASS(ctx_buffer(c->G, (size_t)c->Q1D * c->D1D, cfg->G_h1));
+   LGH_PASS(ctx_buffer(c->Bl, (size_t)c->Q1D * c->L1D, cfg->B_l2));
+   LGH_PASS(ctx_buffer(c->W, (size_t)c->NQ, cfg->weights));
+   LGH_PASS(ctx_buffer(c->gamma, (size_t)c->NE, cfg->gamma));
+   const size_t nmap = (size_t)c->NE * c->ND;
+   LGH_PASS(ctx_buffer(c->h1map, nmap, cfg->h1_map));
+   LGH_PASS(mesh_order_build(c, cfg->h1_map)); // the library's own zone order and node numbering (lgh_order.hip; the identity below 3D)
+   // transpose of the restriction in CSR form (ascending E-vector position per node: the fixed order of every node sum)
+   t_off.assign((size_t)c->N + 1, 0);
+   t_idx.resize(nmap);
+   for (size_t i = 0; i < nmap; i++) { t_off[(size_t)cfg->h1_map[i] + 1]++; }
+   for (int n = 0; n < c->N; n++) { t_off[(size_t)n + 1] += t_off[n]; }
+   std::vector<int> pos(t_off.begin(), t_off.end() - 1);
+   for (size_t i = 0; i < nmap; i++) { t_idx[pos[cfg->h1_map[i]]++] = (int)i; }
+   LGH_PASS(ctx_buffer(c->t_off, t_off.size(), t_off.data()));
+   LGH_PASS(ctx_buffer(c->t_idx, t_idx.size(), t_idx.data()));
+   for (int k = 0; k < (dim == 1 ? 1 : 3); k++) // (a 2D context has the third mask too, empty)
+   {
+      c->ess_count[k] = (k < dim) ? cfg->ess_count[k] : 0;
+      std::vector<uint8_t> mask((size_t)c->N, 0);
+      for (int i = 0; i < c->ess_count[k]; i++) { mask[cfg->ess[k][i]] = 1; }
+      LGH_PASS(ctx_buffer(c->essmask[k], mask.size(), mask.data()));
+      LGH_PASS(ctx_buffer(c->ess[k], (size_t)c->ess_count[k], c->ess_count[k] ? cfg->ess[k] : nullptr));
+   }
+
+   const size_t nv = std::max<size_t>((size_t)c->N, (size_t)c->L2V);
+   c->part_stride = (int)std::max<size_t>(std::max<size_t>((size_t)c->NE, (nv + 255) / 256), 2048) + (int)kShards;
+   LGH_PASS(ctx_buffer(c->partials, 4 * (size_t)c->part_stride));
+   LGH_PASS(ctx_buffer(c->tickets, 4 * (size_t)kTicketSlot));
+   LGH_PASS(ctx_buffer(c->cgs, 1));
+   LGH_PASS(ctx_buffer(c->scal, 16));
+   LGH_HIP_CHECK(hipHostMalloc((void **)&c->host_pinned, kPinDoubles * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+   memset(c->host_pinned, 0, kPinDoubles * sizeof(double));
+   LGH_HIP_CHECK(hipHostGetDevicePointer((void **)&c->host_pinned_dev, c->host_pinned, 0)); // (the one-thread kernels in front of a host look write there)
+   LGH_HIP_CHECK(hipEventCreate(&c->timers.ev[0]));
+   LGH_HIP_CHECK(hipEventCreate(&c->timers.ev[1]));
+   const std::vector<double> infs((size_t)kDtSlotStride * (1 + kDtSlots), std::numeric_limits<double>::infinity());
+   return ctx_buffer(c->dt_est_dev, infs.size(), infs.data());
 }
 
 static bool kernel_id_supported(int id)
@@ -405,7 +460,7 @@ extern "C"
 const char *lgh_last_error(void) { return g_err; }
 const char *lgh_version(void) { return "laghos_hip 0.1 (gfx950)"; }
 
-static int create_impl(const lgh_config *cfg, lgh_ctx *c, const int kid);
+static int create_impl(const lgh_config *cfg, lgh_ctx *c);
 
 int lgh_create(const lgh_config *cfg, lgh_ctx **out)
 {
@@ -453,12 +508,12 @@ int lgh_create(const lgh_config *cfg, lgh_ctx **out)
       return LGH_ERR_UNSUPPORTED;
    }
 
-   lgh_ctx *c = new lgh_ctx(); // (value-initialised: every member zero, then the default member initialisers)
+   lgh_ctx *c = new lgh_ctx;
    c->sw = read_switches();
    if (c->sw.roctx) { roctx_enable(); }
    c->device = cfg->device;
    // every failure below (HIP errors, out of memory) releases what was built so far
-   const int rc_create = (cfg->dim == 1) ? create_1d(cfg, c) : create_impl(cfg, c, kid);
+   const int rc_create = (cfg->dim == 1) ? create_1d(cfg, c) : create_impl(cfg, c);
    if (rc_create != LGH_OK)
    {
       lgh_destroy(c);
@@ -490,37 +545,14 @@ static double q_force_bound(const lgh_config *cfg)
    return 3.0 * cG * (cB * cB);
 }
 
-static int create_impl(const lgh_config *cfg, lgh_ctx *c, const int kid)
+static int create_impl(const lgh_config *cfg, lgh_ctx *c)
 {
-   c->dim = cfg->dim; c->NE = cfg->NE; c->D1D = cfg->D1D; c->Q1D = cfg->Q1D; c->L1D = cfg->L1D;
+   std::vector<int> off, idx; // the transpose of the restriction on the host
+   LGH_PASS(create_common(cfg, c, off, idx));
    const int dim = c->dim;
-   c->ND = dim == 2 ? c->D1D * c->D1D : c->D1D * c->D1D * c->D1D;
-   c->NQ = dim == 2 ? c->Q1D * c->Q1D : c->Q1D * c->Q1D * c->Q1D;
-   c->NL = dim == 2 ? c->L1D * c->L1D : c->L1D * c->L1D * c->L1D;
-   c->N = cfg->N;
-   c->H1V = dim * c->N;
-   c->L2V = c->NE * c->NL;
-   c->kid = kid;
-   c->visc = cfg->use_viscosity != 0;
-   c->vort = cfg->use_vorticity != 0;
-   c->cfl = cfg->cfl;
-   c->h1order = (double)cfg->order_v;
    c->q_tiny_grad = c->sw.q_tiny_grad;
    c->q_discard = (c->sw.q_discard == 1) ? (kQDiscardDt | kQDiscardF1) : (c->sw.q_discard == 2) ? kQDiscardDt : (c->sw.q_discard == 3) ? kQDiscardF1 : 0;
    c->q_cF = q_force_bound(cfg);
-   c->stress_store = 1; // (the reference's behaviour: UpdateQuadratureData leaves stressJinvT in memory)
-   c->stress_current = 0;
-   c->h0 = 0.0;
-   c->device = cfg->device;
-   c->cur_ess = -1;
-   c->nranks = 1;
-   c->rank = 0;
-   if (cfg->stream) { c->stream = (hipStream_t)cfg->stream; c->own_stream = false; }
-   else { LGH_HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
-
-   int rc;
-#define LGH_TRY(x) do { rc = (x); if (rc) { return rc; } } while (0)
-   LGH_TRY(dev_alloc_copy(&c->B, cfg->B_h1, (size_t)c->Q1D * c->D1D));
    {
       // mirror symmetry of the tables (every nodal or Bernstein basis on symmetric points has it); LGH_B_SYM=0: assume not
       auto mirror = [&](const double *B, const int n) {
@@ -535,9 +567,6 @@ static int create_impl(const lgh_config *cfg, lgh_ctx *c, const int kid)
       c->b_h1_sym = mirror(cfg->B_h1, c->Q1D * c->D1D);
       c->b_l2_sym = mirror(cfg->B_l2, c->Q1D * c->L1D);
    }
-   LGH_TRY(dev_alloc_copy(&c->G, cfg->G_h1, (size_t)c->Q1D * c->D1D));
-   LGH_TRY(dev_alloc_copy(&c->Bl, cfg->B_l2, (size_t)c->Q1D * c->L1D));
-   LGH_TRY(dev_alloc_copy(&c->W, cfg->weights, (size_t)c->NQ));
    {
       // Tensor-product rule?  w[i] = W[i, 0, 0] / w[0]^(dim - 1) with w[0] = W[0]^(1/dim); every entry of W must be the
       // product of its three factors to 8 ulp.  The plane-form L2 mass apply then takes the weights from Q scalars
@@ -563,12 +592,12 @@ static int create_impl(const lgh_config *cfg, lgh_ctx *c, const int kid)
          const double prod = (dim == 3) ? w1[qx] * w1[qy] * w1[qz] : w1[qx] * w1[qy];
          ok = std::fabs(prod - cfg->weights[q]) <= 1.8e-15 * std::fabs(cfg->weights[q]);
       }
-      if (ok && c->sw.mass_sep) { LGH_TRY(dev_alloc_copy(&c->w1d, w1.data(), (size_t)Q)); } // (LGH_MASS_SEP=0, A/B: weights from the NQ-entry table)
+      if (ok && c->sw.mass_sep) { LGH_PASS(c->w1d.upload(w1.data(), (size_t)Q)); } // (LGH_MASS_SEP=0, A/B: weights from the NQ-entry table)
       // 1-D mass tiles of the two bases on this rule, M1[i + n j] = sum_q B[q, i] w[q] B[q, j] (long double sums, rounded
       // once): with compact mass data the element matrices are s_e M1 (x) M1 (x) M1 (lgh_vcg_slab.hip, lgh_mass.hip)
       if (c->w1d && c->sw.mass_kron) // (LGH_MASS_KRON=0, A/B: always contract through the quadrature points)
       {
-         auto tile = [&](const double *Bt, const int n, double **out) -> int {
+         auto tile = [&](const double *Bt, const int n, DevPtr<double> &out) -> int {
             std::vector<double> M((size_t)n * n);
             for (int i = 0; i < n; i++)
             {
@@ -579,136 +608,66 @@ static int create_impl(const lgh_config *cfg, lgh_ctx *c, const int kid)
                   M[(size_t)i + (size_t)n * j] = (double)s;
                }
             }
-            return dev_alloc_copy(out, M.data(), M.size());
+            return out.upload(M.data(), M.size());
          };
-         LGH_TRY(tile(cfg->B_h1, c->D1D, &c->M1h));
-         LGH_TRY(tile(cfg->B_l2, c->L1D, &c->M1l));
+         LGH_PASS(tile(cfg->B_h1, c->D1D, c->M1h));
+         LGH_PASS(tile(cfg->B_l2, c->L1D, c->M1l));
       }
    }
-   LGH_TRY(dev_alloc_copy(&c->gamma, cfg->gamma, (size_t)c->NE));
    const size_t nmap = (size_t)c->NE * c->ND;
-   LGH_TRY(dev_alloc_copy(&c->h1map, cfg->h1_map, nmap));
-   LGH_TRY(mesh_order_build(c, cfg->h1_map)); // the library's own zone order and node numbering (lgh_order.hip)
-   // transpose of the restriction in CSR form (ascending element order per node)
    {
-      std::vector<int> off((size_t)c->N + 1, 0), idx(nmap);
-      for (size_t i = 0; i < nmap; i++)
-      {
-         const int n = cfg->h1_map[i];
-         if (n < 0 || n >= c->N) { set_error("h1_map entry out of range"); return LGH_ERR_ARG; }
-         off[(size_t)n + 1]++;
-      }
-      for (int n = 0; n < c->N; n++) { off[(size_t)n + 1] += off[n]; }
-      std::vector<int> pos(off.begin(), off.end() - 1);
-      for (size_t i = 0; i < nmap; i++) { idx[pos[cfg->h1_map[i]]++] = (int)i; }
-      LGH_TRY(dev_alloc_copy(&c->t_off, off.data(), off.size()));
-      LGH_TRY(dev_alloc_copy(&c->t_idx, idx.data(), idx.size()));
+      // the transpose in ELL form
       int deg = 0;
       for (int n = 0; n < c->N; n++) { deg = std::max(deg, off[(size_t)n + 1] - off[n]); }
       std::vector<int> ell((size_t)deg * c->N, -1);
       for (int n = 0; n < c->N; n++)
          for (int k = off[n]; k < off[(size_t)n + 1]; k++) { ell[(size_t)(k - off[n]) * c->N + n] = idx[k]; }
       c->t_deg = deg;
-      LGH_TRY(dev_alloc_copy(&c->t_ell, ell.data(), ell.size()));
+      LGH_PASS(ctx_buffer(c->t_ell, ell.size(), ell.data()));
    }
-   for (int k = 0; k < 3; k++)
-   {
-      c->ess_count[k] = (k < dim) ? cfg->ess_count[k] : 0;
-      std::vector<uint8_t> mask((size_t)c->N, 0);
-      for (int i = 0; i < c->ess_count[k]; i++)
-      {
-         const int n = cfg->ess[k][i];
-         if (n < 0 || n >= c->N) { set_error("essential dof out of range"); return LGH_ERR_ARG; }
-         mask[n] = 1;
-      }
-      LGH_TRY(dev_alloc_copy(&c->essmask[k], mask.data(), mask.size()));
-      LGH_TRY(dev_alloc_copy(&c->ess[k], c->ess_count[k] ? cfg->ess[k] : nullptr, (size_t)c->ess_count[k]));
-   }
-   if (cfg->owner) { LGH_TRY(dev_alloc_copy(&c->owner, cfg->owner, (size_t)c->N)); }
+   if (cfg->owner) { LGH_PASS(c->owner.upload(cfg->owner, (size_t)c->N)); }
 
    const size_t nq = (size_t)c->NE * c->NQ;
-   LGH_TRY(dev_alloc_zero(&c->stressJinvT, nq * dim * dim));
-   LGH_TRY(dev_alloc_zero(&c->Jac0inv, nq * dim * dim));
-   LGH_TRY(dev_alloc_zero(&c->Jac0inv_soa, nq * dim * dim));
-   LGH_TRY(dev_alloc_zero(&c->Jac0inv_e, (size_t)cfg->NE * dim * dim));
-   LGH_TRY(dev_alloc_zero(&c->rho0DetJ0w, nq));
-   LGH_TRY(dev_alloc_zero(&c->massD, nq + 2048)); // (one set of the matrix-core K1 behind the last element: its pipeline prefetches without predicates)
-   LGH_TRY(dev_alloc_zero(&c->diagV, (size_t)c->N));
-   LGH_TRY(dev_alloc_zero(&c->dinvV, (size_t)c->N));
-   LGH_TRY(dev_alloc_zero(&c->dt_est_dev, (size_t)kDtSlotStride * (1 + kDtSlots)));
+   LGH_PASS(ctx_buffer(c->stressJinvT, nq * dim * dim));
+   LGH_PASS(ctx_buffer(c->Jac0inv, nq * dim * dim));
+   LGH_PASS(ctx_buffer(c->Jac0inv_soa, nq * dim * dim));
+   LGH_PASS(ctx_buffer(c->Jac0inv_e, (size_t)cfg->NE * dim * dim));
+   LGH_PASS(ctx_buffer(c->rho0DetJ0w, nq));
+   LGH_PASS(ctx_buffer(c->massD, nq + 2048)); // (one set of the matrix-core K1 behind the last element: its pipeline prefetches without predicates)
+   LGH_PASS(ctx_buffer(c->diagV, (size_t)c->N));
+   LGH_PASS(ctx_buffer(c->dinvV, (size_t)c->N));
    {
       if (c->sw.fused_ftv) // (LGH_FUSED_FTV=0, A/B: F^T v always by its own kernel)
       {
-         LGH_TRY(dev_alloc_zero(&c->erhs_q, (size_t)c->L2V));
-         LGH_TRY(dev_alloc_zero(&c->v_snap, (size_t)c->H1V));
+         LGH_PASS(ctx_buffer(c->erhs_q, (size_t)c->L2V));
+         LGH_PASS(ctx_buffer(c->v_snap, (size_t)c->H1V));
       }
-      LGH_TRY(dev_alloc_zero(&c->dev_flags, (size_t)8));
-      c->mass_rank1 = -1;
+      LGH_PASS(ctx_buffer(c->dev_flags, (size_t)8));
       // (LGH_FUSED_F1=0, A/B: F.1 always by its own kernel)
-      if (c->dim == 3 && c->sw.fused_f1) { LGH_TRY(dev_alloc_zero(&c->force_e_q, nmap * dim + (size_t)dim * c->ND)); } // (+ a zero element: vcg_init_force_z_k)
+      if (c->dim == 3 && c->sw.fused_f1) { LGH_PASS(ctx_buffer(c->force_e_q, nmap * dim + (size_t)dim * c->ND)); } // (+ a zero element: vcg_init_force_z_k)
    }
    const size_t ne_nd = nmap * dim;
-   LGH_TRY(dev_alloc_zero(&c->XE, std::max<size_t>(ne_nd, (size_t)c->L2V)));
-   LGH_TRY(dev_alloc_zero(&c->YE, ne_nd + (size_t)dim * c->ND)); // (+ a zero element: vcg_init_force_z_k)
+   LGH_PASS(ctx_buffer(c->XE, std::max<size_t>(ne_nd, (size_t)c->L2V)));
+   LGH_PASS(ctx_buffer(c->YE, ne_nd + (size_t)dim * c->ND)); // (+ a zero element: vcg_init_force_z_k)
    const size_t nv = std::max<size_t>((size_t)c->N, (size_t)c->L2V);
-   LGH_TRY(dev_alloc_zero(&c->cg_r, nv));
-   LGH_TRY(dev_alloc_zero(&c->cg_z, nv));
-   LGH_TRY(dev_alloc_zero(&c->cg_d0, nv));
-   LGH_TRY(dev_alloc_zero(&c->cg_d1, nv));
-   LGH_TRY(dev_alloc_zero(&c->cg_y, nv));
-   c->part_stride = (int)std::max<size_t>(std::max<size_t>((size_t)c->NE, (nv + 255) / 256), 2048) + (int)kShards;
-   LGH_TRY(dev_alloc_zero(&c->partials, 4 * (size_t)c->part_stride));
-   LGH_TRY(dev_alloc_zero(&c->tickets, 4 * (size_t)kTicketSlot));
-   LGH_TRY(dev_alloc_zero(&c->cgs, 1));
-   LGH_TRY(dev_alloc_zero(&c->scal, 16));
-   LGH_HIP_CHECK(hipHostMalloc((void **)&c->host_pinned, kPinDoubles * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-   memset(c->host_pinned, 0, kPinDoubles * sizeof(double));
-   LGH_HIP_CHECK(hipHostGetDevicePointer((void **)&c->host_pinned_dev, c->host_pinned, 0)); // (the one-thread kernels in front of a host look write there)
-   LGH_HIP_CHECK(hipEventCreate(&c->timers.ev[0]));
-   LGH_HIP_CHECK(hipEventCreate(&c->timers.ev[1]));
-   {
-      const std::vector<double> infs((size_t)kDtSlotStride * (1 + kDtSlots), std::numeric_limits<double>::infinity());
-      LGH_HIP_CHECK(hipMemcpy(c->dt_est_dev, infs.data(), infs.size() * sizeof(double), hipMemcpyHostToDevice));
-   }
-#undef LGH_TRY
+   LGH_PASS(ctx_buffer(c->cg_r, nv));
+   LGH_PASS(ctx_buffer(c->cg_z, nv));
+   LGH_PASS(ctx_buffer(c->cg_d0, nv));
+   LGH_PASS(ctx_buffer(c->cg_d1, nv));
+   LGH_PASS(ctx_buffer(c->cg_y, nv));
    return LGH_OK;
 }
+
+lgh_ctx::lgh_ctx() = default;
+lgh_ctx::~lgh_ctx() = default;
 
 int lgh_destroy(lgh_ctx *c)
 {
    if (!c) { return LGH_OK; }
    (void)hipSetDevice(c->device);
    (void)hipStreamSynchronize(c->stream);
-   void *ptrs[] = {c->B, c->G, c->Bl, c->W, c->w1d, c->M1h, c->M1l, c->gamma, c->h1map, c->t_off, c->t_idx, c->t_ell, c->essmask[0],
-                   c->essmask[1], c->essmask[2], c->ess[0], c->ess[1], c->ess[2], c->owner,
-                   c->stressJinvT, c->Jac0inv, c->Jac0inv_soa, c->Jac0inv_e, c->rho0DetJ0w, c->massD, c->diagV, c->dinvV,
-                   c->dt_est_dev, c->erhs_q, c->v_snap, c->dev_flags, c->ones_l2, c->massS, c->ones_ne, c->force_e_q, c->XE, c->YE, c->cg_r, c->cg_z, c->cg_d0, c->cg_d1, c->cg_y,
-                   c->partials, c->tickets, c->cgs, c->scal, c->vcg_s, c->vcg_vec, c->vcg_partials,
-                   c->vcg_tickets, c->me_fac, c->fp_dev, c->diag_dev, c->prof_dev, c->map_dev};
-   for (void *p : ptrs) { if (p) { (void)hipFree(p); } }
-   if (c->host_pinned) { (void)hipHostFree(c->host_pinned); }
-   if (c->timers.ev[0]) { (void)hipEventDestroy(c->timers.ev[0]); }
-   if (c->timers.ev[1]) { (void)hipEventDestroy(c->timers.ev[1]); }
-   if (c->ktime)
-   {
-      for (hipEvent_t e : c->ktime->ev) { (void)hipEventDestroy(e); }
-      delete c->ktime;
-   }
-   cg_l2_free(c);
-   vcg_free(c);
-   mesh_order_free(c);
-   if (c->q_trace_dev) { (void)hipFree(c->q_trace_dev); }
-   if (c->stream2)
-   {
-      (void)hipStreamSynchronize(c->stream2);
-      (void)hipStreamDestroy(c->stream2);
-      if (c->ev_fork) { (void)hipEventDestroy(c->ev_fork); } // (create_stream2 may have failed between the stream and its events)
-      if (c->ev_join) { (void)hipEventDestroy(c->ev_join); }
-   }
-   extern void lgh_comm_free(lgh_ctx *);
-   lgh_comm_free(c);
-   if (c->own_stream) { (void)hipStreamDestroy(c->stream); }
-   delete c;
+   if (c->stream2) { (void)hipStreamSynchronize(c->stream2); }
+   delete c; // every member releases what it owns (lgh_common.hpp)
    return LGH_OK;
 }
 
@@ -998,7 +957,7 @@ static int one_vector(lgh_ctx *c, const double *one_l2, const double **out)
    if (one_l2) { *out = one_l2; return LGH_OK; }
    if (!c->ones_l2)
    {
-      LGH_HIP_CHECK(hipMalloc((void **)&c->ones_l2, sizeof(double) * (size_t)c->L2V));
+      LGH_PASS(c->ones_l2.alloc((size_t)c->L2V));
       const int rc = vec_set(c, c->ones_l2, 1.0, c->L2V);
       if (rc) { return rc; }
    }
@@ -1229,8 +1188,8 @@ int lgh_enable_timers(lgh_ctx *c, int on)
 int lgh_ktime_begin(lgh_ctx *c, int which, int max_samples)
 {
    LGH_CHECK_ARG(c && which >= 0 && max_samples > 0);
-   if (!c->ktime) { c->ktime = new KTime(); }
-   KTime *k = c->ktime;
+   if (!c->ktime) { c->ktime.reset(new KTime()); }
+   KTime *k = c->ktime.get();
    while ((int)k->ev.size() < 2 * max_samples)
    {
       hipEvent_t e;
@@ -1245,7 +1204,7 @@ int lgh_ktime_begin(lgh_ctx *c, int which, int max_samples)
 int lgh_ktime_end(lgh_ctx *c, int *launches, double *mean_seconds)
 {
    LGH_CHECK_ARG(c && launches && mean_seconds && c->ktime);
-   KTime *k = c->ktime;
+   KTime *k = c->ktime.get();
    LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
    double tot = 0.0;
    for (int i = 0; i < k->n; i++)

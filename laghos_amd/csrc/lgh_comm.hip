@@ -96,7 +96,7 @@ bool halo_can_piggyback(const lgh_ctx *c)
 // lgh_order.hip) - the same node lists in THAT numbering; everything else of the exchange does not know about numbers
 int halo_sum(lgh_ctx *c, double *v, int ncomp, double *extra, int nextra, bool packed, const HaloNodeAlias *alias)
 {
-   Comm *cm = c->comm;
+   Comm *cm = c->comm.get();
    if (!cm || cm->tab.n_nbr == 0) { return LGH_OK; }
    const HaloTables &t = cm->tab;
    const int *const l_nodes = alias ? alias->nodes : t.nodes.p, *const l_sh_node = alias ? alias->sh_node : t.sh_node.p;
@@ -132,7 +132,7 @@ bool comm_second_channel(const lgh_ctx *c) { return c->comm && c->comm->channel2
 
 bool comm_pack_tables(const lgh_ctx *c, HaloPackTables *t)
 {
-   const Comm *cm = c->comm;
+   const Comm *cm = c->comm.get();
    if (!cm || cm->tab.n_nbr == 0 || !cm->tab.sh_off || !cm->tab.sendbuf[0]) { return false; }
    t->sh_off = cm->tab.sh_off; t->sh_src = cm->tab.sh_src; t->pos = cm->tab.pos; t->cnt = cm->tab.cnt;
    t->base = cm->tab.d_base; t->ncnt = cm->tab.d_cnt; t->sbuf = cm->tab.sendbuf[0]; t->n_nbr = cm->tab.n_nbr;
@@ -142,7 +142,7 @@ bool comm_pack_tables(const lgh_ctx *c, HaloPackTables *t)
 // the node lists of the exchanges (device, the caller's numbering): concatenated neighbour lists, unique shared nodes
 void comm_node_lists(const lgh_ctx *c, const int **nodes, int *total, const int **sh_node, int *n_shared)
 {
-   const Comm *cm = c->comm;
+   const Comm *cm = c->comm.get();
    *nodes = cm ? cm->tab.nodes.p : nullptr;
    *total = cm ? cm->tab.total : 0;
    *sh_node = cm ? cm->tab.sh_node.p : nullptr;
@@ -152,7 +152,7 @@ void comm_node_lists(const lgh_ctx *c, const int **nodes, int *total, const int 
 // lower and the higher peers' blocks" is then not the rank-ordered sum every rank must form alike)
 int comm_ranks_before(const lgh_ctx *c)
 {
-   const Comm *cm = c->comm;
+   const Comm *cm = c->comm.get();
    int n = 0;
    if (cm)
    {
@@ -166,7 +166,7 @@ int comm_ranks_before(const lgh_ctx *c)
 }
 void comm_shared_nodes(const lgh_ctx *c, const uint8_t **hmask, const int **sh_node, int *n_shared)
 {
-   const Comm *cm = c->comm;
+   const Comm *cm = c->comm.get();
    *hmask = cm ? cm->tab.hmask.p : nullptr;
    *sh_node = cm ? cm->tab.sh_node.p : nullptr;
    *n_shared = (cm && cm->tab.hmask) ? cm->tab.n_shared : 0;
@@ -174,7 +174,7 @@ void comm_shared_nodes(const lgh_ctx *c, const uint8_t **hmask, const int **sh_n
 
 int comm_word_peers(lgh_ctx *c, int nwords, const long long **peers, int *n_peers)
 {
-   Comm *cm = c->comm;
+   Comm *cm = c->comm.get();
    *peers = nullptr;
    *n_peers = 0;
    if (!cm || cm->tab.n_nbr == 0) { return LGH_OK; } // (a communicator of size 1: nobody to hear from)
@@ -182,7 +182,6 @@ int comm_word_peers(lgh_ctx *c, int nwords, const long long **peers, int *n_peer
    if (!cm->tab.allpairs) { set_error("comm_word_peers: all-pairs partitions only"); return LGH_ERR_ARG; }
    if (cm->wordcap != nwords || cm->wordnbr != n_nbr) // (sized by BOTH factors)
    {
-      cm->wordbuf = DevPtr<long long>();
       cm->wordcap = 0;
       LGH_COMM_TRY(cm->wordbuf.alloc((size_t)n_nbr * nwords, true));
       cm->wordcap = nwords;
@@ -195,7 +194,7 @@ int comm_word_peers(lgh_ctx *c, int nwords, const long long **peers, int *n_peer
 
 int exchange_words(lgh_ctx *c, const long long *src, int nwords)
 {
-   Comm *cm = c->comm;
+   Comm *cm = c->comm.get();
    if (!cm || cm->tab.n_nbr == 0) { return LGH_OK; }
    if (!cm->tab.allpairs || !cm->wordbuf || cm->wordcap != nwords || cm->wordnbr != cm->tab.n_nbr || c->on_stream2) { set_error("exchange_words: all-pairs partition, main channel, peer buffer of %d words", nwords); return LGH_ERR_ARG; }
    if (!cm->transport) { set_error("exchange_words: neighbour lists without a communicator (lgh_comm_init)"); return LGH_ERR_COMM; }
@@ -205,7 +204,7 @@ int exchange_words(lgh_ctx *c, const long long *src, int nwords)
 
 int allreduce_dev(lgh_ctx *c, double *dev, int count, int op, bool packed)
 {
-   Comm *cm = c->comm;
+   Comm *cm = c->comm.get();
    // Sums of up to three scalars in an all-pairs partition (the CG dot products on <= 2x2x2 ranks):
    // one grouped exchange with every peer and a sum in rank order, the transport of the halo
    // messages, instead of a ring / tree all-reduce - one hop, bit-identical on every rank.
@@ -221,7 +220,7 @@ int allreduce_dev(lgh_ctx *c, double *dev, int count, int op, bool packed)
 // Any number of values, in pieces of what the transport takes at a time
 int allreduce_dev_n(lgh_ctx *c, double *dev, long count, int op)
 {
-   const Comm *cm = c->comm;
+   const Comm *cm = c->comm.get();
    const long piece = (cm && cm->transport) ? cm->transport->allreduce_max() : (1L << 24);
    for (long i = 0; i < count; i += piece)
    {
@@ -352,13 +351,6 @@ using namespace lgh;
 extern "C"
 {
 
-void lgh_comm_free(lgh_ctx *c)
-{
-   if (!c) { return; }
-   delete c->comm; // (the transport closes first, then the buffers go: the order of Comm's members)
-   c->comm = nullptr;
-}
-
 int lgh_comm_unique_id(char id_out[128])
 {
    LGH_CHECK_ARG(id_out);
@@ -382,7 +374,7 @@ int lgh_comm_init(lgh_ctx *c, int nranks, int rank, const char unique_id[128])
       set_error("lgh_comm_init: a 1D context runs on one rank (several ranks are not supported in 1D)");
       return LGH_ERR_UNSUPPORTED;
    }
-   if (!c->comm) { c->comm = new Comm(); }
+   if (!c->comm) { c->comm.reset(new Comm()); }
    OpenedTransport o;
    if (memcmp(unique_id, "LGHSHM", 6) == 0) { LGH_COMM_TRY(open_shm(c, nranks, rank, unique_id, o)); } // cross-process loopback (bench.py --transport shm, tests)
    else if (memcmp(unique_id, "LGHLOCAL", 8) == 0) { LGH_COMM_TRY(open_local(c, nranks, rank, unique_id, o)); } // in-process loopback (tests)
@@ -399,7 +391,7 @@ int lgh_comm_init(lgh_ctx *c, int nranks, int rank, const char unique_id[128])
 int lgh_comm_stats(lgh_ctx *c, int *n_neighbours, long *max_nodes_per_neighbour, long *shared_nodes, int *all_pairs, int *second_channel)
 {
    LGH_CHECK_ARG(c && n_neighbours && max_nodes_per_neighbour && shared_nodes && all_pairs && second_channel);
-   const Comm *cm = c->comm;
+   const Comm *cm = c->comm.get();
    *n_neighbours = cm ? cm->tab.n_nbr : 0;
    long mx = 0;
    if (cm) { for (int k = 0; k < cm->tab.n_nbr; k++) { mx = std::max(mx, (long)cm->tab.nbr_count[k]); } }
@@ -414,8 +406,8 @@ int lgh_comm_set_neighbors(lgh_ctx *c, int n_nbr, const int *nbr_rank, const int
                            const int *const *nbr_nodes)
 {
    LGH_CHECK_ARG(c && n_nbr >= 0);
-   if (!c->comm) { c->comm = new Comm(); }
-   Comm *cm = c->comm;
+   if (!c->comm) { c->comm.reset(new Comm()); }
+   Comm *cm = c->comm.get();
    // Everything that can fail locally (argument checks, allocations) runs first and its status is folded
    // into the collective below: a rank that fails must not leave its peers blocked in the all-reduce.
    HaloTables t;
@@ -442,7 +434,7 @@ int lgh_comm_set_neighbors(lgh_ctx *c, int n_nbr, const int *nbr_rank, const int
    // Publication: the tables change hands whole (the previous ones leave with t), and what was built for them goes -
    // the peer buffer of exchange_words, sized by the neighbour count, and the flag bytes of the node kernel K2
    cm->tab = std::move(t);
-   cm->wordbuf = DevPtr<long long>();
+   cm->wordbuf.reset();
    cm->wordcap = 0;
    cm->word_src = nullptr;
    vcg_free(c);
@@ -463,7 +455,7 @@ int lgh_test_word_peers(lgh_ctx *c, int nwords, long *capacity_words)
    int n_peers = 0;
    const int rc = comm_word_peers(c, nwords, &peers, &n_peers);
    if (rc) { return rc; }
-   const Comm *cm = c->comm;
+   const Comm *cm = c->comm.get();
    *capacity_words = (cm && cm->wordbuf) ? (long)cm->wordnbr * cm->wordcap : 0;
    if (peers) { LGH_HIP_CHECK(hipMemset((void *)peers, 0, (size_t)n_peers * nwords * sizeof(long long))); } // (writes the whole buffer: a short one faults here)
    return (cm && cm->wordbuf && cm->wordnbr == n_peers && cm->wordcap == nwords) || n_peers == 0 ? LGH_OK : LGH_ERR_COMM;

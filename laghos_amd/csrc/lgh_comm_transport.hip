@@ -115,7 +115,7 @@ struct RcclTransport : Transport
    }
    int exchange_words(lgh_ctx *c, const long long *src, int nwords) override
    {
-      const Comm *cm = c->comm;
+      const Comm *cm = c->comm.get();
       LGH_NCCL_CHECK(g_nccl.GroupStart());
       for (int k = 0; k < cm->tab.n_nbr; k++)
       {
@@ -362,12 +362,12 @@ struct LocalTransport : Loopback
    }
    int exchange_words(lgh_ctx *c, const long long *src, int nwords) override
    {
-      Comm *cm = c->comm;
+      Comm *cm = c->comm.get();
       cm->word_src = src;
       return bracket(c, "words", "", [] { return LGH_OK; }, [&]() -> int {
          for (int k = 0; k < cm->tab.n_nbr; k++)
          {
-            const Comm *pc = g->ctx[cm->tab.nbr_rank[k]]->comm;
+            const Comm *pc = g->ctx[cm->tab.nbr_rank[k]]->comm.get();
             if (!pc->word_src) { set_error("local communicator: rank %d exchanges no words", cm->tab.nbr_rank[k]); return LGH_ERR_COMM; }
             LGH_HIP_CHECK(hipMemcpyAsync(cm->wordbuf + (size_t)k * nwords, pc->word_src, (size_t)nwords * sizeof(long long), hipMemcpyDeviceToDevice, c->stream));
          }
@@ -559,7 +559,7 @@ struct ShmTransport : Loopback
    }
    int exchange_words(lgh_ctx *c, const long long *src, int nwords) override
    {
-      const Comm *cm = c->comm;
+      const Comm *cm = c->comm.get();
       const int n_nbr = cm->tab.n_nbr;
       const size_t bytes = (size_t)nwords * sizeof(long long);
       if (bytes > g.hdr()->cap) { set_error("shm transport: %zu bytes of words, room for %zu", bytes, g.hdr()->cap); return LGH_ERR_COMM; }

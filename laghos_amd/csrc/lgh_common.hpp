@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -39,31 +40,49 @@ void set_error(const char *fmt, ...);
       }                                                                                  \
    } while (0)
 
+#define LGH_PASS(call) do { const int rc_ = (call); if (rc_ != LGH_OK) { return rc_; } } while (0) // an LGH_* status: passed on
+
 constexpr int kWave = 64;          // gfx950 wavefront
 
-// one device allocation, freed with its owner (move-only)
+// One device allocation, freed with its owner (move-only): the only place of the library that allocates or frees device
+// memory.  alloc and upload release what the pointer holds first, so a buffer regrows by calling them again.
 template <typename T> struct DevPtr
 {
    T *p = nullptr;
    DevPtr() = default;
    DevPtr(DevPtr &&o) noexcept : p(o.p) { o.p = nullptr; } // (declaring the moves deletes the copies)
    DevPtr &operator=(DevPtr &&o) noexcept { std::swap(p, o.p); return *this; }
-   ~DevPtr() { (void)hipFree(p); }
+   ~DevPtr() { reset(); }
    operator T *() const { return p; }
-   T **out() { return &p; }              // for the builders that allocate (make_ellz, ...)
+   T *operator->() const { return p; }
+   void reset() { if (p) { (void)hipFree(p); p = nullptr; } } // (an empty one never touches the runtime: host-only entry points hold some)
    int alloc(const size_t n, const bool zero = false) // n elements, uninitialised or zero
    {
+      reset();
       LGH_HIP_CHECK(hipMalloc((void **)&p, n * sizeof(T)));
-      if (zero) { LGH_HIP_CHECK(hipMemset(p, 0, n * sizeof(T))); }
+      if (zero)
+      {
+         LGH_HIP_CHECK(hipMemset(p, 0, n * sizeof(T)));
+         LGH_HIP_CHECK(hipStreamSynchronize(nullptr)); // (the fill runs on the null stream; a context's stream does not wait for it)
+      }
       return LGH_OK;
    }
    int upload(const T *host, const size_t n) // n elements, copied from the host
    {
-      LGH_HIP_CHECK(hipMalloc((void **)&p, n * sizeof(T)));
+      const int rc = alloc(n);
+      if (rc != LGH_OK) { return rc; }
       LGH_HIP_CHECK(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
       return LGH_OK;
    }
 };
+// a buffer of a context's set-up: at least one element, so never null; copied from `src`, or zero without one
+template <typename T> int ctx_buffer(DevPtr<T> &d, const size_t n, const T *src = nullptr)
+{
+   const int rc = d.alloc(std::max<size_t>(n, 1), !src);
+   if (rc != LGH_OK || !src || !n) { return rc; }
+   LGH_HIP_CHECK(hipMemcpy(d.p, src, n * sizeof(T), hipMemcpyHostToDevice));
+   return LGH_OK;
+}
 
 // Device-resident scalars of one CG solve (SURVEY §3.2 names).
 struct CgScalars
@@ -96,6 +115,10 @@ struct Timers
 {
    bool enabled = true;
    hipEvent_t ev[2] = {nullptr, nullptr};
+   Timers() = default;
+   Timers(const Timers &) = delete;
+   Timers &operator=(const Timers &) = delete;
+   ~Timers() { for (hipEvent_t e : ev) { if (e) { (void)hipEventDestroy(e); } } }
    double t[4] = {0, 0, 0, 0}; // cgH1, cgL2, force, qdata (seconds)
    long c[3] = {0, 0, 0};      // H1iter, L2iter, quad_tstep
 };
@@ -105,9 +128,15 @@ struct KTime
 {
    int which = -1, max = 0, n = 0;
    std::vector<hipEvent_t> ev; // 2 per sample
+   KTime() = default;
+   KTime(const KTime &) = delete;
+   KTime &operator=(const KTime &) = delete;
+   ~KTime() { for (hipEvent_t e : ev) { (void)hipEventDestroy(e); } }
 };
 
-struct Comm; // several ranks: the transport and the neighbour tables (lgh_comm_transport.hpp)
+struct Comm;       // several ranks: the transport and the neighbour tables (lgh_comm_transport.hpp)
+struct VcgScalars; // the device scalars of the velocity CG (lgh_vcg.hpp)
+struct VcgAux;     // ... and the tables of its node kernel K2
 
 // The library's own order of the zones and numbering of the nodes (lgh_order.hip): found from the element -> node map at
 // lgh_create by face adjacency, nothing about the caller's numbering is assumed.  identity: the caller's order already is
@@ -119,7 +148,7 @@ struct MeshOrder
    std::vector<int> zorder;   // internal zone i is the caller's zone zorder[i]
    std::vector<int> nnum;     // the caller's node n is internal node nnum[n]
    std::vector<int> ncaller;  // internal node m is the caller's node ncaller[m]
-   int *zorder_d = nullptr, *ncaller_d = nullptr, *nnum_d = nullptr; // the same on the device (nullptr when identity)
+   DevPtr<int> zorder_d, ncaller_d, nnum_d; // the same on the device (nullptr when identity)
 };
 
 constexpr double kMassRank1Tol = 1e-12; // relative spread of D / W inside an element up to which the mass data counts as W[q] s_e (mass_rank1_k)
@@ -161,6 +190,7 @@ struct Switches
 Switches read_switches();
 
 struct ScalarCg; // one scalar CG solve: what its kernels are launched with, how far it has been enqueued (lgh_scg.hip)
+void cg_l2_free(ScalarCg *r);
 
 // The energy solve between lgh_solve_energy_begin and _end (lgh_energy.hip): which way _begin took, and what _end needs for it.
 struct EnergySolve
@@ -178,120 +208,137 @@ struct EnergySolve
    struct { const double *S, *v; double *dS, *e_rhs; const double *src; double tol; int maxit; } args = {}; // Deferred
 };
 
+// What a context holds that is not device memory: its streams, the events between them and the pinned block.  The energy
+// solve swaps `stream` and `stream2` while it runs, so they stay plain handles; they are released here, in the destructor
+// of lgh_ctx's base - after every member of lgh_ctx, so after everything that could still be enqueued on an owned stream.
+struct CtxHandles
+{
+   int device = 0;
+   hipStream_t stream = nullptr;
+   bool own_stream = false;
+   // second stream + fork/join events: the energy solve overlaps the velocity solve (lgh_energy.hip)
+   hipStream_t stream2 = nullptr;
+   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+   double *host_pinned = nullptr;     // pinned host staging, kPinDoubles doubles; its slots: kPin*
+   double *host_pinned_dev = nullptr; // the same memory as the device addresses it: scalars a host look needs are written there by the kernel that
+                                      // finishes them (no copy kernel between it and the stream synchronisation)
+   CtxHandles() = default;
+   CtxHandles(const CtxHandles &) = delete;
+   CtxHandles &operator=(const CtxHandles &) = delete;
+   ~CtxHandles();
+};
+
 } // namespace lgh
 
-struct lgh_ctx
+// One context.  Every device buffer is a DevPtr of its element type and every other resource has an owner of its own, so
+// deleting the context releases all of it, members in reverse order of declaration, then the base: nothing is freed by
+// name anywhere (lgh_destroy).  A new buffer is a DevPtr member and an alloc / upload call where it is first needed.
+// Buffers that code branches on (owner, w1d, M1h, M1l, erhs_q, v_snap, force_e_q, the first-use ones) are null until built.
+struct lgh_ctx : lgh::CtxHandles
 {
+   lgh_ctx();
+   ~lgh_ctx(); // (out of line, lgh_api.hip: where Comm, VcgAux and MeshOrder are complete types)
    lgh::Switches sw;     // the environment switches as they were at lgh_create
-   int dim, NE, D1D, Q1D, L1D, ND, NQ, NL, N, H1V, L2V;
-   int kid; // (dim<<8)|(D1D<<4)|Q1D, the reference's kernel id
-   bool visc, vort;
-   double cfl, h0, h1order;
-   double q_tiny_grad;   // QUpdate: threshold of the wave-uniform eigen-decomposition shortcut (lgh_qupdate.hip)
-   int q_discard;        // QUpdate: which provably unused work is skipped (kQDiscardDt | kQDiscardF1, lgh_qpoint.hpp; LGH_Q_DISCARD)
-   double q_cF;          // ... C_F = 3 cG cB^2: |F.1 output| <= C_F max|stressJinvT w detJ| of the zone (q_force_bound, lgh_api.hip)
-   int device;
-   hipStream_t stream;
-   // second stream + fork/join events: the energy solve overlaps the velocity solve (lgh_energy.hip)
-   hipStream_t stream2;
-   int on_stream2;       // 1 while `stream` holds the second stream (energy solve beside the velocity solve): reductions use the communicator's second channel
-   hipEvent_t ev_fork, ev_join;
-   lgh::ScalarCg *l2run = nullptr; // the run of a split L2 solve (lgh_scg.hip: cg_l2_begin .. cg_l2_end, cg_l2_free), allocated on first use
-   const double *accel_src; // dim*N acceleration source of SolveVelocity (source_type 2) or nullptr
+   int dim = 0, NE = 0, D1D = 0, Q1D = 0, L1D = 0, ND = 0, NQ = 0, NL = 0, N = 0, H1V = 0, L2V = 0;
+   int kid = 0; // (dim<<8)|(D1D<<4)|Q1D, the reference's kernel id
+   bool visc = false, vort = false;
+   double cfl = 0.0, h0 = 0.0, h1order = 0.0;
+   double q_tiny_grad = 0.0;   // QUpdate: threshold of the wave-uniform eigen-decomposition shortcut (lgh_qupdate.hip)
+   int q_discard = 0;      // QUpdate: which provably unused work is skipped (kQDiscardDt | kQDiscardF1, lgh_qpoint.hpp; LGH_Q_DISCARD)
+   double q_cF = 0.0;      // ... C_F = 3 cG cB^2: |F.1 output| <= C_F max|stressJinvT w detJ| of the zone (q_force_bound, lgh_api.hip)
+   int on_stream2 = 0;     // 1 while `stream` holds the second stream (energy solve beside the velocity solve): reductions use the communicator's second channel
+   std::unique_ptr<lgh::ScalarCg, void (*)(lgh::ScalarCg *)> l2run{nullptr, lgh::cg_l2_free}; // the run of a split L2 solve (lgh_scg.hip: cg_l2_begin .. cg_l2_end, cg_l2_free), allocated on first use
+   const double *accel_src = nullptr; // dim*N acceleration source of SolveVelocity (source_type 2) or nullptr
    lgh::EnergySolve energy; // the energy solve lgh_solve_energy_begin has begun
    long ls_stats[3] = {0, 0, 0}; // lockstep energy solves; their iterations enqueued inside the velocity solve; ... and after it (lgh_energy_lockstep_stats)
-   bool own_stream;
 
    // tables (device): B_h1/G_h1 [q + Q*d], B_l2 [q + Q*l], weights [NQ]
-   double *B, *G, *Bl, *W, *gamma;
+   lgh::DevPtr<double> B, G, Bl, W, gamma;
    // element restriction: gather map, and its transpose in CSR form
-   int *h1map;   // NE*ND
-   int *t_off;   // N+1   (CSR transpose, used by the multi-component force gather)
-   int *t_idx;   // NE*ND: E-vector positions (e*ND + d) contributing to node
-   int *t_ell;   // t_deg*N: the same in ELL format, [k*N + n], -1 = none
-   int t_deg;    // max contributions per node (8 for hexes, 4 for quads)
-   uint8_t *essmask[3]; // N each (0/1)
-   int *ess[3];
-   int ess_count[3];
-   double *owner; // N or nullptr
-   int cur_ess;
+   lgh::DevPtr<int> h1map;  // NE*ND
+   lgh::DevPtr<int> t_off;  // N+1   (CSR transpose, used by the multi-component force gather)
+   lgh::DevPtr<int> t_idx;  // NE*ND: E-vector positions (e*ND + d) contributing to node
+   lgh::DevPtr<int> t_ell;  // t_deg*N: the same in ELL format, [k*N + n], -1 = none
+   int t_deg = 0;  // max contributions per node (8 for hexes, 4 for quads)
+   lgh::DevPtr<uint8_t> essmask[3]; // N each (0/1)
+   lgh::DevPtr<int> ess[3];
+   int ess_count[3] = {0, 0, 0};
+   lgh::DevPtr<double> owner; // N or nullptr
+   int cur_ess = -1;
 
    // QuadratureData + mass PA data
-   double *stressJinvT, *Jac0inv, *rho0DetJ0w, *massD, *diagV, *dinvV;
-   double *Jac0inv_soa;  // plane-major copy of Jac0inv for coalesced reads in QUpdate
-   double *Jac0inv_e;    // dim*dim per zone: Jac0inv where it is the same at every point of a zone (an affine initial zone; jac0_compact)
-   int jac0_compact;     // 1: the row-form update reads Jac0inv_e (checked at lgh_setup_rho0detj0), 0: the point values
+   lgh::DevPtr<double> stressJinvT, Jac0inv, rho0DetJ0w, massD, diagV, dinvV;
+   lgh::DevPtr<double> Jac0inv_soa; // plane-major copy of Jac0inv for coalesced reads in QUpdate
+   lgh::DevPtr<double> Jac0inv_e; // dim*dim per zone: Jac0inv where it is the same at every point of a zone (an affine initial zone; jac0_compact)
+   int jac0_compact = 0; // 1: the row-form update reads Jac0inv_e (checked at lgh_setup_rho0detj0), 0: the point values
    // Rank-1 form of the mass data: where detJ0 and rho0 are constant inside every element (affine elements, piecewise
    // constant density - every mesh and problem of data/), massD[q + NQ e] = W[q] * massS[e] to the last bit or two;
    // the mass kernels then read 8 bytes per element instead of 8 NQ.  -1: not looked at yet (set-up, lgh_mass_D handed
    // out), 0: no (massD as stored), 1: yes (lgh_mass.hip mass_data).  LGH_MASS_RANK1=0 keeps massD.
-   double *massS, *ones_ne;
-   double *M1h = nullptr, *M1l = nullptr; // 1-D mass tiles B^T diag(w1d) B of the H1 (D1D x D1D) and L2 (L1D x L1D) bases: the Kronecker form of the
-                                          // mass operators for compact mass data on a tensor-product rule (nullptr: no such rule, or LGH_MASS_KRON=0)
-   double *w1d = nullptr;   // one-dimensional weights when the rule is a tensor product, W[qx + Q (qy + Q qz)] = w[qx] w[qy] w[qz] (checked by lgh_create; nullptr otherwise)
-   int mass_rank1;
-   double *dt_est_dev;   // running min of the point-wise estimate: [0] the estimate, then kDtSlots partial minima 128 bytes apart (the row-form
-                         // update sends its candidates there by non-returning atomic min; lgh_get_dt_est folds them into [0])
+   lgh::DevPtr<double> massS, ones_ne;
+   lgh::DevPtr<double> M1h, M1l; // 1-D mass tiles B^T diag(w1d) B of the H1 (D1D x D1D) and L2 (L1D x L1D) bases: the Kronecker form of the
+                                 // mass operators for compact mass data on a tensor-product rule (nullptr: no such rule, or LGH_MASS_KRON=0)
+   lgh::DevPtr<double> w1d; // one-dimensional weights when the rule is a tensor product, W[qx + Q (qy + Q qz)] = w[qx] w[qy] w[qz] (checked by lgh_create; nullptr otherwise)
+   int mass_rank1 = -1;
+   lgh::DevPtr<double> dt_est_dev; // running min of the point-wise estimate: [0] the estimate, then kDtSlots partial minima 128 bytes apart (the row-form
+                                   // update sends its candidates there by non-returning atomic min; lgh_get_dt_est folds them into [0])
    // Force products formed inside the fused QUpdate.  Validity is by construction, not by address: `fused_*_valid` says
    // that the product belongs to the quadrature data as it stands (set by lgh_qupdate, cleared by everything that can
    // change stressJinvT: lgh_reset_quadrature_data, lgh_qdata_stressJinvT, lgh_set_fused_forces, the set-up), and
    // F^T v is only used for a velocity that compares equal, element for element, to the one it was formed from.
-   double *erhs_q;       // L2V: F^T v of ...
-   double *v_snap;       // ... H1V: the velocity block of the state of the last lgh_qupdate (copy)
-   double *force_e_q;    // NE*ND*dim: F.1 as E-vector (3D)
-   int fused_ftv_valid, fused_f1_valid;
-   unsigned long qgen;   // counts lgh_qupdate / invalidations (lgh_quadrature_generation)
-   int *dev_flags;       // 8 device ints, one owner each: [0] / [2] "v differs from v_snap" of the current lgh_solve_energy (main /
-                         // second stream), [1] "x differs from ones" of lgh_force_mult, [3] "mass table is not W[q]*s_e" (mass_data),
-                         // [4] "an energy right-hand side was poisoned" (erhs_take_or_poison_k; read and cleared by lgh_get_dt_est),
-                         // [5] "Jac0inv varies inside a zone" (jac0_compact_k, lgh_setup_rho0detj0)
-   double *ones_l2;      // L2V ones: the operator's own `one` (laghos_solver.cpp:170-171), allocated on first use
-   int stress_store;            // lgh_qupdate_store_stress: 1 (default) = lgh_qupdate writes the nine stressJinvT planes; 0 = the stress stays in registers
-   int stress_current;          // stressJinvT holds the stress of the current quadrature data (consumers refuse it otherwise)
-   int fused_forces_off;        // lgh_set_fused_forces(ctx, 0): the update forms no force products (measurement / A-B)
+   lgh::DevPtr<double> erhs_q; // L2V: F^T v of ...
+   lgh::DevPtr<double> v_snap; // ... H1V: the velocity block of the state of the last lgh_qupdate (copy)
+   lgh::DevPtr<double> force_e_q; // NE*ND*dim: F.1 as E-vector (3D)
+   int fused_ftv_valid = 0, fused_f1_valid = 0;
+   unsigned long qgen = 0; // counts lgh_qupdate / invalidations (lgh_quadrature_generation)
+   lgh::DevPtr<int> dev_flags; // 8 device ints, one owner each: [0] / [2] "v differs from v_snap" of the current lgh_solve_energy (main /
+                               // second stream), [1] "x differs from ones" of lgh_force_mult, [3] "mass table is not W[q]*s_e" (mass_data),
+                               // [4] "an energy right-hand side was poisoned" (erhs_take_or_poison_k; read and cleared by lgh_get_dt_est),
+                               // [5] "Jac0inv varies inside a zone" (jac0_compact_k, lgh_setup_rho0detj0)
+   lgh::DevPtr<double> ones_l2; // L2V ones: the operator's own `one` (laghos_solver.cpp:170-171), allocated on first use
+   int stress_store = 1; // lgh_qupdate_store_stress: 1 (default) = lgh_qupdate writes the nine stressJinvT planes; 0 = the stress stays in registers
+   int stress_current = 0; // stressJinvT holds the stress of the current quadrature data (consumers refuse it otherwise)
+   int fused_forces_off = 0; // lgh_set_fused_forces(ctx, 0): the update forms no force products (measurement / A-B)
    // scratch
-   double *XE;           // max(L2V, NE*ND*dim)
-   double *YE;           // NE*ND*dim
-   double *cg_r, *cg_z, *cg_d0, *cg_d1, *cg_y; // max(N, L2V)
-   double *partials;     // 4 reduction slots of part_stride block partials each
-   int part_stride;      // slot size: >= max #blocks of any reducing launch + kShards
-   unsigned int *tickets;// 4 reduction slots of lgh::kTicketSlot counters (sharded tickets)
-   lgh::CgScalars *cgs;  // device
-   double *scal;         // small device scalar pool (16 doubles)
-   double *host_pinned;  // pinned host staging, lgh::kPinDoubles doubles; its slots: lgh::kPin*
-   unsigned long long look_token; // counts the host looks that wait for a token in pinned memory (host_wait_token)
-   double *host_pinned_dev; // the same memory as the device addresses it: scalars a host look needs are written there by the kernel that
-                            // finishes them (no copy kernel between it and the stream synchronisation)
+   lgh::DevPtr<double> XE; // max(L2V, NE*ND*dim)
+   lgh::DevPtr<double> YE; // NE*ND*dim
+   lgh::DevPtr<double> cg_r, cg_z, cg_d0, cg_d1, cg_y; // max(N, L2V)
+   lgh::DevPtr<double> partials; // 4 reduction slots of part_stride block partials each
+   int part_stride = 0; // slot size: >= max #blocks of any reducing launch + kShards
+   lgh::DevPtr<unsigned int> tickets;// 4 reduction slots of lgh::kTicketSlot counters (sharded tickets)
+   lgh::DevPtr<lgh::CgScalars> cgs;
+   lgh::DevPtr<double> scal; // small device scalar pool (16 doubles)
+   unsigned long long look_token = 0; // counts the host looks that wait for a token in pinned memory (host_wait_token)
 
    // lockstep velocity CG (lgh_vcg.hip), allocated on first use
-   void *vcg_s;
-   double *vcg_vec, *vcg_partials;
-   unsigned int *vcg_tickets;
-   unsigned vcg_stride;
-   int vcg_last;
-   int vcg_grid;         // persistent grid size of the K1 kernel (one resident wave)
-   int b_h1_sym, b_l2_sym; // the 1-D H1 / L2 table is mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (to 1e-14: the round-off of its evaluation): kernels may hold half of it
-   int ncu;              // CUs of this context's device (0: not asked yet)
-   void *vcg_aux;        // tables of the node kernel K2 (lgh_vcg.hpp VcgAux; built and dropped by lgh_vcg_tables.hip), allocated on first use
+   lgh::DevPtr<lgh::VcgScalars> vcg_s;
+   lgh::DevPtr<double> vcg_vec, vcg_partials;
+   lgh::DevPtr<unsigned int> vcg_tickets;
+   unsigned vcg_stride = 0;
+   int vcg_last = 0;
+   int vcg_grid = 0;     // persistent grid size of the K1 kernel (one resident wave)
+   int b_h1_sym = 0, b_l2_sym = 0; // the 1-D H1 / L2 table is mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (to 1e-14: the round-off of its evaluation): kernels may hold half of it
+   int ncu = 0;          // CUs of this context's device (0: not asked yet)
+   std::unique_ptr<lgh::VcgAux> vcg_aux; // tables of the node kernel K2 (lgh_vcg.hpp VcgAux; built and dropped by lgh_vcg_tables.hip), allocated on first use
 
    lgh::Timers timers;
-   lgh::KTime *ktime;
-   int cg_last_iters[2][3]; // iteration count of the previous solve per (space, component)
-   lgh::Comm *comm;
-   int nranks, rank;
-   int multi;            // 1: run the multi-rank code path (nranks > 1, or LGH_FORCE_MULTI=1 for testing on one GPU)
-   unsigned long long *q_trace_dev; // debug (LGH_Q_TRACE): stage stamps of the quadrature update's workgroups, NE records
-   int q_trace_n, q_trace_calls;
-   void *order;          // lgh::MeshOrder (lgh_order.hip)
-   unsigned long mass_gen; // counts changes of the mass data / Jacobi diagonal (the velocity solve keeps copies in its own numbering)
-   double *me_fac;       // 1D: NE * L1D^2, Cholesky factors of the zone mass matrices Me(z) of the energy solve (lgh_1d.hip)
-   int setup_done;       // lgh_setup_rho0detj0 has run: rho0DetJ0w holds the masses of the points (lgh_diagnostics refuses before)
-   double *diag_dev;     // lgh_diagnostics (lgh_diag.hip): 32 doubles of folded values, then the 17 zone arrays; allocated on first use
-   void *prof_dev = nullptr; // lgh_profile (lgh_profile.hip): accumulator words, flags, maxima and the packed rows for prof_rows rows;
+   std::unique_ptr<lgh::KTime> ktime;
+   int cg_last_iters[2][3] = {{0, 0, 0}, {0, 0, 0}}; // iteration count of the previous solve per (space, component)
+   std::unique_ptr<lgh::Comm> comm;
+   int nranks = 1, rank = 0;
+   int multi = 0;        // 1: run the multi-rank code path (nranks > 1, or LGH_FORCE_MULTI=1 for testing on one GPU)
+   lgh::DevPtr<unsigned long long> q_trace_dev; // debug (LGH_Q_TRACE): stage stamps of the quadrature update's workgroups, NE records
+   int q_trace_n = 0, q_trace_calls = 0;
+   std::unique_ptr<lgh::MeshOrder> order; // (lgh_order.hip)
+   unsigned long mass_gen = 0; // counts changes of the mass data / Jacobi diagonal (the velocity solve keeps copies in its own numbering)
+   lgh::DevPtr<double> me_fac; // 1D: NE * L1D^2, Cholesky factors of the zone mass matrices Me(z) of the energy solve (lgh_1d.hip)
+   int setup_done = 0;   // lgh_setup_rho0detj0 has run: rho0DetJ0w holds the masses of the points (lgh_diagnostics refuses before)
+   lgh::DevPtr<double> diag_dev; // lgh_diagnostics (lgh_diag.hip): 32 doubles of folded values, then the 17 zone arrays; allocated on first use
+   lgh::DevPtr<char> prof_dev; // lgh_profile (lgh_profile.hip): accumulator words, flags, maxima and the packed rows for prof_rows rows;
    int prof_rows = 0;        // allocated at the first call, regrown only when nbins grows
-   void *map_dev = nullptr;  // lgh_map (lgh_map.hip): the same for map_rows rows of eight sum columns; regrown only when the cell count grows
+   lgh::DevPtr<char> map_dev;  // lgh_map (lgh_map.hip): the same for map_rows rows of eight sum columns; regrown only when the cell count grows
    int map_rows = 0;
-   unsigned long long *fp_dev; // lgh_vec_fingerprint (lgh_fingerprint.hip): the two words of the result and the workgroups' partial words, allocated on first use
+   lgh::DevPtr<unsigned long long> fp_dev; // lgh_vec_fingerprint (lgh_fingerprint.hip): the two words of the result and the workgroups' partial words, allocated on first use
 };
 
 namespace lgh
@@ -540,11 +587,10 @@ inline int grid_for(long n) { return (int)std::min<long>(std::max<long>((n + 255
 
 // ---- lgh_order.hip
 int mesh_order_build(lgh_ctx *c, const int *map_host);
-void mesh_order_free(lgh_ctx *c);
 // the internal order when it differs from the caller's, else nullptr
 inline const MeshOrder *mesh_order(const lgh_ctx *c)
 {
-   const MeshOrder *o = (const MeshOrder *)c->order;
+   const MeshOrder *o = c->order.get();
    return (o && !o->identity) ? o : nullptr;
 }
 int order_gather_nodes(lgh_ctx *c, const double *in, double *out, int ncomp);  // out[k N + m] = in[k N + ncaller[m]]
@@ -569,12 +615,12 @@ int vcg_solve(lgh_ctx *c, double *B, double *X, double rel_tol, int max_iter, in
               const double *force_E = nullptr);
 bool vcg_fused_init_ok(const lgh_ctx *c);
 // tables of the node kernel K2 (lgh_vcg_tables.hip)
-int partition_nodes_by_cost(lgh_ctx *c, int W, int **out, const std::vector<int> *valence = nullptr);
-int make_ellz(lgh_ctx *c, unsigned **out, const int *ell = nullptr, int deg = 0);
+int partition_nodes_by_cost(lgh_ctx *c, int W, DevPtr<int> &out, const std::vector<int> *valence = nullptr);
+int make_ellz(lgh_ctx *c, DevPtr<unsigned> &out, const int *ell = nullptr, int deg = 0);
 int vcg_test_merged_faces(lgh_ctx *c, unsigned char *mask, long *n_merged); // lgh_test_vcg_merged_faces
 int vcg_layout_stats(lgh_ctx *c, long out[4]); // lgh_vcg_layout_stats
-int make_essbits(lgh_ctx *c, uint8_t **out);
-void vcg_free(lgh_ctx *c);
+int make_essbits(lgh_ctx *c, DevPtr<uint8_t> &out);
+void vcg_free(lgh_ctx *c); // drops the tables of K2: the next solve builds them again (a communicator has changed)
 constexpr int kDtSlots = 256, kDtSlotStride = 16; // doubles; slot s at dt_est_dev[kDtSlotStride * (1 + s)]
 // dt_est_dev[kDtHint], one of the padding doubles behind the estimate: the hint word of the row-form update.  It only ever
 // holds +inf, the estimate itself (lgh_set_dt_est) or a value that was also deposited in a slot, so the folded estimate is
@@ -618,7 +664,6 @@ int comm_ranks_before(const lgh_ctx *c); // neighbours whose rank is lower than 
 bool vcg_lockstep_ready(const lgh_ctx *c); // the velocity solve of this context exchanges accumulator words and packs its halo itself
 int cg_l2_begin(lgh_ctx *c, const double *b, double *x, double rel_tol, int max_iter);
 int cg_l2_end(lgh_ctx *c, int *iters);
-void cg_l2_free(lgh_ctx *c);
 int cg_solve(lgh_ctx *c, int space, const double *b, double *x, double rel_tol, int max_iter,
              int *iters, bool x_is_zero);
 int stress_on_hand(lgh_ctx *c, const char *who); // LGH_OK: the stress of the current quadrature data is in memory (lgh_api.hip)
@@ -664,6 +709,7 @@ int allreduce_dev(lgh_ctx *c, double *dev, int count, int op, bool packed = fals
 
 // ---- lgh_1d.hip: the 1D path (the entry points send a context with dim == 1 there; the 2D/3D kernels never see one)
 bool kernel_id_supported_1d(int kid);
+int create_common(const lgh_config *cfg, lgh_ctx *c, std::vector<int> &t_off, std::vector<int> &t_idx); // (lgh_api.hip) what create_1d and the 2D/3D create share
 int create_1d(const lgh_config *cfg, lgh_ctx *c);
 int setup_1d(lgh_ctx *c, const double *x0, const double *rho0_l2, const double *rho0_q, double *volume);
 int mass_changed_1d(lgh_ctx *c); // Jacobi diagonal and zone mass factors from the current mass data
@@ -684,12 +730,12 @@ int sedov_density_error_1d(lgh_ctx *c, const double *x_h1, const double *rho_l2,
 // bracket one launch of kernel `id` with an event pair when sampling is on
 inline void kt_begin(lgh_ctx *c, int id)
 {
-   KTime *k = c->ktime;
+   KTime *k = c->ktime.get();
    if (k && k->which == id && k->n < k->max) { (void)hipEventRecord(k->ev[2 * k->n], c->stream); }
 }
 inline void kt_end(lgh_ctx *c, int id)
 {
-   KTime *k = c->ktime;
+   KTime *k = c->ktime.get();
    if (k && k->which == id && k->n < k->max) { (void)hipEventRecord(k->ev[2 * k->n + 1], c->stream); k->n++; }
 }
 

@@ -334,10 +334,7 @@ int lgh_diagnostics(lgh_ctx *c, const double *S, double out[LGH_DIAG_COUNT])
    LGH_CHECK_ARG(c && S && out);
    int rc = diag_ready(c, "lgh_diagnostics");
    if (rc) { return rc; }
-   if (!c->diag_dev)
-   {
-      LGH_HIP_CHECK(hipMalloc((void **)&c->diag_dev, ((size_t)kDiagZone * c->NE + 32) * sizeof(double)));
-   }
+   if (!c->diag_dev) { LGH_PASS(c->diag_dev.alloc((size_t)kDiagZone * c->NE + 32)); }
    double *g = c->diag_dev, *zone = g + 32;
    rc = diag_zones(c, S, zone);
    if (rc) { return rc; }

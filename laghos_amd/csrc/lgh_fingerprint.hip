@@ -168,7 +168,7 @@ int lgh_vec_fingerprint(lgh_ctx *c, const double *x, long n, unsigned long long 
    int head;
    fp_shape(c, x, n, &blocks, &head, &cap);
    // fp_dev: the two words of the result, then two per workgroup of the largest grid (the device, and with it cap, is the context's)
-   if (!c->fp_dev) { LGH_HIP_CHECK(hipMalloc((void **)&c->fp_dev, (2 + 2 * (size_t)cap) * sizeof(unsigned long long))); }
+   if (!c->fp_dev) { LGH_PASS(c->fp_dev.alloc(2 + 2 * (size_t)cap)); }
    {
       KtScope kt(c, LGH_KERNEL_FINGERPRINT);
       hipLaunchKernelGGL(fingerprint_k, dim3((unsigned)blocks), dim3(kFpThreads), 0, c->stream, (const unsigned long long *)x, n, head,

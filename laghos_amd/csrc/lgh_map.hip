@@ -198,12 +198,11 @@ extern "C" int lgh_map(lgh_ctx *c, const double *S, const lgh_map_spec *spec, do
    const int R = (int)ncells + 1;
    if (R > c->map_rows)
    {
-      if (c->map_dev) { LGH_HIP_CHECK(hipFree(c->map_dev)); c->map_dev = nullptr; c->map_rows = 0; }
+      c->map_rows = 0;
       const size_t bytes = prof_layout<kMapSums>(nullptr, R).bytes;
-      if (hipMalloc(&c->map_dev, bytes) != hipSuccess)
+      if (c->map_dev.alloc(bytes) != LGH_OK)
       {
          (void)hipGetLastError(); // (cleared: the context stays usable, a smaller grid may still fit)
-         c->map_dev = nullptr;
          set_error("lgh_map: cannot allocate %zu bytes of scratch memory for %ld cells", bytes, ncells);
          return LGH_ERR_HIP;
       }

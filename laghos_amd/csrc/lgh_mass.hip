@@ -890,10 +890,10 @@ int mass_data(lgh_ctx *c, const double **Dq, int *dqs, const double **Se)
 {
    if (c->mass_rank1 < 0)
    {
-      if (!c->massS)
+      if (!c->ones_ne)
       {
-         LGH_HIP_CHECK(hipMalloc((void **)&c->massS, sizeof(double) * (size_t)c->NE));
-         LGH_HIP_CHECK(hipMalloc((void **)&c->ones_ne, sizeof(double) * (size_t)c->NE));
+         LGH_PASS(c->massS.alloc((size_t)c->NE));
+         LGH_PASS(c->ones_ne.alloc((size_t)c->NE));
       }
       int *flag = c->dev_flags + 3, h = 1;
       LGH_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), c->stream));

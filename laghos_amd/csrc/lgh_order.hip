@@ -37,20 +37,6 @@
 namespace lgh
 {
 
-static void free_order(MeshOrder *o)
-{
-   if (!o) { return; }
-   (void)hipFree(o->zorder_d);
-   (void)hipFree(o->ncaller_d);
-   (void)hipFree(o->nnum_d);
-   delete o;
-}
-void mesh_order_free(lgh_ctx *c)
-{
-   free_order((MeshOrder *)c->order);
-   c->order = nullptr;
-}
-
 // host part: fills zorder / nnum / ncaller and the statistics; returns false when the map is not a set of structured
 // blocks (the permutations are then left empty = identity)
 static bool analyse(const int *map, const int NE, const int N, const int D, MeshOrder &o)
@@ -190,9 +176,8 @@ static bool analyse(const int *map, const int NE, const int N, const int D, Mesh
 
 int mesh_order_build(lgh_ctx *c, const int *map)
 {
-   mesh_order_free(c);
-   MeshOrder *o = new MeshOrder();
-   c->order = o;
+   c->order.reset(new MeshOrder());
+   MeshOrder *o = c->order.get();
    if (c->dim != 3 || !c->sw.order) { return LGH_OK; } // (LGH_ORDER=0, A/B: the caller's numbering everywhere, rounds 1-5)
    o->structured = analyse(map, c->NE, c->N, c->D1D, *o);
    if (!o->structured)
@@ -207,13 +192,9 @@ int mesh_order_build(lgh_ctx *c, const int *map)
    for (int n = 0; ident && n < c->N; n++) { ident = o->ncaller[n] == n; }
    o->identity = ident;
    if (ident) { return LGH_OK; }
-   LGH_HIP_CHECK(hipMalloc((void **)&o->zorder_d, (size_t)c->NE * sizeof(int)));
-   LGH_HIP_CHECK(hipMalloc((void **)&o->ncaller_d, (size_t)c->N * sizeof(int)));
-   LGH_HIP_CHECK(hipMalloc((void **)&o->nnum_d, (size_t)c->N * sizeof(int)));
-   LGH_HIP_CHECK(hipMemcpy(o->zorder_d, o->zorder.data(), (size_t)c->NE * sizeof(int), hipMemcpyHostToDevice));
-   LGH_HIP_CHECK(hipMemcpy(o->ncaller_d, o->ncaller.data(), (size_t)c->N * sizeof(int), hipMemcpyHostToDevice));
-   LGH_HIP_CHECK(hipMemcpy(o->nnum_d, o->nnum.data(), (size_t)c->N * sizeof(int), hipMemcpyHostToDevice));
-   return LGH_OK;
+   LGH_PASS(o->zorder_d.upload(o->zorder.data(), (size_t)c->NE));
+   LGH_PASS(o->ncaller_d.upload(o->ncaller.data(), (size_t)c->N));
+   return o->nnum_d.upload(o->nnum.data(), (size_t)c->N);
 }
 
 // ---- permutation kernels -------------------------------------------------------------------------------------------
@@ -252,28 +233,28 @@ __global__ void __launch_bounds__(256) order_blocks_k(const double *__restrict__
 
 int order_gather_nodes(lgh_ctx *c, const double *in, double *out, int ncomp)
 {
-   const MeshOrder *o = (const MeshOrder *)c->order;
+   const MeshOrder *o = c->order.get();
    hipLaunchKernelGGL(order_gather_k, dim3(ceil_div(c->N, 256)), dim3(256), 0, c->stream, in, o->ncaller_d, out, c->N, ncomp);
    LGH_HIP_CHECK(hipGetLastError());
    return LGH_OK;
 }
 int order_scatter_nodes(lgh_ctx *c, const double *in, double *out, int ncomp)
 {
-   const MeshOrder *o = (const MeshOrder *)c->order;
+   const MeshOrder *o = c->order.get();
    hipLaunchKernelGGL(order_scatter_k, dim3(ceil_div(c->N, 256)), dim3(256), 0, c->stream, in, o->ncaller_d, out, c->N, ncomp);
    LGH_HIP_CHECK(hipGetLastError());
    return LGH_OK;
 }
 int order_gather_bytes(lgh_ctx *c, const uint8_t *in, uint8_t *out)
 {
-   const MeshOrder *o = (const MeshOrder *)c->order;
+   const MeshOrder *o = c->order.get();
    hipLaunchKernelGGL(order_gather_u8_k, dim3(ceil_div(c->N, 256)), dim3(256), 0, c->stream, in, o->ncaller_d, out, c->N);
    LGH_HIP_CHECK(hipGetLastError());
    return LGH_OK;
 }
 int order_zone_blocks(lgh_ctx *c, const double *in, double *out, int per, bool to_caller)
 {
-   const MeshOrder *o = (const MeshOrder *)c->order;
+   const MeshOrder *o = c->order.get();
    const size_t n = (size_t)c->NE * per;
    hipLaunchKernelGGL(order_blocks_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, in, o->zorder_d, out, (size_t)c->NE, per, to_caller ? 1 : 0);
    LGH_HIP_CHECK(hipGetLastError());
@@ -307,7 +288,7 @@ extern "C" int lgh_mesh_order_host(int dim, int NE, int N, int D1D, const int *h
 extern "C" int lgh_mesh_order(lgh_ctx *c, long out[8])
 {
    LGH_CHECK_ARG(c && out);
-   const lgh::MeshOrder *o = (const lgh::MeshOrder *)c->order;
+   const lgh::MeshOrder *o = c->order.get();
    for (int i = 0; i < 8; i++) { out[i] = 0; }
    if (!o) { return LGH_OK; }
    out[0] = o->structured ? 1 : 0;

@@ -219,8 +219,8 @@ extern "C" int lgh_profile(lgh_ctx *c, const double *S, const lgh_profile_spec *
    const int R = spec->nbins + 2;
    if (R > c->prof_rows)
    {
-      if (c->prof_dev) { LGH_HIP_CHECK(hipFree(c->prof_dev)); c->prof_dev = nullptr; c->prof_rows = 0; }
-      LGH_HIP_CHECK(hipMalloc(&c->prof_dev, prof_layout<kProfSums>(nullptr, R).bytes));
+      c->prof_rows = 0;
+      LGH_PASS(c->prof_dev.alloc(prof_layout<kProfSums>(nullptr, R).bytes));
       c->prof_rows = R;
    }
    ProfArgs a;

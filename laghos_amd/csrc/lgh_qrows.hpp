@@ -512,8 +512,7 @@ template <int MINW6> static int launch_qrows_w(lgh_ctx *c, const QArgs &a)
    {
       if (c->q_trace_n != c->NE)
       {
-         if (c->q_trace_dev) { (void)hipFree(c->q_trace_dev); c->q_trace_dev = nullptr; }
-         LGH_HIP_CHECK(hipMalloc((void **)&c->q_trace_dev, (size_t)kQTraceRec * c->NE * 8));
+         LGH_PASS(c->q_trace_dev.alloc((size_t)kQTraceRec * c->NE));
          c->q_trace_n = c->NE;
       }
       LGH_HIP_CHECK(hipMemsetAsync(c->q_trace_dev, 0, (size_t)kQTraceRec * c->NE * 8, c->stream)); // (word 14 of a record is a counter)

@@ -431,8 +431,8 @@ int cg_solve(lgh_ctx *c, int space, const double *b, double *x, double rel_tol, 
 // only the initial look (rhs == 0) is folded into the first one.
 static int cg_l2_begin_impl(lgh_ctx *c, const double *b, double *x, double rel_tol, int max_iter, const bool enqueue)
 {
-   if (!c->l2run) { c->l2run = new ScalarCg(); }
-   ScalarCg *r = c->l2run;
+   if (!c->l2run) { c->l2run.reset(new ScalarCg()); }
+   ScalarCg *r = c->l2run.get();
    const int rc = scg_begin(c, r, LGH_SPACE_L2, b, x, rel_tol, max_iter, true);
    if (rc || !enqueue) { return rc; } // (lockstep: the velocity solve interleaves the iterations)
    const int last = *r->last;
@@ -441,22 +441,18 @@ static int cg_l2_begin_impl(lgh_ctx *c, const double *b, double *x, double rel_t
 int cg_l2_begin(lgh_ctx *c, const double *b, double *x, double rel_tol, int max_iter) { return cg_l2_begin_impl(c, b, x, rel_tol, max_iter, true); }
 int cg_l2_end(lgh_ctx *c, int *iters)
 {
-   ScalarCg *r = c->l2run;
+   ScalarCg *r = c->l2run.get();
    if (!r || !r->active) { return LGH_ERR_ARG; }
    return scg_finish(c, r, false, 0, iters);
 }
-void cg_l2_free(lgh_ctx *c)
-{
-   delete c->l2run;
-   c->l2run = nullptr;
-}
+void cg_l2_free(ScalarCg *r) { delete r; } // (the deleter of lgh_ctx::l2run: the type is known here only)
 
 // ---- lockstep with the velocity CG (lgh_common.hpp): set-up and initial residual here, one iteration per velocity
 // iteration from inside vcg_solve (apply behind K1, update behind K2), the rest - if any - by cg_l2_end as before
 bool l2_lockstep_possible(lgh_ctx *c) { return l2_fused_update(c); }
 int l2_lockstep_limit(lgh_ctx *c)
 {
-   const ScalarCg *r = c->l2run;
+   const ScalarCg *r = c->l2run.get();
    const int last = c->cg_last_iters[1][0];
    const int want = last > 0 ? last : 8;
    return (r && r->active) ? std::min(want, r->max_iter) : 0; // (never past the cap this solve was given)
@@ -464,7 +460,7 @@ int l2_lockstep_limit(lgh_ctx *c)
 int cg_l2_begin_lockstep(lgh_ctx *c, const double *b, double *x, double rel_tol, int max_iter) { return cg_l2_begin_impl(c, b, x, rel_tol, max_iter, false); }
 int l2_lockstep_apply(lgh_ctx *c, int it, const LockstepWords &prev, double *den_mirror)
 {
-   ScalarCg *r = c->l2run;
+   ScalarCg *r = c->l2run.get();
    if (!r || !r->active || !r->m.no_y || it != r->it + 1 || it > r->max_iter) { set_error("l2_lockstep_apply: no energy solve set up for iteration %d", it); return LGH_ERR_ARG; }
    ++r->it;
    r->m.iter = r->it;
@@ -475,7 +471,7 @@ int l2_lockstep_apply(lgh_ctx *c, int it, const LockstepWords &prev, double *den
 }
 int l2_lockstep_update(lgh_ctx *c, int it, const double *den_src, long long *word_out)
 {
-   ScalarCg *r = c->l2run;
+   ScalarCg *r = c->l2run.get();
    if (!r || !r->active || it != r->it) { set_error("l2_lockstep_update: iteration %d has no apply", it); return LGH_ERR_ARG; }
    r->v.iter = r->it;
    MassArgs m = r->m;
@@ -491,7 +487,7 @@ __global__ void l2_lockstep_fold_k(CgScalars *s, const int it, const LockstepWor
 }
 int l2_lockstep_fold(lgh_ctx *c, int it, const LockstepWords &last)
 {
-   ScalarCg *r = c->l2run;
+   ScalarCg *r = c->l2run.get();
    if (!r || !r->active || it != r->it) { set_error("l2_lockstep_fold: iteration %d is not the last one enqueued", it); return LGH_ERR_ARG; }
    hipLaunchKernelGGL(l2_lockstep_fold_k, dim3(1), dim3(1), 0, c->stream, c->cgs, it, last);
    LGH_HIP_CHECK(hipGetLastError());
@@ -499,7 +495,7 @@ int l2_lockstep_fold(lgh_ctx *c, int it, const LockstepWords &last)
 }
 int cg_l2_end_lockstep(lgh_ctx *c, int *iters)
 {
-   ScalarCg *r = c->l2run;
+   ScalarCg *r = c->l2run.get();
    if (!r || !r->active) { return LGH_ERR_ARG; }
    r->m.ls_on = 0; // (from here on the solve reduces its scalars itself: the sequence of cg_solve)
    r->m.ls_den_mirror = nullptr;

@@ -448,13 +448,6 @@ __global__ void __launch_bounds__(1024) sum_ordered_k(const int n, const double 
    if (t == 0) { out[0] = red[0]; }
 }
 
-struct DevBuf
-{
-   void *p = nullptr;
-   ~DevBuf() { if (p) { (void)hipFree(p); } }
-   int alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 8)) == hipSuccess ? LGH_OK : LGH_ERR_HIP; }
-};
-
 } // namespace lgh
 
 using namespace lgh;
@@ -518,18 +511,18 @@ int lgh_compute_density(lgh_ctx *c, const double *x_h1, double *rho_l2)
    LGH_CHECK_ARG(c && x_h1 && rho_l2);
    if (c->dim == 1) { return density_1d(c, x_h1, rho_l2); } // (lgh_1d.hip)
    const int grid = std::min(c->NE, 2048);
-   DevBuf scratch;
-   if (scratch.alloc((size_t)grid * c->NL * (c->NL + 1) * sizeof(double))) { set_error("lgh_compute_density: hipMalloc failed"); return LGH_ERR_HIP; }
+   DevPtr<double> scratch;
+   if (scratch.alloc((size_t)grid * c->NL * (c->NL + 1))) { set_error("lgh_compute_density: hipMalloc failed"); return LGH_ERR_HIP; }
    const size_t lds = ((size_t)c->dim * c->ND + c->NQ + c->NL) * sizeof(double);
    if (c->dim == 3)
    {
       hipLaunchKernelGGL(density_project_k<3>, dim3(grid), dim3(256), lds, c->stream, c->NE, c->N, c->D1D, c->Q1D, c->L1D,
-                         c->h1map, c->B, c->G, c->Bl, c->W, x_h1, c->rho0DetJ0w, (double *)scratch.p, rho_l2);
+                         c->h1map, c->B, c->G, c->Bl, c->W, x_h1, c->rho0DetJ0w, scratch.p, rho_l2);
    }
    else if (c->dim == 2)
    {
       hipLaunchKernelGGL(density_project_k<2>, dim3(grid), dim3(256), lds, c->stream, c->NE, c->N, c->D1D, c->Q1D, c->L1D,
-                         c->h1map, c->B, c->G, c->Bl, c->W, x_h1, c->rho0DetJ0w, (double *)scratch.p, rho_l2);
+                         c->h1map, c->B, c->G, c->Bl, c->W, x_h1, c->rho0DetJ0w, scratch.p, rho_l2);
    }
    LGH_HIP_CHECK(hipGetLastError());
    LGH_HIP_CHECK(hipStreamSynchronize(c->stream)); // the scratch is released on return
@@ -550,14 +543,14 @@ int lgh_sedov_density_error(lgh_ctx *c, const double *x_h1, const double *rho_l2
    tab.insert(tab.end(), B_h1, B_h1 + (size_t)n1d * D);
    tab.insert(tab.end(), G_h1, G_h1 + (size_t)n1d * D);
    tab.insert(tab.end(), B_l2, B_l2 + (size_t)n1d * L);
-   DevBuf dtab, part;
-   if (dtab.alloc(tab.size() * sizeof(double)) || part.alloc((size_t)c->NE * sizeof(double)))
+   DevPtr<double> dtab, part;
+   if (dtab.alloc(tab.size()) || part.alloc((size_t)c->NE))
    {
       set_error("lgh_sedov_density_error: hipMalloc failed");
       return LGH_ERR_HIP;
    }
    LGH_HIP_CHECK(hipMemcpy(dtab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-   const double *dw = (const double *)dtab.p, *dB = dw + n1d, *dG = dB + (size_t)n1d * D, *dBl = dG + (size_t)n1d * D;
+   const double *dw = dtab, *dB = dw + n1d, *dG = dB + (size_t)n1d * D, *dBl = dG + (size_t)n1d * D;
    const SedovPar s = par_from(par);
    const SedovShock k = sedov_shock(s, t);
    const size_t lds = ((size_t)c->dim * c->ND + c->NL + 256) * sizeof(double);
@@ -565,12 +558,12 @@ int lgh_sedov_density_error(lgh_ctx *c, const double *x_h1, const double *rho_l2
    if (c->dim == 3)
    {
       hipLaunchKernelGGL(sedov_density_error_k<3>, dim3(grid), dim3(256), lds, c->stream, c->NE, c->N, D, L, n1d, c->h1map,
-                         dB, dG, dBl, dw, x_h1, rho_l2, s, k, origin[0], origin[1], origin[2], (double *)part.p);
+                         dB, dG, dBl, dw, x_h1, rho_l2, s, k, origin[0], origin[1], origin[2], part.p);
    }
    else if (c->dim == 2)
    {
       hipLaunchKernelGGL(sedov_density_error_k<2>, dim3(grid), dim3(256), lds, c->stream, c->NE, c->N, D, L, n1d, c->h1map,
-                         dB, dG, dBl, dw, x_h1, rho_l2, s, k, origin[0], origin[1], 0.0, (double *)part.p);
+                         dB, dG, dBl, dw, x_h1, rho_l2, s, k, origin[0], origin[1], 0.0, part.p);
    }
    LGH_HIP_CHECK(hipGetLastError());
    hipLaunchKernelGGL(sum_ordered_k, dim3(1), dim3(1024), 0, c->stream, c->NE, (const double *)part.p, c->scal);

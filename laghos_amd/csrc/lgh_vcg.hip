@@ -783,7 +783,7 @@ vcg_gather_list_k(const VcgArgs a)
 
 // ---- host side -----------------------------------------------------------------------
 bool vcg_fused_init_ok(const lgh_ctx *c) { return c->sw.fused_init && vcg_available(c) && c->multi == 0 && c->t_deg <= 8; }
-bool vcg_lockstep_ready(const lgh_ctx *c) { return c->vcg_aux && ((const VcgAux *)c->vcg_aux)->ls_ready != 0; }
+bool vcg_lockstep_ready(const lgh_ctx *c) { return c->vcg_aux && c->vcg_aux->ls_ready != 0; }
 
 // ---- launchers of the node kernels the solve and the test hooks share
 // one launch of K2 as the one-rank solve issues it in iteration `it`: the bounded-grid kernel, x updated every second iteration
@@ -812,21 +812,14 @@ void vcg_launch_rz_finish(lgh_ctx *c, const VcgArgs &a, const int last, VcgScala
 // ---- vcg_prepare, step 1: the work buffers of the context
 static int vcg_work_buffers(lgh_ctx *c)
 {
-   if (c->vcg_s) { return LGH_OK; }
+   if (c->vcg_tickets) { return LGH_OK; } // (the last one built: a failure on the way leaves the rest to the next call)
    const size_t N = (size_t)c->N;
-   LGH_HIP_CHECK(hipMalloc((void **)&c->vcg_s, sizeof(VcgScalars)));
-   LGH_HIP_CHECK(hipMemset(c->vcg_s, 0, sizeof(VcgScalars)));
-   if (!c->vcg_vec)
-   {
-      LGH_HIP_CHECK(hipMalloc((void **)&c->vcg_vec, 3 * kVC * N * sizeof(double))); // r, d, yL (z = r/diag is never stored)
-      LGH_HIP_CHECK(hipMemset(c->vcg_vec, 0, 3 * kVC * N * sizeof(double)));
-   }
+   LGH_VCG_TRY(c->vcg_s.alloc(1, true));
+   LGH_VCG_TRY(c->vcg_vec.alloc(3 * kVC * N, true)); // r, d, yL (z = r/diag is never stored)
    // block partials of the largest reducing launch: K1 (<= NE batches), vcg_update_k (N/256 blocks), vcg_update_p_k (2 per CU)
    c->vcg_stride = (unsigned)(std::max<size_t>(std::max<size_t>((size_t)c->NE, (N + 255) / 256), 4096) + kShards);
-   LGH_HIP_CHECK(hipMalloc((void **)&c->vcg_partials, 2 * kVC * (size_t)c->vcg_stride * sizeof(double)));
-   LGH_HIP_CHECK(hipMemset(c->vcg_partials, 0, 2 * kVC * (size_t)c->vcg_stride * sizeof(double)));
-   LGH_HIP_CHECK(hipMalloc((void **)&c->vcg_tickets, 2 * kTicketSlot * sizeof(unsigned int)));
-   LGH_HIP_CHECK(hipMemset(c->vcg_tickets, 0, 2 * kTicketSlot * sizeof(unsigned int)));
+   LGH_VCG_TRY(c->vcg_partials.alloc(2 * kVC * (size_t)c->vcg_stride, true));
+   LGH_VCG_TRY(c->vcg_tickets.alloc(2 * kTicketSlot, true));
    return LGH_OK;
 }
 
@@ -983,7 +976,7 @@ static int vcg_fill_args(lgh_ctx *c, VcgAux *aux, const VcgK1 &k1, const VcgMode
    a.queue = a.limbs ? (unsigned *)(a.limbs + 2 * kLimbWords) : nullptr;
    a.den_limbs = m.den_limbs;
    a.k2_skip = c->sw.k2_skip;
-   a.s = (VcgScalars *)c->vcg_s;
+   a.s = c->vcg_s;
    a.stride = c->vcg_stride;
    a.multi = m.multi ? 1 : 0;
    // debug: LGH_VCG_TRACE=<file> dumps "block start loop_end end (xcc<<32|hw_id)" of the
@@ -1015,14 +1008,14 @@ int vcg_prepare(lgh_ctx *c, double *B, double *X, double rel_tol, VcgPlan &plan,
 {
    LGH_VCG_TRY(vcg_work_buffers(c));
    if (!c->vcg_aux) { LGH_VCG_TRY(vcg_build_aux(c)); } // (first solve, or the communicator has changed since)
-   VcgAux *aux = (VcgAux *)c->vcg_aux;
+   VcgAux *aux = c->vcg_aux.get();
    plan.aux = aux;
    plan.k1 = vcg_resolve_k1(c);
    LGH_VCG_TRY(vcg_mode(c, aux, plan.k1, in_solve, plan.mode));
    const VcgMode &m = plan.mode;
    if (!in_solve)
    {
-      hipLaunchKernelGGL(vcg_set_tol_k, dim3(1), dim3(1), 0, c->stream, (VcgScalars *)c->vcg_s, rel_tol * rel_tol, m.limbs ? aux->limbs.p : nullptr,
+      hipLaunchKernelGGL(vcg_set_tol_k, dim3(1), dim3(1), 0, c->stream, c->vcg_s.p, rel_tol * rel_tol, m.limbs ? aux->limbs.p : nullptr,
                          m.rzl ? aux->rzl.p : nullptr);
    }
    return vcg_fill_args(c, aux, plan.k1, m, B, X, rel_tol, in_solve, plan.a);

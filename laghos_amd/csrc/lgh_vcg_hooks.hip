@@ -111,11 +111,10 @@ vcg_test_exact_fold_k(const long long *__restrict__ set, int E, const double *__
 int vcg_test_exact_sum(lgh_ctx *c, int mode, long n, int G, int E, const double *scale, const double *v, const long long *w_in,
                        long long *w_out, double *d_out, int *i_out)
 {
-   DevPtr<void> dv, dw, dd, di, ds;
-   auto up = [&](DevPtr<void> &b, const void *src, size_t bytes) -> hipError_t {
-      hipError_t e = hipMalloc(&b.p, bytes);
-      if (e == hipSuccess) { e = src ? hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) : hipMemsetAsync(b.p, 0, bytes, c->stream); }
-      return e;
+   DevPtr<char> dv, dw, dd, di, ds;
+   auto up = [&](DevPtr<char> &b, const void *src, size_t bytes) -> hipError_t {
+      if (b.alloc(bytes) != LGH_OK) { return hipErrorOutOfMemory; }
+      return src ? hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) : hipMemsetAsync(b.p, 0, bytes, c->stream);
    };
    if (scale) { LGH_HIP_CHECK(up(ds, scale, sizeof(double))); }
    const double *dscale = (const double *)ds.p;

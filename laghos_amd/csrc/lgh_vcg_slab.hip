@@ -163,13 +163,12 @@ static bool slab_swaps_ok(lgh_ctx *c)
 }
 static bool slab_swaps_probe(lgh_ctx *c)
 {
-   double *dev = nullptr;
-   if (hipMalloc((void **)&dev, 2 * 36 * 64 * sizeof(double)) != hipSuccess) { return false; }
+   DevPtr<double> dev;
+   if (dev.alloc(2 * 36 * 64) != LGH_OK) { return false; }
    hipLaunchKernelGGL(slab_swap_probe_k, dim3(1), dim3(64), 0, c->stream, dev);
    std::vector<double> h(2 * 36 * 64);
    const bool ok = hipMemcpyAsync(h.data(), dev, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
                    hipStreamSynchronize(c->stream) == hipSuccess;
-   (void)hipFree(dev);
    if (!ok) { return false; }
    bool good = true;
    for (int lane = 0; lane < 64 && good; lane++)

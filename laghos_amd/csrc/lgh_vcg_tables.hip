@@ -62,7 +62,7 @@ vcg_ellz_k(const int *__restrict__ ell, unsigned *__restrict__ ellz, const size_
 // (measured: t = 4.2..5.3 ns + 1.7..1.8 ns * valence per node and workgroup, the traces of the persistent-solve experiment, profiles/r2_pcg_trace_*.txt); with equal
 // node counts the workgroups whose range covers element-boundary planes take 40 % longer and every barrier
 // waits for them.  Ranges of equal cost instead, boundaries rounded to 16 nodes (128 B).
-int partition_nodes_by_cost(lgh_ctx *c, const int W, int **out, const std::vector<int> *valence)
+int partition_nodes_by_cost(lgh_ctx *c, const int W, DevPtr<int> &out, const std::vector<int> *valence)
 {
    const int N = c->N;
    std::vector<int> off((size_t)N + 1);
@@ -87,17 +87,15 @@ int partition_nodes_by_cost(lgh_ctx *c, const int W, int **out, const std::vecto
       ns[w] = std::min(nb, N);
    }
    ns[std::max(W, 1)] = N;
-   LGH_HIP_CHECK(hipMalloc((void **)out, ns.size() * sizeof(int)));
-   LGH_HIP_CHECK(hipMemcpy(*out, ns.data(), ns.size() * sizeof(int), hipMemcpyHostToDevice));
-   return LGH_OK;
+   return out.upload(ns.data(), ns.size());
 }
 // ELL transpose of the restriction as byte offsets into a Y_E plane of NE*ND + pad doubles whose slot NE*ND is
 // zero: absent contributions point there, so the gather needs no predicate
-int make_ellz(lgh_ctx *c, unsigned **out, const int *ell, const int deg)
+int make_ellz(lgh_ctx *c, DevPtr<unsigned> &out, const int *ell, const int deg)
 {
    const size_t ell_n = (size_t)8 * c->N;
-   LGH_HIP_CHECK(hipMalloc((void **)out, ell_n * sizeof(unsigned)));
-   hipLaunchKernelGGL(vcg_ellz_k, dim3((unsigned)((ell_n + 255) / 256)), dim3(256), 0, nullptr, ell ? ell : c->t_ell, *out,
+   LGH_PASS(out.alloc(ell_n));
+   hipLaunchKernelGGL(vcg_ellz_k, dim3((unsigned)((ell_n + 255) / 256)), dim3(256), 0, nullptr, ell ? ell : c->t_ell.p, out.p,
                       (size_t)(ell ? deg : c->t_deg) * c->N, ell_n, c->NE * c->ND);
    LGH_HIP_CHECK(hipGetLastError());
    return LGH_OK;
@@ -155,15 +153,15 @@ int slab_merge_layout(lgh_ctx *c, const VcgAux *x, SlabLayout &L)
    return LGH_OK;
 }
 // bit k of entry n: node n is essential for component k
-int make_essbits(lgh_ctx *c, uint8_t **out)
+int make_essbits(lgh_ctx *c, DevPtr<uint8_t> &out)
 {
-   LGH_HIP_CHECK(hipMalloc((void **)out, (size_t)c->N));
+   LGH_PASS(out.alloc((size_t)c->N));
    const uint8_t *hmask = nullptr;
    const int *sh_node = nullptr;
    int n_shared = 0;
    if (c->multi) { comm_shared_nodes(c, &hmask, &sh_node, &n_shared); }
    hipLaunchKernelGGL(vcg_essbits_k, dim3((unsigned)((c->N + 255) / 256)), dim3(256), 0, nullptr, c->essmask[0], c->essmask[1],
-                      c->essmask[2], hmask, c->multi ? c->owner : nullptr, *out, c->N);
+                      c->essmask[2], hmask, c->multi ? c->owner.p : nullptr, out.p, c->N);
    LGH_HIP_CHECK(hipGetLastError());
    return LGH_OK;
 }
@@ -196,8 +194,8 @@ static int vcg_build_merged_tables(lgh_ctx *c, VcgAux *x)
    x->degm = degm;
    LGH_VCG_TRY(x->settab.upload(L.settab.data(), L.settab.size()));
    LGH_VCG_TRY(x->ellm.upload(ellm.data(), ellm.size()));
-   LGH_VCG_TRY(make_ellz(c, x->ellzm.out(), x->ellm, 8));
-   return partition_nodes_by_cost(c, x->grid2, x->nstartm.out(), &val);
+   LGH_VCG_TRY(make_ellz(c, x->ellzm, x->ellm, 8));
+   return partition_nodes_by_cost(c, x->grid2, x->nstartm, &val);
 }
 
 // The order the lockstep solve runs in: the library's own (lgh_order.hip) unless it is the caller's anyway.  Several ranks:
@@ -314,8 +312,8 @@ int vcg_build_aux(lgh_ctx *c)
       if (c->sw.k2_grid > 0) { x->grid2 = c->sw.k2_grid * ncu; }
       else { x->grid2 = (int)std::max<long>(4L * ncu, (((long)c->N + 1023) / 1024 + 7) & ~7L); }
       x->grid2 = std::min<long>(x->grid2, (long)c->vcg_stride - (long)kShards); // (one partial per workgroup in a reduction slot)
-      LGH_VCG_TRY(make_ellz(c, x->ellz.out(), x->o_ell, x->o_ell ? c->t_deg : 0));
-      LGH_VCG_TRY(make_essbits(c, x->essbits.out()));
+      LGH_VCG_TRY(make_ellz(c, x->ellz, x->o_ell, x->o_ell ? c->t_deg : 0));
+      LGH_VCG_TRY(make_essbits(c, x->essbits));
       if (x->ord)
       {
          // (the flag bytes were built from the caller's masks: into the internal numbering)
@@ -326,7 +324,7 @@ int vcg_build_aux(lgh_ctx *c)
          LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
          x->essbits = std::move(tmp);
       }
-      LGH_VCG_TRY(partition_nodes_by_cost(c, x->grid2, x->nstart.out(), x->ord ? &x->o_valence : nullptr));
+      LGH_VCG_TRY(partition_nodes_by_cost(c, x->grid2, x->nstart, x->ord ? &x->o_valence : nullptr));
       if ((size_t)kVC * (c->NE + 1) * c->ND * 8 < 0xffffffffull)
       {
          // (the FORCE E-vector is in the caller's zone order: o_ellc)
@@ -343,7 +341,7 @@ int vcg_build_aux(lgh_ctx *c)
       LGH_VCG_TRY(x->mapb.alloc(nm));
       hipLaunchKernelGGL(vcg_mapb_k, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, nullptr, v_map, x->mapb, nm);
       LGH_HIP_CHECK(hipGetLastError());
-      int *flag = (int *)c->scal, h = 1;
+      int *flag = (int *)c->scal.p, h = 1;
       LGH_HIP_CHECK(hipMemset(flag, 0, sizeof(int)));
       hipLaunchKernelGGL(vcg_map_xrows_k, dim3((unsigned)((nm / c->D1D + 255) / 256)), dim3(256), 0, nullptr, v_map, nm / c->D1D, c->D1D, flag);
       LGH_HIP_CHECK(hipMemcpy(&h, flag, sizeof(int), hipMemcpyDeviceToHost));
@@ -354,14 +352,13 @@ int vcg_build_aux(lgh_ctx *c)
       if (x->ellz && c->sw.slab_merge) { LGH_VCG_TRY(vcg_build_merged_tables(c, x)); }
    }
    LGH_HIP_CHECK(hipStreamSynchronize(nullptr)); // the fills run asynchronously on the null stream
-   c->vcg_aux = owner.release();
+   c->vcg_aux = std::move(owner);
    return LGH_OK;
 }
 
 void vcg_free(lgh_ctx *c)
 {
-   delete (VcgAux *)c->vcg_aux;
-   c->vcg_aux = nullptr;
+   c->vcg_aux.reset();
 }
 
 } // namespace lgh
