@@ -363,6 +363,39 @@ int lgh_sample_derived(lgh_ctx *ctx, const double *S, int R1, const double *B_h1
                        const double *G_h1_lat /* host, R1*D1D */, const double *B_l2_lat /* host, R1*L1D */,
                        double *detj_out, double *gradv_out, double *div_out, double *vort_out, double *cs_out);
 
+/* ---- the same fields on zone faces (outer surface, logical cut planes): a face is (zone e, local face f = 2a + s), the side
+ * xi_a = s of the caller's zone e, a < dim, s = 0 or 1.  Its lattice is the volume lattice above with one abscissa on axis a:
+ * NPF = R1^(dim-1) points over the other axes in ascending order, p = r_b + R1 r_c (3D, b < c), p = r_b (2D).  For the list
+ * faces[2k] = e, faces[2k + 1] = f of nfaces faces (a HOST array, read during the call like the tables; a zone may appear any
+ * number of times, in any order; the device copy lives in a buffer of the context), NPt = nfaces * NPF and pt = k * NPF + p.
+ * Outputs are device arrays, structure of arrays over NPt with NP -> NPt in the layouts above; each may be NULL and is skipped:
+ *   x_out, v_out, e_out, rho_out, p_out              as lgh_sample_fields
+ *   detj_out, gradv_out, div_out, vort_out, cs_out   as lgh_sample_derived
+ *   an_out[c * NPt + pt], c < dim                    the outward area vector per unit reference area (Nanson's formula):
+ *                                                    N_i = sgn adj(J)_{a i}, J adj(J) = det J I, sgn = +1 for s = 1, -1 for s = 0;
+ *                                                    2D: a length-weighted normal.  No branch looks at the sign of det J.
+ * For every finite state each output but an_out has THE BITS the volume functions give at the lattice point with r_a = 0
+ * (s = 0) or R1 - 1 (s = 1) and the other indices equal: the same stages in the same order, one table row on axis a.
+ * LGH_ERR_ARG: dim == 1, R1 out of range, nfaces < 0, a NULL table an output needs (B_h1_lat: x, v and the derivatives; G_h1_lat:
+ * detj, gradv, div, vort, an; B_l2_lat: e, rho, p, cs), rho_out / p_out without rho_l2, a zone outside 0..NE-1, a local face
+ * outside 0..2 dim - 1.  LGH_ERR_UNSUPPORTED with the bytes in the message: tables of more than 81 entries, a face that needs
+ * more than 64 KB of LDS.  The message names the offending value; nothing is launched.  nfaces == 0, or no output: LGH_OK, no launch.
+ * Asynchronous on the context's stream; reads S, rho_l2, h1_map, gamma; writes its outputs only.  2D and 3D. */
+int lgh_sample_faces(lgh_ctx *ctx, const double *S, const double *rho_l2 /* or NULL */, int R1,
+                     const double *B_h1_lat /* host, R1*D1D, or NULL */, const double *G_h1_lat /* host, R1*D1D, or NULL */,
+                     const double *B_l2_lat /* host, R1*L1D, or NULL */, int nfaces, const int *faces /* host, 2*nfaces */,
+                     double *x_out, double *v_out, double *e_out, double *rho_out, double *p_out, double *detj_out,
+                     double *gradv_out, double *div_out, double *vort_out, double *cs_out, double *an_out);
+/* Faces per workgroup of that kernel for lists long enough: as many as fit 256 lattice points and 48 KB of LDS, one where they
+ * do not - min(256 / NPF, (48 KB - tables) / face), with (R1 + 2) (2 D1D + L1D) doubles of tables and per face
+ * 1 + max(D^dim + 2 R1 D^(dim-1) [+ 3 R1^2 D in 3D], L^dim + R1 L^(dim-1) [+ R1^2 L in 3D]) doubles.  Lists of FPB - 1, FPB, FPB + 1
+ * faces are the edges of the launch.  LGH_ERR_ARG where lgh_sample_faces refuses dim or R1. */
+int lgh_sample_faces_fpb(lgh_ctx *ctx, int R1, int *fpb);
+/* The boundary of a mesh given by its element -> node map alone (no GPU, no context; for callers that hand over a mesh
+ * library's numbering): the faces (e, f) whose D1D^(dim-1) nodes are, as a set, the nodes of no other face of any zone, in
+ * ascending (e, f), into faces_out[2k], faces_out[2k + 1] (room for 2 * 2 dim NE ints); *nfaces their number.  dim 1..3. */
+int lgh_mesh_boundary_faces_host(int dim, int NE, int N, int D1D, const int *h1_map, int *faces_out, int *nfaces);
+
 /* ---- conservation and mesh-health diagnostics (the driver's `-hist` time history; the reference prints one number,
  * "Energy diff", after the last step).  At quadrature point q of zone z, with the context's own tables and rule (those
  * lgh_qupdate uses): J_q = grad x and detJ_q from the x block of S, v_q from the v block, e_q from the e block through
@@ -472,6 +505,7 @@ int lgh_enable_timers(lgh_ctx *ctx, int on);
 #define LGH_KERNEL_PROFILE 11     /* lgh_profile: both passes over the zones and the kernels between and behind them */
 #define LGH_KERNEL_DERIVED 12     /* lgh_sample_derived */
 #define LGH_KERNEL_MAP 13         /* lgh_map: as LGH_KERNEL_PROFILE */
+#define LGH_KERNEL_FACES 14       /* lgh_sample_faces */
 int lgh_ktime_begin(lgh_ctx *ctx, int which, int max_samples);
 int lgh_ktime_end(lgh_ctx *ctx, int *launches, double *mean_seconds);
 /* Whether lgh_create found the 1-D H1 / L2 tables mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (any nodal or

@@ -97,6 +97,9 @@ SYMBOLS = {
     "lgh_sedov_density_error": (_I, [_P, _P, _P, c_dbl_p, _D, c_dbl_p, _I, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
     "lgh_sample_fields": (_I, [_P, _P, _P, _I, c_dbl_p, c_dbl_p, _P, _P, _P, _P, _P]),
     "lgh_sample_derived": (_I, [_P, _P, _I, c_dbl_p, c_dbl_p, c_dbl_p, _P, _P, _P, _P, _P]),
+    "lgh_sample_faces": (_I, [_P, _P, _P, _I, c_dbl_p, c_dbl_p, c_dbl_p, _I, c_int_p] + [_P] * 11),
+    "lgh_sample_faces_fpb": (_I, [_P, _I, ctypes.POINTER(_I)]),
+    "lgh_mesh_boundary_faces_host": (_I, [_I, _I, _I, _I, c_int_p, c_int_p, ctypes.POINTER(_I)]),
     "lgh_diagnostics_zones": (_I, [_P, _P, _P]),
     "lgh_diagnostics": (_I, [_P, _P, c_dbl_p]),
     "lgh_profile": (_I, [_P, _P, ctypes.POINTER(LghProfileSpec), c_dbl_p, ctypes.POINTER(ctypes.c_long)]),

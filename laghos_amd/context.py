@@ -126,6 +126,18 @@ def diagnostics_dict(out):
     return {k: (int(out[i]) if k in _DIAG_INTS else float(out[i])) for i, k in enumerate(DIAG_NAMES)}
 
 
+def boundary_faces_host(dim, NE, N, D1D, h1_map):
+    """lgh_mesh_boundary_faces_host: the faces (zone, local face 2 axis + side) of a mesh given by its element -> node map whose
+    D1D^(dim-1) nodes are the node set of no other zone's face, as (nfaces, 2) ints in ascending order.  Needs no GPU."""
+    hm = _np_i32(np.asarray(h1_map).reshape(-1))
+    assert hm.size == NE * D1D ** dim
+    out = np.empty((2 * dim * NE, 2), np.int32)
+    n = ctypes.c_int(-1)
+    ip = ctypes.POINTER(ctypes.c_int)
+    check(_lib.load().lgh_mesh_boundary_faces_host(dim, NE, N, D1D, hm.ctypes.data_as(ip), out.ctypes.data_as(ip), ctypes.byref(n)))
+    return out[:n.value].copy()
+
+
 class Context:
     """lgh_ctx owner.  Arguments follow struct lgh_config: tables are (Q,D)
     arrays B[q,d]; h1_map is (NE, ND); ess is a list of dim int arrays."""
@@ -511,6 +523,34 @@ class Context:
         opt = lambda t: _ptr(t) if t is not None else None
         check(self.lib.lgh_sample_derived(self.h, _ptr(S), R1, _dbl(Bh), _dbl(Gh), _dbl(Bl), opt(detj), opt(grad_v), opt(div_v), opt(vorticity),
                                           opt(sound_speed)))
+
+    def sample_faces(self, S, rho_l2, B_h1_lat, G_h1_lat, B_l2_lat, faces, x=None, v=None, e=None, rho=None, p=None, detj=None, grad_v=None,
+                     div_v=None, vorticity=None, sound_speed=None, area_normal=None):
+        """lgh_sample_faces: the outputs of sample_fields and sample_derived on the lattices of the zone faces `faces` - (nfaces, 2)
+        ints (zone, local face 2 axis + side), a host array - and the outward area vectors; tables as there ([r, d]; None where no
+        output needs one); device tensors over NPt = nfaces * R1^(dim-1) points in the layouts of the two volume calls, area_normal
+        dim * NPt; each may be None (skipped).  Asynchronous."""
+        tab = lambda T: None if T is None else _np_f64(np.asarray(T).T.reshape(-1))   # -> [r + R1*d]
+        Bh, Gh, Bl = tab(B_h1_lat), tab(G_h1_lat), tab(B_l2_lat)
+        R1 = int(np.asarray(next(T for T in (B_h1_lat, G_h1_lat, B_l2_lat) if T is not None)).shape[0])
+        f = np.ascontiguousarray(np.asarray(faces, dtype=np.int32).reshape(-1))
+        assert f.size % 2 == 0
+        opt = lambda t: _ptr(t) if t is not None else None
+        dbl = lambda a: _dbl(a) if a is not None else None
+        fp = f.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if f.size else None
+        check(self.lib.lgh_sample_faces(self.h, _ptr(S), opt(rho_l2), R1, dbl(Bh), dbl(Gh), dbl(Bl), f.size // 2, fp, opt(x), opt(v), opt(e),
+                                        opt(rho), opt(p), opt(detj), opt(grad_v), opt(div_v), opt(vorticity), opt(sound_speed), opt(area_normal)))
+
+    def faces_per_block(self, R1):
+        """lgh_sample_faces_fpb: faces per workgroup of sample_faces on R1 lattice points per direction, for lists long enough."""
+        n = ctypes.c_int(-1)
+        check(self.lib.lgh_sample_faces_fpb(self.h, int(R1), ctypes.byref(n)))
+        return n.value
+
+    def boundary_faces(self):
+        """The boundary faces of this context's mesh, (nfaces, 2) ints (zone, local face) in ascending order, found from the
+        element -> node map alone (lgh_mesh_boundary_faces_host; no GPU work)."""
+        return boundary_faces_host(self.dim, self.NE, self.N, self.D1D, self._keep["h1"])
 
     def diagnostics_zones(self, S, out):
         """lgh_diagnostics_zones: the 17 zone diagnostics of S into the device tensor out (17 * NE), out[k * NE + z] with z

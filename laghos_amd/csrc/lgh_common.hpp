@@ -338,6 +338,8 @@ struct lgh_ctx : lgh::CtxHandles
    int prof_rows = 0;        // allocated at the first call, regrown only when nbins grows
    lgh::DevPtr<char> map_dev;  // lgh_map (lgh_map.hip): the same for map_rows rows of eight sum columns; regrown only when the cell count grows
    int map_rows = 0;
+   lgh::DevPtr<int> faces_dev; // lgh_sample_faces (lgh_faces.hip): the device copy of the caller's face list, 2 * faces_cap ints; regrown only when a longer list comes
+   int faces_cap = 0;
    lgh::DevPtr<unsigned long long> fp_dev; // lgh_vec_fingerprint (lgh_fingerprint.hip): the two words of the result and the workgroups' partial words, allocated on first use
 };
 

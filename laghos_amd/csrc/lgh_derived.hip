@@ -95,35 +95,8 @@ __device__ __forceinline__ void derived_component(const DerivedArgs &a, const do
    __syncthreads(); // the next pass gathers into the same LDS
 }
 
-// det J, adj(J) (J adj(J) = det J I), entry (i, j) at [i][j]
-template <int DIM>
-__device__ __forceinline__ double derived_adj(const double (&J)[DIM][DIM], double (&A)[DIM][DIM])
-{
-   if constexpr (DIM == 1)
-   {
-      A[0][0] = 1.0;
-      return J[0][0];
-   }
-   else if constexpr (DIM == 2)
-   {
-      A[0][0] = J[1][1]; A[0][1] = -J[0][1];
-      A[1][0] = -J[1][0]; A[1][1] = J[0][0];
-      return J[0][0] * J[1][1] - J[0][1] * J[1][0];
-   }
-   else
-   {
-      A[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-      A[0][1] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
-      A[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
-      A[1][0] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-      A[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
-      A[1][2] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
-      A[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-      A[2][1] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
-      A[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-      return J[0][0] * A[0][0] + J[0][1] * A[1][0] + J[0][2] * A[2][0];
-   }
-}
+// (det J and adj(J), the sound speed and L with what follows from it: derived_adj, derived_cs, derived_grad of lgh_sample.hpp,
+// shared with the face kernel)
 
 template <int DIM>
 __global__ void __launch_bounds__(kSampleThreads) sample_derived_k(const DerivedArgs a)
@@ -226,52 +199,14 @@ __global__ void __launch_bounds__(kSampleThreads) sample_derived_k(const Derived
       if (a.cs)
       {
          const double gz = a.gamma[e0 + i / NPZ];
-         a.cs[pt] = sqrt((gz * (gz - 1.0)) * fmax(ev[k], 0.0));
+         a.cs[pt] = derived_cs(gz, ev[k]);
       }
       if (!a.need_x) { continue; }
       double A[DIM][DIM];
       const double det = derived_adj<DIM>(J[k], A);
       if (a.detj) { a.detj[pt] = det; }
       if (!a.need_v) { continue; }
-      double Lm[DIM][DIM];
-#pragma unroll
-      for (int r = 0; r < DIM; r++)
-      {
-#pragma unroll
-         for (int c = 0; c < DIM; c++)
-         {
-            double s = V[k][r][0] * A[0][c];
-#pragma unroll
-            for (int m = 1; m < DIM; m++) { s += V[k][r][m] * A[m][c]; }
-            Lm[r][c] = s / det;
-         }
-      }
-      if (a.gradv)
-      {
-#pragma unroll
-         for (int r = 0; r < DIM; r++)
-         {
-#pragma unroll
-            for (int c = 0; c < DIM; c++) { a.gradv[(size_t)(r * DIM + c) * NP + pt] = Lm[r][c]; }
-         }
-      }
-      if (a.div)
-      {
-         double s = Lm[0][0];
-#pragma unroll
-         for (int m = 1; m < DIM; m++) { s += Lm[m][m]; }
-         a.div[pt] = s;
-      }
-      if (a.vort)
-      {
-         if constexpr (DIM == 2) { a.vort[pt] = Lm[1][0] - Lm[0][1]; }
-         if constexpr (DIM == 3)
-         {
-            a.vort[pt] = Lm[2][1] - Lm[1][2];
-            a.vort[NP + pt] = Lm[0][2] - Lm[2][0];
-            a.vort[2 * NP + pt] = Lm[1][0] - Lm[0][1];
-         }
-      }
+      derived_grad<DIM>(V[k], A, det, pt, NP, a.gradv, a.div, a.vort);
    }
 }
 

@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(kSampleThreads) sample_fields_k(const SampleAr
          {
             const double rv = sample_last(L, R1, preH, p, Tl, in + (size_t)(z * NF + nh + 1) * sin);
             if (a.rho_out) { a.rho_out[p0 + zp] = rv; }
-            if (a.p_out) { a.p_out[p0 + zp] = (a.gamma[e0 + z] - 1.0) * rv * fmax(ev, 0.0); }
+            if (a.p_out) { a.p_out[p0 + zp] = sample_pressure(a.gamma[e0 + z], rv, ev); }
          }
       }
    }

@@ -1,5 +1,7 @@
-// lgh_sample.hpp — what the lattice kernels share (lgh_sample.hip: the fields; lgh_derived.hip: their derivatives): the
-// sizes, and the sum-factorisation stages.  Every sum runs over its dofs in ascending order in one thread.
+// lgh_sample.hpp — what the lattice kernels share (lgh_sample.hip: the fields; lgh_derived.hip: their derivatives;
+// lgh_faces.hip: both on zone faces): the sizes, the sum-factorisation stages and the point expressions.  Every sum runs
+// over its dofs in ascending order in one thread; one text for each expression is what makes the face values the bits of
+// the volume values.
 #pragma once
 #include "lgh_common.hpp"
 
@@ -8,6 +10,14 @@ namespace lgh
 
 constexpr int kSampleMaxTab = 81; // R1 * D1D of the largest lattice table (R1 <= 9, D1D <= 9)
 constexpr int kSampleThreads = 256;
+
+// The sum every stage is made of: sum_d T[R1*d] u[d*pre], d ascending from 0 in one thread (T: the table at the lattice point's row)
+__device__ __forceinline__ double sample_dot(const int n, const int R1, const int pre, const double *__restrict__ T, const double *__restrict__ u)
+{
+   double s = 0.0;
+   for (int d = 0; d < n; d++) { s += T[R1 * d] * u[d * pre]; }
+   return s;
+}
 
 // One contraction stage along axis a of every field of a group (n dofs per direction, table T[r + R1*d]):
 // out[(hi*R1 + r)*pre + lo] = sum_d T[r + R1*d] in[(hi*n + d)*pre + lo], pre = R1^a points done, post = n^(DIM-1-a) to do.
@@ -21,9 +31,7 @@ __device__ __forceinline__ void sample_stage(const int nz, const int nf, const i
       const int o = i % cnt, zf = i / cnt, f = zf % nf, z = zf / nf;
       const int lo = o % pre, r = (o / pre) % R1, hi = o / (pre * R1);
       const double *u = in + (size_t)(z * NF + f0 + f) * sin + (size_t)hi * n * pre + lo;
-      double s = 0.0;
-      for (int d = 0; d < n; d++) { s += T[r + R1 * d] * u[d * pre]; }
-      out[(size_t)(z * NF + f0 + f) * sout + o] = s;
+      out[(size_t)(z * NF + f0 + f) * sout + o] = sample_dot(n, R1, pre, T + r, u);
    }
 }
 
@@ -32,9 +40,89 @@ __device__ __forceinline__ double sample_last(const int n, const int R1, const i
                                               const double *__restrict__ u)
 {
    const int lo = p % pre, r = p / pre;
-   double s = 0.0;
-   for (int d = 0; d < n; d++) { s += T[r + R1 * d] * u[d * pre + lo]; }
-   return s;
+   return sample_dot(n, R1, pre, T + r, u + lo);
+}
+
+// ---- the point expressions the volume kernels and the face kernel (lgh_faces.hip) share: one text, the same bits -----
+// pressure of the equation of state at a point of zone gamma gz
+__device__ __forceinline__ double sample_pressure(const double gz, const double rv, const double ev) { return (gz - 1.0) * rv * fmax(ev, 0.0); }
+// sound speed there
+__device__ __forceinline__ double derived_cs(const double gz, const double ev) { return sqrt((gz * (gz - 1.0)) * fmax(ev, 0.0)); }
+
+// det J, adj(J) (J adj(J) = det J I), entry (i, j) at [i][j]
+template <int DIM>
+__device__ __forceinline__ double derived_adj(const double (&J)[DIM][DIM], double (&A)[DIM][DIM])
+{
+   if constexpr (DIM == 1)
+   {
+      A[0][0] = 1.0;
+      return J[0][0];
+   }
+   else if constexpr (DIM == 2)
+   {
+      A[0][0] = J[1][1]; A[0][1] = -J[0][1];
+      A[1][0] = -J[1][0]; A[1][1] = J[0][0];
+      return J[0][0] * J[1][1] - J[0][1] * J[1][0];
+   }
+   else
+   {
+      A[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+      A[0][1] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
+      A[0][2] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
+      A[1][0] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
+      A[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
+      A[1][2] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
+      A[2][0] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+      A[2][1] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
+      A[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+      return J[0][0] * A[0][0] + J[0][1] * A[1][0] + J[0][2] * A[2][0];
+   }
+}
+
+// L = (dv/dxi) adj(J) / det J at point pt of NP and what follows from it, stored where an output is asked for
+template <int DIM>
+__device__ __forceinline__ void derived_grad(const double (&V)[DIM][DIM], const double (&A)[DIM][DIM], const double det, const size_t pt,
+                                             const size_t NP, double *gradv, double *div, double *vort)
+{
+   double Lm[DIM][DIM];
+#pragma unroll
+   for (int r = 0; r < DIM; r++)
+   {
+#pragma unroll
+      for (int c = 0; c < DIM; c++)
+      {
+         double s = V[r][0] * A[0][c];
+#pragma unroll
+         for (int m = 1; m < DIM; m++) { s += V[r][m] * A[m][c]; }
+         Lm[r][c] = s / det;
+      }
+   }
+   if (gradv)
+   {
+#pragma unroll
+      for (int r = 0; r < DIM; r++)
+      {
+#pragma unroll
+         for (int c = 0; c < DIM; c++) { gradv[(size_t)(r * DIM + c) * NP + pt] = Lm[r][c]; }
+      }
+   }
+   if (div)
+   {
+      double s = Lm[0][0];
+#pragma unroll
+      for (int m = 1; m < DIM; m++) { s += Lm[m][m]; }
+      div[pt] = s;
+   }
+   if (vort)
+   {
+      if constexpr (DIM == 2) { vort[pt] = Lm[1][0] - Lm[0][1]; }
+      if constexpr (DIM == 3)
+      {
+         vort[pt] = Lm[2][1] - Lm[1][2];
+         vort[NP + pt] = Lm[0][2] - Lm[2][0];
+         vort[2 * NP + pt] = Lm[1][0] - Lm[0][1];
+      }
+   }
 }
 
 inline int ipow(int b, int e)

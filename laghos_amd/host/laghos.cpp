@@ -65,6 +65,13 @@ struct Options
    // grad_v, detj, sound_speed, or all (which leaves vorticity out in 1D); the DERIVED_* bits of LagrangianHydroOperator
    bool pv_fields_set = false, pv_vort_named = false; // (named: `vorticity` itself, not through `all`)
    unsigned pv_fields = 0;
+   // -pv-surface / -pv-slice AXIS K: dumps of zone FACES instead of volumes (lgh_sample_faces) - the boundary of the
+   // global mesh, and up to 8 node planes K of the global zone grid along x, y or z (0 <= K <= n: the side-0 faces of zone layer K,
+   // for K = n the side-1 faces of the last layer).  They are written when -paraview writes, with or without it, under
+   // <basename>_surface/ and <basename>_slice_<axis><K>/ with a collection each; -vr and -pv-fields apply.
+   bool pv_surface = false;
+   std::vector<std::pair<int, int>> pv_slices; // (axis, K)
+   bool FaceDumps() const { return pv_surface || !pv_slices.empty(); }
    int dev = 0;
    // multi-rank (set by the launcher, not the reference CLI)
    int nranks = 1, rank = 0;
@@ -307,6 +314,27 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
          if (!o.pv_fields) { err = "-pv-fields needs a list of div_v, vorticity, grad_v, detj, sound_speed, or all: the list is empty"; return false; }
          continue;
       }
+      if (a == "-pv-surface" || a == "--paraview-surface") { o.pv_surface = true; continue; }
+      if (a == "-pv-slice" || a == "--paraview-slice")
+      {
+         if (i + 2 >= argc) { err = "missing value for " + a + " AXIS K"; return false; }
+         if (!(v = need(i))) { return false; }
+         const std::string ax = v;
+         if (ax != "x" && ax != "y" && ax != "z") { err = "-pv-slice AXIS K: the axis must be x, y or z, got " + ax; return false; }
+         if (!(v = need(i))) { return false; }
+         char *end = nullptr;
+         const long K = std::strtol(v, &end, 10);
+         if (end == v || *end || K < 0 || K > 1000000000L) { err = "-pv-slice " + ax + " K: K must be a node plane 0 <= K <= n of the zone grid, got " + std::string(v); return false; }
+         const std::pair<int, int> sl(ax[0] - 'x', (int)K);
+         if (std::find(o.pv_slices.begin(), o.pv_slices.end(), sl) != o.pv_slices.end())
+         {
+            err = "-pv-slice " + ax + " " + std::to_string(K) + " is given twice";
+            return false;
+         }
+         if (o.pv_slices.size() == 8) { err = "-pv-slice " + ax + " " + std::to_string(K) + ": at most 8 slices, this is the ninth"; return false; }
+         o.pv_slices.push_back(sl);
+         continue;
+      }
       if (a == "-store-stress" || a == "--store-stress") { o.store_stress = true; continue; }
       if (a == "-no-store-stress" || a == "--no-store-stress") { o.store_stress = false; continue; }
       if (a == "-renumber" || a == "--renumber") { if (!(v = need(i))) { return false; } o.renumber = v; continue; }
@@ -317,12 +345,12 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
       return false;
    }
    if (!o.vis_refine_set) { o.vis_refine = o.order_v; }
-   if ((o.vis_refine_set || o.paraview) && (o.vis_refine < 1 || o.vis_refine > 8))
+   if ((o.vis_refine_set || o.paraview || o.FaceDumps()) && (o.vis_refine < 1 || o.vis_refine > 8))
    {
       err = "-vr / --vis-refine must be between 1 and 8, got " + std::to_string(o.vis_refine);
       return false;
    }
-   if (o.pv_fields_set && !o.paraview)
+   if (o.pv_fields_set && !o.paraview && !o.FaceDumps())
    {
       err = "-pv-fields adds fields to the -paraview dumps: it needs -paraview";
       return false;
@@ -471,6 +499,16 @@ struct laghos_sim
    Vector pv_rho, pv_dev;
    std::vector<double> pv_host;
    double pv_seconds[3] = {0, 0, 0}; // density + sampling (GPU), device-to-host copy, file write
+   // -pv-surface / -pv-slice: the face lists of this rank (fixed at the start: the mesh is Lagrangian), in the order of the command
+   // line with the surface first; scratch; where the time of their dumps goes
+   struct FaceSet
+   {
+      std::string tag;        // "surface", "slice_z3": the directory is <basename>_<tag>
+      std::vector<int> faces; // (zone, local face) pairs in ascending order
+      Vector dev;
+   };
+   std::vector<FaceSet> pv_faces;
+   double pvf_seconds[3] = {0, 0, 0};
    // -ckpt / -restart: the fingerprint of the set-up arrays, the pieces this run wrote (oldest first; -ckpt-keep removes from
    // this list only), scratch, and where the time of a checkpoint goes
    unsigned long long setup_fp[2] = {0, 0};
@@ -496,9 +534,46 @@ struct laghos_sim
    int steps_at_start = 0;             // RK steps the checkpoint of a restart had taken: timing / FOM cover the restarted segment
 };
 
+// The derived blocks of a dump as the file holds them, in the order of the table of DESIGN.md §7f: point by point, vectors and
+// tensors padded with zeros to 3 and 3 x 3 (the 2D vorticity is the z component).  detj .. cs: the blocks of NP points in the
+// layout of lgh_sample_derived; vort_buf / grad_buf hold the padded copies the returned fields point into.
+static std::vector<VtuField> DerivedVtuFields(unsigned mask, int dim, long NP, const double *detj, const double *grad, const double *div,
+                                              const double *vort, const double *cs, std::vector<double> &vort_buf, std::vector<double> &grad_buf)
+{
+   using H = hydrodynamics::LagrangianHydroOperator;
+   std::vector<VtuField> extra;
+   const int nv = (dim == 3) ? 3 : (dim == 2 ? 1 : 0);
+   if (mask & H::DERIVED_DIV) { extra.push_back({"div_v", 1, div}); }
+   if (mask & H::DERIVED_VORT)
+   {
+      vort_buf.assign(3 * (size_t)NP, 0.0);
+      for (int c = 0; c < nv; c++)
+      {
+         for (long i = 0; i < NP; i++) { vort_buf[3 * i + (dim == 2 ? 2 : c)] = vort[c * NP + i]; }
+      }
+      extra.push_back({"vorticity", 3, vort_buf.data()});
+   }
+   if (mask & H::DERIVED_GRAD)
+   {
+      grad_buf.assign(9 * (size_t)NP, 0.0);
+      for (int a = 0; a < dim; a++)
+      {
+         for (int b = 0; b < dim; b++)
+         {
+            for (long i = 0; i < NP; i++) { grad_buf[9 * i + 3 * a + b] = grad[(a * dim + b) * NP + i]; }
+         }
+      }
+      extra.push_back({"velocity_gradient", 9, grad_buf.data()});
+   }
+   if (mask & H::DERIVED_DETJ) { extra.push_back({"detJ", 1, detj}); }
+   if (mask & H::DERIVED_CS) { extra.push_back({"sound_speed", 1, cs}); }
+   return extra;
+}
+
 // One `-paraview` dump of the state at cycle `cycle` (laghos.cpp:691-701, :845-871): density, lattice values on the GPU, one
 // copy to the host, <basename>_paraview/cycle_<cycle>[.<rank>].vtu; rank 0 adds the .pvtu of a multi-rank cycle and
 // rewrites <basename>.pvd.  rho: the density of this state where the caller (`-print`) has projected it already.
+// (DumpVis below has entered the dump into pv_times / pv_cycles.)
 static bool DumpParaview(laghos_sim *s, int cycle, const Vector *rho = nullptr)
 {
    using clk = std::chrono::steady_clock;
@@ -513,7 +588,6 @@ static bool DumpParaview(laghos_sim *s, int cycle, const Vector *rho = nullptr)
       hydro.ComputeDensity(s->S, s->pv_rho); // rho_gf is refreshed before the output (laghos.cpp:827-830)
       rho = &s->pv_rho;
    }
-   using H = hydrodynamics::LagrangianHydroOperator;
    const long base = (2 * dim + 3) * NP; // the blocks of SampleFields; those of SampleDerived follow in the same vector
    if (o.pv_fields && s->pv_dev.Size() < base + hydro.DerivedSize(R)) { s->pv_dev.SetSize(base + hydro.DerivedSize(R)); }
    hydro.SampleFields(s->S, *rho, R, s->pv_dev);
@@ -526,43 +600,16 @@ static bool DumpParaview(laghos_sim *s, int cycle, const Vector *rho = nullptr)
    const std::string dir = o.basename + "_paraview";
    const size_t slash = o.basename.find_last_of('/');
    const std::string rel_dir = (slash == std::string::npos ? o.basename : o.basename.substr(slash + 1)) + "_paraview";
-   // the derived blocks as the file holds them, in the order of the table of DESIGN.md §7f: point by point, vectors and
-   // tensors padded with zeros to 3 and 3 x 3 (the 2D vorticity is the z component)
    std::vector<VtuField> extra;
    std::vector<double> pv_vort, pv_grad;
    if (o.pv_fields)
    {
       const int nv = (dim == 3) ? 3 : (dim == 2 ? 1 : 0);
       const double *detj = h + base, *grad = detj + NP, *div = grad + (long)dim * dim * NP, *vort = div + NP, *cs = vort + nv * NP;
-      if (o.pv_fields & H::DERIVED_DIV) { extra.push_back({"div_v", 1, div}); }
-      if (o.pv_fields & H::DERIVED_VORT)
-      {
-         pv_vort.assign(3 * (size_t)NP, 0.0);
-         for (int c = 0; c < nv; c++)
-         {
-            for (long i = 0; i < NP; i++) { pv_vort[3 * i + (dim == 2 ? 2 : c)] = vort[c * NP + i]; }
-         }
-         extra.push_back({"vorticity", 3, pv_vort.data()});
-      }
-      if (o.pv_fields & H::DERIVED_GRAD)
-      {
-         pv_grad.assign(9 * (size_t)NP, 0.0);
-         for (int a = 0; a < dim; a++)
-         {
-            for (int b = 0; b < dim; b++)
-            {
-               for (long i = 0; i < NP; i++) { pv_grad[9 * i + 3 * a + b] = grad[(a * dim + b) * NP + i]; }
-            }
-         }
-         extra.push_back({"velocity_gradient", 9, pv_grad.data()});
-      }
-      if (o.pv_fields & H::DERIVED_DETJ) { extra.push_back({"detJ", 1, detj}); }
-      if (o.pv_fields & H::DERIVED_CS) { extra.push_back({"sound_speed", 1, cs}); }
+      extra = DerivedVtuFields(o.pv_fields, dim, NP, detj, grad, div, vort, cs, pv_vort, pv_grad);
    }
    bool ok = WriteVtuFields(dir, dim, s->disc->NE, R + 1, h, h + dim * NP, h + 2 * dim * NP, h + (2 * dim + 1) * NP,
                             h + (2 * dim + 2) * NP, extra, cycle, s->t, o.rank, o.nranks);
-   s->pv_times.push_back(s->t);
-   s->pv_cycles.push_back(cycle);
    if (ok && o.rank == 0)
    {
       if (o.nranks > 1) { ok = WritePvtuFields(dir, cycle, s->t, o.nranks, extra); }
@@ -578,6 +625,115 @@ static bool DumpParaview(laghos_sim *s, int cycle, const Vector *rho = nullptr)
       std::fprintf(stderr, "%s\n", s->error.c_str());
    }
    return ok;
+}
+
+static std::string FaceSetDir(const std::string &basename, const std::string &tag) { return basename + "_" + tag; }
+
+// The faces of this rank's zones on the boundary of the GLOBAL mesh (axis < 0), or on node plane K of the global zone grid along
+// `axis`: from the driver's own structured coordinates - zone j is the structured zone elem_perm[j] of the rank's block, which
+// starts at Partition::eoff in the global grid of CartMesh::ne zones - so the selection holds under -renumber and on several
+// ranks, and an inter-rank interface is no boundary.  Ascending (zone, face).
+static std::vector<int> SelectFaces(const Discretization &d, int axis, int K)
+{
+   std::vector<int> faces;
+   for (int j = 0; j < d.NE; j++)
+   {
+      int l = d.elem_perm.empty() ? j : d.elem_perm[j], g[3] = {0, 0, 0};
+      for (int a = 0; a < d.dim; a++)
+      {
+         g[a] = l % d.part.ne[a] + d.part.eoff[a];
+         l /= d.part.ne[a];
+      }
+      for (int a = 0; a < d.dim; a++)
+      {
+         const int n = d.mesh.ne(a);
+         if (axis < 0)
+         {
+            if (g[a] == 0) { faces.push_back(j); faces.push_back(2 * a); }
+            if (g[a] == n - 1) { faces.push_back(j); faces.push_back(2 * a + 1); }
+         }
+         else if (a == axis)
+         {
+            if (K < n && g[a] == K) { faces.push_back(j); faces.push_back(2 * a); }
+            if (K == n && g[a] == n - 1) { faces.push_back(j); faces.push_back(2 * a + 1); }
+         }
+      }
+   }
+   return faces;
+}
+
+// One face set of the state as it stands into host arrays: the blocks of LagrangianHydroOperator::SampleFaces.
+static void SampleFaceSet(laghos_sim *s, laghos_sim::FaceSet &fs, const Vector &rho, int R, unsigned mask, std::vector<double> &host,
+                          double seconds[2])
+{
+   using clk = std::chrono::steady_clock;
+   auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+   const clk::time_point t0 = clk::now();
+   s->hydro->SampleFaces(s->S, rho, R, fs.faces, mask, fs.dev);
+   s->hydro->Sync();
+   const clk::time_point t1 = clk::now();
+   fs.dev.ToHost(host);
+   const clk::time_point t2 = clk::now();
+   seconds[0] += secs(t0, t1);
+   seconds[1] += secs(t1, t2);
+}
+
+// The `-pv-surface` / `-pv-slice` files of the state at cycle `cycle`: per face set the lattice values on the GPU, one copy to
+// the host, <basename>_<tag>/cycle_<cycle>[.<rank>].vtu (a rank without faces writes an empty piece); rank 0 adds the .pvtu
+// of a multi-rank cycle and rewrites <basename>_<tag>.pvd.
+static bool DumpFaces(laghos_sim *s, int cycle, const Vector &rho)
+{
+   using clk = std::chrono::steady_clock;
+   const Options &o = s->opt;
+   auto &hydro = *s->hydro;
+   const int dim = s->disc->dim, R = o.vis_refine;
+   const int nv = (dim == 3) ? 3 : 1;
+   for (laghos_sim::FaceSet &fs : s->pv_faces)
+   {
+      const int nfaces = (int)fs.faces.size() / 2;
+      const long NPt = hydro.FacePoints(R, nfaces);
+      SampleFaceSet(s, fs, rho, R, o.pv_fields, s->pv_host, s->pvf_seconds);
+      const clk::time_point t2 = clk::now();
+      const double *h = s->pv_host.data();
+      const double *x = h, *v = x + dim * NPt, *e = v + dim * NPt, *r = e + NPt, *p = r + NPt;
+      const double *detj = p + NPt, *grad = detj + NPt, *div = grad + (long)dim * dim * NPt, *vort = div + NPt, *cs = vort + nv * NPt, *an = cs + NPt;
+      std::vector<double> vort_buf, grad_buf;
+      const std::vector<VtuField> extra = DerivedVtuFields(o.pv_fields, dim, NPt, detj, grad, div, vort, cs, vort_buf, grad_buf);
+      const std::string dir = FaceSetDir(o.basename, fs.tag);
+      const size_t slash = o.basename.find_last_of('/');
+      const std::string rel_dir = FaceSetDir(slash == std::string::npos ? o.basename : o.basename.substr(slash + 1), fs.tag);
+      bool ok = WriteVtuFaces(dir, dim, nfaces, fs.faces.data(), R + 1, x, v, e, r, p, extra, an, cycle, s->t, o.rank, o.nranks);
+      if (ok && o.rank == 0)
+      {
+         if (o.nranks > 1) { ok = WritePvtuFaces(dir, cycle, s->t, o.nranks, extra); }
+         ok = ok && WritePvd(dir + ".pvd", rel_dir, s->pv_times, s->pv_cycles, o.nranks);
+      }
+      s->pvf_seconds[2] += std::chrono::duration<double>(clk::now() - t2).count();
+      if (!ok)
+      {
+         s->error = "cannot write the -pv-" + std::string(fs.tag == "surface" ? "surface" : "slice") + " files under " + dir;
+         std::fprintf(stderr, "%s\n", s->error.c_str());
+         return false;
+      }
+   }
+   return true;
+}
+
+// Everything that is written when -paraview writes (cycle 0, ti % vs == 0, the last step): the volume dump and the face dumps, one
+// entry of pv_times / pv_cycles (which the collections list and a checkpoint carries) and one density projection for all.
+static bool DumpVis(laghos_sim *s, int cycle, const Vector *rho = nullptr)
+{
+   const Options &o = s->opt;
+   if (!o.paraview && !o.FaceDumps()) { return true; }
+   s->pv_times.push_back(s->t);
+   s->pv_cycles.push_back(cycle);
+   if (o.FaceDumps() && !rho)
+   {
+      s->hydro->ComputeDensity(s->S, s->pv_rho); // rho_gf is refreshed before the output (laghos.cpp:827-830)
+      rho = &s->pv_rho;
+   }
+   if (o.paraview && !DumpParaview(s, cycle, rho)) { return false; }
+   return !o.FaceDumps() || DumpFaces(s, cycle, *rho);
 }
 
 static std::string Hex32(const unsigned long long fp[2])
@@ -920,6 +1076,27 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
          }
          o.pv_fields &= ~(unsigned)hydrodynamics::LagrangianHydroOperator::DERIVED_VORT; // (all)
       }
+      if (o.FaceDumps() && o.dim == 1)
+      {
+         std::fprintf(stderr, "laghos: %s: zone faces are dumped in 2D and 3D, this mesh is 1D (its -paraview dump is small already)\n",
+                      o.pv_surface ? "-pv-surface" : "-pv-slice");
+         return nullptr;
+      }
+      for (const auto &sl : o.pv_slices)
+      {
+         const char ax = (char)('x' + sl.first);
+         if (sl.first >= o.dim)
+         {
+            std::fprintf(stderr, "laghos: -pv-slice %c %d: the mesh has %d dimensions, there is no %c axis\n", ax, sl.second, o.dim, ax);
+            return nullptr;
+         }
+         if (sl.second > mesh.ne(sl.first))
+         {
+            std::fprintf(stderr, "laghos: -pv-slice %c %d: K is out of range, the zone grid has node planes 0..%d along %c\n", ax, sl.second,
+                         mesh.ne(sl.first), ax);
+            return nullptr;
+         }
+      }
       if (o.prof_axis.empty()) { o.prof_axis = (o.problem == 1) ? "r" : "x"; }
       if (o.prof_steps > 0 && o.prof_axis != "r" && o.prof_axis[0] - 'x' >= o.dim)
       {
@@ -1050,6 +1227,18 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
    }
    if (o.prof_steps > 0) { ProfileSetup(s.get(), S0); }
    if (o.map_steps > 0) { MapSetup(s.get(), S0); }
+   if (o.pv_surface)
+   {
+      s->pv_faces.emplace_back();
+      s->pv_faces.back().tag = "surface";
+      s->pv_faces.back().faces = SelectFaces(d, -1, 0);
+   }
+   for (const auto &sl : o.pv_slices)
+   {
+      s->pv_faces.emplace_back();
+      s->pv_faces.back().tag = std::string("slice_") + (char)('x' + sl.first) + std::to_string(sl.second);
+      s->pv_faces.back().faces = SelectFaces(d, sl.first, sl.second);
+   }
    if (restarting)
    {
       // the set-up data came from S0 as in every run; the state now comes from the file and must have arrived in HBM intact
@@ -1110,7 +1299,7 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
    s->hydro->ResetTimeStepEstimate();                                                // :707
    s->t = 0.0;
    s->dt = s->hydro->GetTimeStepEstimate(s->S);                                      // :708
-   if (o.paraview && !DumpParaview(s.get(), 0)) { return nullptr; }                   // :691-701
+   if (!DumpVis(s.get(), 0)) { return nullptr; }                                      // :691-701
    if (o.hist_steps > 0 && !(HistoryOpen(s.get(), -1) && HistoryRecord(s.get(), 0))) { return nullptr; }
    if (o.prof_steps > 0 && !ProfileRecord(s.get(), 0)) { return nullptr; }
    if (o.map_steps > 0 && !MapRecord(s.get(), 0)) { return nullptr; }
@@ -1195,7 +1384,7 @@ int laghos_sim_step(laghos_sim *s)
                return -1;
             }
          }
-         if (o.paraview && !DumpParaview(s, s->ti, o.gfprint ? &rho : nullptr)) { return -1; } // laghos.cpp:845-871 (one projection for both)
+         if (!DumpVis(s, s->ti, o.gfprint ? &rho : nullptr)) { return -1; } // laghos.cpp:845-871 (one projection for all)
       }
       if (o.check)
       {
@@ -1309,6 +1498,50 @@ int laghos_sim_derived_fields(laghos_sim *s, int R, double *detj, double *gradv,
    take(detj, NP); take(gradv, (long)dim * dim * NP); take(div, NP); take(vort, nv * NP); take(cs, NP);
    return 0;
 }
+// The face lists of the driver's dumps for this rank: kind 0 the boundary of the global mesh (`-pv-surface`), kind 1 node plane K
+// along axis 0..2 (`-pv-slice`).  Returns the number of faces, -1 with laghos_sim_error() set for a bad selection; faces (may be
+// NULL: count only) takes the (zone, local face) pairs.
+int laghos_sim_select_faces(laghos_sim *s, int kind, int axis, int K, int *faces)
+{
+   const Discretization &d = *s->disc;
+   if (d.dim == 1) { s->error = "laghos_sim_select_faces: zone faces are sampled in 2D and 3D"; return -1; }
+   if (kind != 0 && (kind != 1 || axis < 0 || axis >= d.dim || K < 0 || K > d.mesh.ne(axis)))
+   {
+      s->error = "laghos_sim_select_faces: kind " + std::to_string(kind) + ", axis " + std::to_string(axis) + ", K " + std::to_string(K) + " is no surface or slice of this mesh";
+      return -1;
+   }
+   const std::vector<int> f = SelectFaces(d, kind == 0 ? -1 : axis, K);
+   if (faces) { std::copy(f.begin(), f.end(), faces); }
+   return (int)f.size() / 2;
+}
+// lgh_sample_faces of the state as it stands on the lattice of R cells per direction (1 <= R <= 8) of nfaces faces, all outputs,
+// into one host array of LagrangianHydroOperator::FacesSize doubles in the blocks of SampleFaces.  0 = ok; -1 with
+// laghos_sim_error() set.
+int laghos_sim_face_fields(laghos_sim *s, int R, int nfaces, const int *faces, double *out)
+{
+   using H = hydrodynamics::LagrangianHydroOperator;
+   const Discretization &d = *s->disc;
+   if (R < 1 || R > 8) { s->error = "laghos_sim_face_fields: R = " + std::to_string(R) + " is out of range (1 <= R <= 8)"; return -1; }
+   if (d.dim == 1 || nfaces < 0 || (nfaces > 0 && (!faces || !out))) { s->error = "laghos_sim_face_fields: 1D, or a NULL argument"; return -1; }
+   for (int k = 0; k < nfaces; k++)
+   {
+      if (faces[2 * k] < 0 || faces[2 * k] >= d.NE || faces[2 * k + 1] < 0 || faces[2 * k + 1] >= 2 * d.dim)
+      {
+         s->error = "laghos_sim_face_fields: face " + std::to_string(k) + " = (" + std::to_string(faces[2 * k]) + ", " + std::to_string(faces[2 * k + 1]) + ") is out of range";
+         return -1;
+      }
+   }
+   if (nfaces == 0) { return 0; }
+   laghos_sim::FaceSet fs;
+   fs.faces.assign(faces, faces + 2 * (size_t)nfaces);
+   Vector rho;
+   s->hydro->ComputeDensity(s->S, rho);
+   std::vector<double> h;
+   double secs[2] = {0, 0};
+   SampleFaceSet(s, fs, rho, R, H::DERIVED_ALL, h, secs);
+   std::memcpy(out, h.data(), (size_t)s->hydro->FacesSize(R, nfaces) * sizeof(double));
+   return 0;
+}
 double laghos_sim_energy(laghos_sim *s) { return s->hydro->InternalEnergy(s->S) + s->hydro->KineticEnergy(s->S); }
 void laghos_sim_sync(laghos_sim *s) { s->hydro->Sync(); }
 void laghos_sim_enable_timers(laghos_sim *s, int on) { s->hydro->EnableTimers(on != 0); }
@@ -1416,6 +1649,18 @@ int laghos_host_write_vtu_fields(const char *dir, int dim, int NE, int R1, const
 int laghos_host_write_pvtu_fields(const char *dir, int cycle, double time, int nranks, int n_extra, const char *const *names, const int *comps)
 {
    return WritePvtuFields(dir, cycle, time, nranks, HostExtra(n_extra, names, comps, nullptr)) ? 0 : -1;
+}
+// host-only: the writers of the `-pv-surface` / `-pv-slice` pieces (WriteVtuFaces, WritePvtuFaces); 0 = written.  The arrays are
+// host arrays in the layout of lgh_sample_faces
+int laghos_host_write_vtu_faces(const char *dir, int dim, int nfaces, const int *faces, int R1, const double *x, const double *v, const double *e,
+                                const double *rho, const double *p, int n_extra, const char *const *names, const int *comps,
+                                const double *const *data, const double *an, int cycle, double time, int rank, int nranks)
+{
+   return WriteVtuFaces(dir, dim, nfaces, faces, R1, x, v, e, rho, p, HostExtra(n_extra, names, comps, data), an, cycle, time, rank, nranks) ? 0 : -1;
+}
+int laghos_host_write_pvtu_faces(const char *dir, int cycle, double time, int nranks, int n_extra, const char *const *names, const int *comps)
+{
+   return WritePvtuFaces(dir, cycle, time, nranks, HostExtra(n_extra, names, comps, nullptr)) ? 0 : -1;
 }
 // host-only: the derivatives of the H1 basis at the lattice abscissae, G_h1_lat[r + (R+1)*d] ((R+1)*(order_v+1))
 int laghos_host_lattice_grad_table(int order_v, int R, double *G_h1_lat)
@@ -1628,6 +1873,13 @@ int laghos_main(int argc, const char *const *argv)
    {
       std::cout << "ParaView dumps: " << s->pv_cycles.size() << " (sample " << s->pv_seconds[0] << " s, copy " << s->pv_seconds[1]
                 << " s, write " << s->pv_seconds[2] << " s) -> " << o.basename << ".pvd" << std::endl;
+   }
+   if (o.FaceDumps() && !o.quiet)
+   {
+      std::cout << "Face dumps: " << s->pv_cycles.size() << " x " << s->pv_faces.size() << " (sample " << s->pvf_seconds[0] << " s, copy " << s->pvf_seconds[1]
+                << " s, write " << s->pvf_seconds[2] << " s) ->";
+      for (const auto &fs : s->pv_faces) { std::cout << " " << FaceSetDir(o.basename, fs.tag) << ".pvd"; }
+      std::cout << std::endl;
    }
    if (o.ckpt_steps > 0 && !o.quiet)
    {

@@ -276,6 +276,36 @@ void LagrangianHydroOperator::SampleDerived(const Vector &S, int R, unsigned mas
                                  (mask & DERIVED_VORT) ? vort : nullptr, (mask & DERIVED_CS) ? cs : nullptr));
 }
 
+long LagrangianHydroOperator::FacePoints(int R, long nfaces) const
+{
+   long np = nfaces;
+   for (int a = 0; a < dim - 1; a++) { np *= R + 1; }
+   return np;
+}
+
+long LagrangianHydroOperator::FacesSize(int R, long nfaces) const
+{
+   const int nv = (dim == 3) ? 3 : (dim == 2 ? 1 : 0);
+   return (2 * dim + 3 + 3 + dim * dim + nv + dim) * FacePoints(R, nfaces);
+}
+
+void LagrangianHydroOperator::SampleFaces(const Vector &S, const Vector &rho, int R, const std::vector<int> &faces, unsigned mask, Vector &out) const
+{
+   const long nfaces = (long)faces.size() / 2, NPt = FacePoints(R, nfaces);
+   const int nv = (dim == 3) ? 3 : (dim == 2 ? 1 : 0);
+   if (out.Size() < FacesSize(R, nfaces)) { out.SetSize(FacesSize(R, nfaces)); }
+   if (nfaces == 0) { return; }
+   std::vector<double> Bh, Bl, Gh;
+   LatticeTables(disc.tab.order_v, disc.tab.order_e, R, Bh, Bl);
+   LatticeGradTable(disc.tab.order_v, R, Gh);
+   double *o = out.Write();
+   double *x = o, *v = x + dim * NPt, *e = v + dim * NPt, *r = e + NPt, *p = r + NPt;
+   double *detj = p + NPt, *grad = detj + NPt, *div = grad + (long)dim * dim * NPt, *vort = div + NPt, *cs = vort + nv * NPt, *an = cs + NPt;
+   LGH_VERIFY(lgh_sample_faces(ctx, S.Read(), rho.Read(), R + 1, Bh.data(), Gh.data(), Bl.data(), (int)nfaces, faces.data(), x, v, e, r, p,
+                               (mask & DERIVED_DETJ) ? detj : nullptr, (mask & DERIVED_GRAD) ? grad : nullptr, (mask & DERIVED_DIV) ? div : nullptr,
+                               (mask & DERIVED_VORT) ? vort : nullptr, (mask & DERIVED_CS) ? cs : nullptr, an));
+}
+
 void LagrangianHydroOperator::Diagnostics(const Vector &S, double out[LGH_DIAG_COUNT]) const
 {
    LGH_VERIFY(lgh_diagnostics(ctx, S.Read(), out));

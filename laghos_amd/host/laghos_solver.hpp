@@ -102,6 +102,15 @@ public:
    enum { DERIVED_DIV = 1, DERIVED_VORT = 2, DERIVED_GRAD = 4, DERIVED_DETJ = 8, DERIVED_CS = 16, DERIVED_ALL = 31 };
    void SampleDerived(const Vector &S, int R, unsigned mask, Vector &out, long offset = 0) const;
    long DerivedSize(int R) const; // (3 + dim^2 + nv) NP
+   // All of the above on the lattices of a list of zone faces (lgh_sample_faces; the driver's `-pv-surface` / `-pv-slice`):
+   // faces[2k] = zone, faces[2k + 1] = local face 2 axis + side.  With NPt = FacePoints(R, nfaces) = nfaces (R+1)^(dim-1), out holds
+   //    [x | v | e | rho | p | detJ | grad v | div v | vorticity | sound speed | area vector]
+   // in blocks of dim, dim, 1, 1, 1, 1, dim^2, 1, nv, 1, dim times NPt values (FacesSize(R, nfaces) in all).  The five standing
+   // blocks and the area vector are always computed, the derived ones by mask (DERIVED_*).  out is sized anew when it is
+   // smaller.  2D and 3D.  Asynchronous on the context's stream; the quadrature data is not touched.
+   void SampleFaces(const Vector &S, const Vector &rho, int R, const std::vector<int> &faces, unsigned mask, Vector &out) const;
+   long FacePoints(int R, long nfaces) const;
+   long FacesSize(int R, long nfaces) const; // (2 dim + 3 + 3 + dim^2 + nv + dim) NPt
    // Conserved integrals, extremes of the point values and counts of bad points of the state S, folded over zones and ranks
    // (lgh_diagnostics; the rows of the driver's `-hist` file).  Synchronous, collective on several ranks; reads S and the
    // set-up data only - the quadrature data, the force products and dt_est stay as they are.

@@ -69,6 +69,18 @@ bool WriteVtuFields(const std::string &dir, int dim, int NE, int R1, const doubl
 bool WritePvtu(const std::string &dir, int cycle, double time, int nranks);
 // ... whose pieces carry the extra arrays (name and components are read, data is not)
 bool WritePvtuFields(const std::string &dir, int cycle, double time, int nranks, const std::vector<VtuField> &extra);
+// One piece of a surface or slice dump (`-pv-surface`, `-pv-slice`) <dir>/VtuName(): the lattices of nfaces zone
+// faces, faces[2k] = zone, faces[2k + 1] = local face 2 axis + side, NPt = nfaces * R1^(dim-1) points in the layout of
+// lgh_sample_faces (x[c * NPt + pt], ..., an[c * NPt + pt]; pt = k * R1^(dim-1) + r_b + R1 * r_c), duplicated face by face.
+// Cells: R^2 VTK_QUAD per face in 3D, R VTK_LINE in 2D, corners ordered so that the cell's normal (right-hand rule; in 2D
+// the tangent turned clockwise) points out of the zone where det J > 0.  PointData: the four standing arrays, `extra` as
+// WriteVtuFields takes it, then area_normal (3 components); CellData zone, face, rank (Int32); FieldData TIME, CYCLE.  The raw
+// appended layout of WriteVtuFields.  nfaces == 0 writes an empty piece (the arrays may then be null).
+bool WriteVtuFaces(const std::string &dir, int dim, int nfaces, const int *faces, int R1, const double *x, const double *v,
+                   const double *e, const double *rho, const double *p, const std::vector<VtuField> &extra, const double *an, int cycle,
+                   double time, int rank, int nranks);
+// <dir>/PvtuName() for such pieces
+bool WritePvtuFaces(const std::string &dir, int cycle, double time, int nranks, const std::vector<VtuField> &extra);
 // The collection <pvd_path>: one DataSet per dump so far, file = <rel_dir>/<piece or .pvtu>
 bool WritePvd(const std::string &pvd_path, const std::string &rel_dir, const std::vector<double> &times,
               const std::vector<int> &cycles, int nranks);

@@ -72,6 +72,15 @@ def load():
                                                    ctypes.POINTER(P), I, D, I, I]
         L.laghos_host_write_pvtu_fields.restype = I
         L.laghos_host_write_pvtu_fields.argtypes = [ctypes.c_char_p, I, D, I, I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(I)]
+        L.laghos_host_write_vtu_faces.restype = I
+        L.laghos_host_write_vtu_faces.argtypes = [ctypes.c_char_p, I, I, P, I, P, P, P, P, P, I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(I),
+                                                  ctypes.POINTER(P), P, I, D, I, I]
+        L.laghos_host_write_pvtu_faces.restype = I
+        L.laghos_host_write_pvtu_faces.argtypes = [ctypes.c_char_p, I, D, I, I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(I)]
+        L.laghos_sim_select_faces.restype = I
+        L.laghos_sim_select_faces.argtypes = [P, I, I, I, P]
+        L.laghos_sim_face_fields.restype = I
+        L.laghos_sim_face_fields.argtypes = [P, I, I, P, P]
         L.laghos_sim_derived_fields.restype = I
         L.laghos_sim_derived_fields.argtypes = [P, I, P, P, P, P, P]
         ULL = ctypes.c_ulonglong
@@ -216,6 +225,42 @@ class Sim:
                                               out["sound_speed"].ctypes.data)
         if rc != 0:
             raise RuntimeError(f"laghos_sim_derived_fields: error {rc}: {self.L.laghos_sim_error(self.h).decode()}")
+        return out
+
+    def select_faces(self, which):
+        """The faces of this rank's zones a dump of the driver holds: which = "surface" (`-pv-surface`: the boundary of the global
+        mesh) or (axis, K) with axis "x", "y", "z" (`-pv-slice`); (nfaces, 2) ints (zone, local face) in ascending order."""
+        kind, axis, K = (0, 0, 0) if which == "surface" else (1, "xyz".index(which[0]), int(which[1]))
+        n = self.L.laghos_sim_select_faces(self.h, kind, axis, K, None)
+        if n < 0:
+            raise RuntimeError(self.L.laghos_sim_error(self.h).decode())
+        faces = np.zeros((n, 2), np.int32)
+        if n:
+            self.L.laghos_sim_select_faces(self.h, kind, axis, K, faces.ctypes.data)
+        return faces
+
+    def face_fields(self, R, which):
+        """The state as it stands on the face lattices of R cells per direction of a surface or slice dump (lgh_sample_faces; what
+        `-pv-surface` / `-pv-slice` write): which as select_faces takes it, or an (nfaces, 2) array of faces.  A dict of numpy
+        arrays over NPt = nfaces (R+1)^(dim-1) points: x, v, area_normal (dim, NPt), e, rho, p, detj, div_v, sound_speed (NPt), grad_v
+        (dim^2, NPt), vorticity (NPt in 2D, (3, NPt) in 3D), and faces."""
+        faces = self.select_faces(which) if (isinstance(which, str) or isinstance(which[0], str)) else \
+            np.ascontiguousarray(np.asarray(which, dtype=np.int32).reshape(-1, 2))
+        dim = self.sizes()["dim"]
+        nf = faces.shape[0]
+        NPt = nf * (R + 1) ** (dim - 1)
+        nv = 3 if dim == 3 else 1
+        blocks = [("x", dim), ("v", dim), ("e", 1), ("rho", 1), ("p", 1), ("detj", 1), ("grad_v", dim * dim), ("div_v", 1), ("vorticity", nv),
+                  ("sound_speed", 1), ("area_normal", dim)]
+        buf = np.full(sum(c for _, c in blocks) * NPt, np.nan)   # (an entry the library did not write would show)
+        if self.L.laghos_sim_face_fields(self.h, int(R), nf, faces.ctypes.data if nf else None, buf.ctypes.data if nf else None) != 0:
+            raise RuntimeError(f"laghos_sim_face_fields: {self.L.laghos_sim_error(self.h).decode()}")
+        out, pos = {}, 0
+        for k, c in blocks:
+            a = buf[pos:pos + c * NPt]
+            out[k] = a.reshape(c, NPt).copy() if c > 1 else a.copy()
+            pos += c * NPt
+        out["faces"] = faces
         return out
 
     def sedov_error(self):
@@ -380,6 +425,32 @@ def host_write_pvtu_fields(directory, cycle, time, nranks, extra):
     """host_write_pvtu whose pieces carry the extra arrays: extra = [(name, components)] (a third entry is ignored)."""
     n, names, comps, _, _ = _extra_args([(e[0], e[1], None) for e in extra])
     if load().laghos_host_write_pvtu_fields(str(directory).encode(), cycle, time, nranks, n, names, comps) != 0:
+        raise RuntimeError(f"cannot write a .pvtu under {directory}")
+    return os.path.join(str(directory), f"cycle_{cycle:06d}.pvtu")
+
+
+def host_write_vtu_faces(directory, dim, faces, R1, x, v, e, rho, p, extra, area_normal, cycle, time, rank=0, nranks=1):
+    """One `-pv-surface` / `-pv-slice` piece from sampled host arrays in the layout of lgh_sample_faces: faces (nfaces, 2) ints, x, v,
+    area_normal dim * NPt, the others NPt = nfaces * R1^(dim-1); extra as host_write_vtu_fields takes it.  No faces: an empty piece.
+    Returns the path written."""
+    L = load()
+    f = np.ascontiguousarray(np.asarray(faces, dtype=np.int32).reshape(-1, 2))
+    NPt = f.shape[0] * R1 ** (dim - 1)
+    arrs = [_f64(a).reshape(-1) for a in (x, v, e, rho, p, area_normal)]
+    assert [a.size for a in arrs] == [dim * NPt, dim * NPt, NPt, NPt, NPt, dim * NPt]
+    n, names, comps, data, keep = _extra_args(extra, NPt)
+    ptr = lambda a: a.ctypes.data if a.size else None
+    if L.laghos_host_write_vtu_faces(str(directory).encode(), dim, f.shape[0], ptr(f), R1, *[ptr(a) for a in arrs[:5]], n, names, comps, data,
+                                     ptr(arrs[5]), cycle, time, rank, nranks) != 0:
+        raise RuntimeError(f"cannot write a face .vtu under {directory}")
+    tag = f"cycle_{cycle:06d}" + (f".{rank}" if nranks > 1 else "")
+    return os.path.join(str(directory), tag + ".vtu")
+
+
+def host_write_pvtu_faces(directory, cycle, time, nranks, extra):
+    """The .pvtu of such pieces: extra = [(name, components)] (a third entry is ignored)."""
+    n, names, comps, _, _ = _extra_args([(e[0], e[1], None) for e in extra])
+    if load().laghos_host_write_pvtu_faces(str(directory).encode(), cycle, time, nranks, n, names, comps) != 0:
         raise RuntimeError(f"cannot write a .pvtu under {directory}")
     return os.path.join(str(directory), f"cycle_{cycle:06d}.pvtu")
 

@@ -110,6 +110,35 @@ class HydroOperator:
         shape = dict(grad_v=(dim * dim, NP), vorticity=(NP,) if dim == 2 else (3, NP))
         return {k: t.cpu().numpy().reshape(shape.get(k, (NP,))) for k, t in out.items()}
 
+    FACE_FIELDS = ("x", "v", "e", "rho", "p", "detj", "grad_v", "div_v", "vorticity", "sound_speed", "area_normal")
+
+    def face_fields(self, S, R, faces, fields=None):
+        """The fields of the state S on the lattices of R cells per direction of the zone faces `faces` ((nfaces, 2) ints: zone, local
+        face 2 axis + side; Context.sample_faces; what `-pv-surface` / `-pv-slice` write): a dict of numpy arrays over NPt = nfaces
+        (R+1)^(dim-1) points - x, v, area_normal (dim, NPt), e, rho, p, detj, div_v, sound_speed (NPt), grad_v (dim^2, NPt), vorticity
+        (NPt or (3, NPt)) - restricted to `fields` where given, and `faces` itself.  The density is projected on the mesh of S as
+        the dumps do.  Reads S and the set-up data only; 2D and 3D."""
+        import numpy as np
+        from . import host_lib
+        p, ctx = self.p, self.ctx
+        dim = p.dim
+        faces = np.ascontiguousarray(np.asarray(faces, dtype=np.int32).reshape(-1, 2))
+        fields = self.FACE_FIELDS if fields is None else tuple(fields)
+        unknown = [k for k in fields if k not in self.FACE_FIELDS]
+        if unknown:
+            raise ValueError(f"face_fields: unknown fields {unknown}")
+        NPt = faces.shape[0] * (R + 1) ** (dim - 1)
+        Bh, Bl = host_lib.host_lattice_tables(p.order_v, p.order_e, R)
+        Gh = host_lib.host_lattice_grad_table(p.order_v, R)
+        ncomp = dict(x=dim, v=dim, grad_v=dim * dim, vorticity=3 if dim == 3 else 1, area_normal=dim)
+        out = {k: ctx.to_dev(np.full(ncomp.get(k, 1) * NPt, np.nan)) for k in fields}   # (an entry the library did not write would show)
+        rho = self.compute_density(S) if ("rho" in fields or "p" in fields) else None
+        ctx.sample_faces(S, rho, Bh, Gh, Bl, faces, **out)
+        ctx.sync()
+        res = {k: (t.cpu().numpy().reshape(ncomp[k], NPt) if ncomp.get(k, 1) > 1 else t.cpu().numpy()) for k, t in out.items()}
+        res["faces"] = faces
+        return res
+
     def reset_time_step_estimate(self):
         self.ctx.set_dt_est(float("inf"))
 
