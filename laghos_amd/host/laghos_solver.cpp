@@ -263,17 +263,14 @@ long LagrangianHydroOperator::DerivedSize(int R) const
 
 void LagrangianHydroOperator::SampleDerived(const Vector &S, int R, unsigned mask, Vector &out, long offset) const
 {
-   const long NP = SamplePoints(R);
-   const int nv = (dim == 3) ? 3 : (dim == 2 ? 1 : 0);
    if (out.Size() < offset + DerivedSize(R)) { out.SetSize(offset + DerivedSize(R)); }
    std::vector<double> Bh, Bl, Gh;
    LatticeTables(disc.tab.order_v, disc.tab.order_e, R, Bh, Bl);
    LatticeGradTable(disc.tab.order_v, R, Gh);
-   double *o = out.Write() + offset;
-   double *detj = o, *grad = detj + NP, *div = grad + (long)dim * dim * NP, *vort = div + NP, *cs = vort + nv * NP;
-   LGH_VERIFY(lgh_sample_derived(ctx, S.Read(), R + 1, Bh.data(), Gh.data(), Bl.data(), (mask & DERIVED_DETJ) ? detj : nullptr,
-                                 (mask & DERIVED_GRAD) ? grad : nullptr, (mask & DERIVED_DIV) ? div : nullptr,
-                                 (mask & DERIVED_VORT) ? vort : nullptr, (mask & DERIVED_CS) ? cs : nullptr));
+   const DerivedBlocks<double> b(out.Write() + offset, dim, SamplePoints(R));
+   LGH_VERIFY(lgh_sample_derived(ctx, S.Read(), R + 1, Bh.data(), Gh.data(), Bl.data(), (mask & DERIVED_DETJ) ? b.detj : nullptr,
+                                 (mask & DERIVED_GRAD) ? b.grad : nullptr, (mask & DERIVED_DIV) ? b.div : nullptr,
+                                 (mask & DERIVED_VORT) ? b.vort : nullptr, (mask & DERIVED_CS) ? b.cs : nullptr));
 }
 
 long LagrangianHydroOperator::FacePoints(int R, long nfaces) const
@@ -292,7 +289,6 @@ long LagrangianHydroOperator::FacesSize(int R, long nfaces) const
 void LagrangianHydroOperator::SampleFaces(const Vector &S, const Vector &rho, int R, const std::vector<int> &faces, unsigned mask, Vector &out) const
 {
    const long nfaces = (long)faces.size() / 2, NPt = FacePoints(R, nfaces);
-   const int nv = (dim == 3) ? 3 : (dim == 2 ? 1 : 0);
    if (out.Size() < FacesSize(R, nfaces)) { out.SetSize(FacesSize(R, nfaces)); }
    if (nfaces == 0) { return; }
    std::vector<double> Bh, Bl, Gh;
@@ -300,10 +296,10 @@ void LagrangianHydroOperator::SampleFaces(const Vector &S, const Vector &rho, in
    LatticeGradTable(disc.tab.order_v, R, Gh);
    double *o = out.Write();
    double *x = o, *v = x + dim * NPt, *e = v + dim * NPt, *r = e + NPt, *p = r + NPt;
-   double *detj = p + NPt, *grad = detj + NPt, *div = grad + (long)dim * dim * NPt, *vort = div + NPt, *cs = vort + nv * NPt, *an = cs + NPt;
+   const DerivedBlocks<double> b(p + NPt, dim, NPt); // (the area vectors follow them)
    LGH_VERIFY(lgh_sample_faces(ctx, S.Read(), rho.Read(), R + 1, Bh.data(), Gh.data(), Bl.data(), (int)nfaces, faces.data(), x, v, e, r, p,
-                               (mask & DERIVED_DETJ) ? detj : nullptr, (mask & DERIVED_GRAD) ? grad : nullptr, (mask & DERIVED_DIV) ? div : nullptr,
-                               (mask & DERIVED_VORT) ? vort : nullptr, (mask & DERIVED_CS) ? cs : nullptr, an));
+                               (mask & DERIVED_DETJ) ? b.detj : nullptr, (mask & DERIVED_GRAD) ? b.grad : nullptr, (mask & DERIVED_DIV) ? b.div : nullptr,
+                               (mask & DERIVED_VORT) ? b.vort : nullptr, (mask & DERIVED_CS) ? b.cs : nullptr, b.end));
 }
 
 void LagrangianHydroOperator::Diagnostics(const Vector &S, double out[LGH_DIAG_COUNT]) const

@@ -9,6 +9,16 @@
 
 namespace laghos
 {
+
+// The blocks of lgh_sample_derived for NP points, [detJ | grad v | div v | vorticity | sound speed], from where they start
+// (the vorticity has 3 components in 3D, 1 in 2D, none in 1D)
+template <class T> struct DerivedBlocks
+{
+   T *detj, *grad, *div, *vort, *cs, *end;
+   DerivedBlocks(T *p, int dim, long NP)
+      : detj(p), grad(detj + NP), div(grad + (long)dim * dim * NP), vort(div + NP), cs(vort + (dim == 3 ? 3 : (dim == 2 ? 1 : 0)) * NP), end(cs + NP) {}
+};
+
 namespace hydrodynamics
 {
 

@@ -11,8 +11,8 @@ NAME = r"LGH_[A-Z0-9_]*[A-Z0-9]"   # (a literal that ends in "_" is a prefix, no
 NOT_SWITCHES = re.compile(r"LGH_(OK|ERR_\w+|KERNEL_\w+|API)$")
 # rows of the DESIGN.md table that liblaghos_hip.so does not read: the C++ driver's switch
 TABLE_NOT_GETENV = {"LGH_STORE_STRESS"}
-# names the tests and bench.py use without the library reading them: laghos_amd/host/laghos.cpp, laghos_amd/host (and the
-# library), tests/helpers.py (the numbering a test hands to the library)
+# names the tests and bench.py use without the library reading them: laghos_amd/host/laghos.cpp, laghos_amd/host/options.cpp
+# (and the library), tests/helpers.py (the numbering a test hands to the library)
 HOST_AND_TEST_ONLY = {"LGH_STORE_STRESS", "LGH_FORCE_MULTI", "LGH_RENUMBER"}
 
 
