@@ -3,7 +3,7 @@
 // The reference runs every 1D problem with full assembly: `-pa` with dim 1 switches to FA (laghos.cpp:454-462).  In 1D the
 // FA operators are the PA ones with one exception, the energy solve: FA inverts the zone mass matrices Me(z) once at set-up
 // (laghos_solver.cpp:203-215) and applies them zone by zone (:501-515) instead of running an energy CG.  This file holds
-// every kernel of that path; the C entry points of lgh_api.hip / lgh_energy.hip / lgh_sedov.hip send a context with dim == 1 here and the
+// every kernel of that path; the C entry points of lgh_api.hip / lgh_velocity.hip / lgh_energy.hip / lgh_sedov.hip send a context with dim == 1 here and the
 // 2D/3D kernels never see one.
 //
 // Layouts (include/laghos_hip.h): S = [x | v | e] with offsets {0, N, 2N}; stressJinvT[e*NQ + q], Jac0inv[e*NQ + q],

@@ -155,7 +155,7 @@ constexpr double kMassRank1Tol = 1e-12; // relative spread of D / W inside an el
 constexpr double kJac0Tol = 1e-12;      // ... of Jac0inv inside a zone up to which it counts as one matrix per zone (jac0_compact_k)
 
 // Every environment switch of the library (DESIGN.md "Environment switches"), read ONCE per context: a context's switches
-// are those of the environment at its lgh_create (read_switches, lgh_api.hip - the only place that asks the environment,
+// are those of the environment at its lgh_create (read_switches, lgh_switches.hip - the only place that asks the environment,
 // but for the two properties of the shared-memory transport, LGH_SHM_MB and LGH_SHM_TIMEOUT, read where it is opened: ShmGroup::open, lgh_comm_transport.hip).
 // Changing the environment afterwards changes nothing for a context that exists; contexts of one process may differ.
 // Flags are 0 / 1; -1 where "not set" is an answer of its own.  Field x holds LGH_X unless noted.
@@ -237,7 +237,7 @@ struct CtxHandles
 struct lgh_ctx : lgh::CtxHandles
 {
    lgh_ctx();
-   ~lgh_ctx(); // (out of line, lgh_api.hip: where Comm, VcgAux and MeshOrder are complete types)
+   ~lgh_ctx(); // (out of line, lgh_context.hip: where Comm, VcgAux and MeshOrder are complete types)
    lgh::Switches sw;     // the environment switches as they were at lgh_create
    int dim = 0, NE = 0, D1D = 0, Q1D = 0, L1D = 0, ND = 0, NQ = 0, NL = 0, N = 0, H1V = 0, L2V = 0;
    int kid = 0; // (dim<<8)|(D1D<<4)|Q1D, the reference's kernel id
@@ -245,7 +245,7 @@ struct lgh_ctx : lgh::CtxHandles
    double cfl = 0.0, h0 = 0.0, h1order = 0.0;
    double q_tiny_grad = 0.0;   // QUpdate: threshold of the wave-uniform eigen-decomposition shortcut (lgh_qupdate.hip)
    int q_discard = 0;      // QUpdate: which provably unused work is skipped (kQDiscardDt | kQDiscardF1, lgh_qpoint.hpp; LGH_Q_DISCARD)
-   double q_cF = 0.0;      // ... C_F = 3 cG cB^2: |F.1 output| <= C_F max|stressJinvT w detJ| of the zone (q_force_bound, lgh_api.hip)
+   double q_cF = 0.0;      // ... C_F = 3 cG cB^2: |F.1 output| <= C_F max|stressJinvT w detJ| of the zone (q_force_bound, lgh_context.hip)
    int on_stream2 = 0;     // 1 while `stream` holds the second stream (energy solve beside the velocity solve): reductions use the communicator's second channel
    std::unique_ptr<lgh::ScalarCg, void (*)(lgh::ScalarCg *)> l2run{nullptr, lgh::cg_l2_free}; // the run of a split L2 solve (lgh_scg.hip: cg_l2_begin .. cg_l2_end, cg_l2_free), allocated on first use
    const double *accel_src = nullptr; // dim*N acceleration source of SolveVelocity (source_type 2) or nullptr
@@ -585,6 +585,7 @@ __device__ __forceinline__ int xcd_swizzle(const int b, const int nblocks)
 }
 
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+template <typename T> inline T ipow(T b, int e) { T r = 1; for (int i = 0; i < e; i++) { r *= b; } return r; } // b to the power e >= 0
 inline int grid_for(long n) { return (int)std::min<long>(std::max<long>((n + 255) / 256, 1), 2048); } // workgroups of 256 for a grid-stride loop over n
 
 // ---- lgh_order.hip
@@ -600,7 +601,7 @@ int order_scatter_nodes(lgh_ctx *c, const double *in, double *out, int ncomp); /
 int order_gather_bytes(lgh_ctx *c, const uint8_t *in, uint8_t *out);
 int order_zone_blocks(lgh_ctx *c, const double *in, double *out, int per, bool to_caller); // blocks of `per` doubles per zone
 
-// ---- cross-TU launch helpers (implemented in the .hip files) ------------------
+// ---- lgh_force.hip, lgh_mass.hip, lgh_qupdate.hip, lgh_qsetup.hip: the operators and the quadrature data
 int force_mult_E(lgh_ctx *c, const double *sJit, const double *xE, double *yE);
 int force_mult_t_L(lgh_ctx *c, const double *sJit, const double *v_h1, double *y_l2, const int *guard = nullptr);
 int force_mult_t_E(lgh_ctx *c, const double *sJit, const double *vE, double *y_l2);
@@ -609,47 +610,58 @@ int mass_apply_h1(lgh_ctx *c, const double *x, double *y, bool eliminate);
 int mass_apply_l2(lgh_ctx *c, const double *x, double *y);
 int mass_apply_E(lgh_ctx *c, int space, const double *xE, double *yE);
 int mass_assemble_diag(lgh_ctx *c);
-int qupdate_form(lgh_ctx *c); // 1: row form of the 3D quadrature update (lgh_qrows.hpp), 0: point form
 // the quadrature data of the mass operators as (table, element stride in doubles, per-element factor): value(q, e) = Dq[q + dqs e] * Se[e]
 int mass_data(lgh_ctx *c, const double **Dq, int *dqs, const double **Se);
 int l2_mass_form(lgh_ctx *c, int *form, int *compact); // kernel of the L2 mass apply: 2 Kronecker, 1 plane, 0 column (lgh_l2_mass_form)
-int vcg_solve(lgh_ctx *c, double *B, double *X, double rel_tol, int max_iter, int iters[3],
-              const double *force_E = nullptr);
-bool vcg_fused_init_ok(const lgh_ctx *c);
-// tables of the node kernel K2 (lgh_vcg_tables.hip)
-int partition_nodes_by_cost(lgh_ctx *c, int W, DevPtr<int> &out, const std::vector<int> *valence = nullptr);
-int make_ellz(lgh_ctx *c, DevPtr<unsigned> &out, const int *ell = nullptr, int deg = 0);
-int vcg_test_merged_faces(lgh_ctx *c, unsigned char *mask, long *n_merged); // lgh_test_vcg_merged_faces
-int vcg_layout_stats(lgh_ctx *c, long out[4]); // lgh_vcg_layout_stats
-int make_essbits(lgh_ctx *c, DevPtr<uint8_t> &out);
-void vcg_free(lgh_ctx *c); // drops the tables of K2: the next solve builds them again (a communicator has changed)
+int qupdate_form(lgh_ctx *c); // 1: row form of the 3D quadrature update (lgh_qrows.hpp), 0: point form
+int qupdate(lgh_ctx *c, const double *S);
+int setup_rho0detj0(lgh_ctx *c, const double *x0, const double *rho0_l2, const double *rho0_q,
+                    double *volume);
+int interp_energy(lgh_ctx *c, int which, const double *vec, double *result);
+int tg_source_2d(lgh_ctx *c, const double *S, double *out);
+int test_eig(lgh_ctx *c, int dim, int n, const double *A, double *lambda, double *vec);
+int test_singular(lgh_ctx *c, int dim, int n, const double *A, double *sv);
+int test_sqrt(lgh_ctx *c, int n, const double *x, double *y);
 constexpr int kDtSlots = 256, kDtSlotStride = 16; // doubles; slot s at dt_est_dev[kDtSlotStride * (1 + s)]
 // dt_est_dev[kDtHint], one of the padding doubles behind the estimate: the hint word of the row-form update.  It only ever
 // holds +inf, the estimate itself (lgh_set_dt_est) or a value that was also deposited in a slot, so the folded estimate is
 // never above it; a wavefront whose candidates provably lie above it skips them (qpoint_body).  The fold resets it to +inf.
 constexpr int kDtHint = 1;
 enum { kQDiscardDt = 1, kQDiscardF1 = 2 }; // lgh_ctx::q_discard
-constexpr int kYePad = 16; // doubles behind every Y_E plane of the CG; the first one (slot NE*ND) stays 0.0
+
+// ---- lgh_vcg*.hip: the lockstep velocity CG and its test hooks (lgh_vcg_hooks.hip)
+int vcg_solve(lgh_ctx *c, double *B, double *X, double rel_tol, int max_iter, int iters[3],
+              const double *force_E = nullptr);
+bool vcg_fused_init_ok(const lgh_ctx *c);
 bool vcg_available(const lgh_ctx *c);
+int vcg_k1_form(lgh_ctx *c); // 0 column, 2 plane, 3 matrix cores, 4 slab, -1 none
+bool vcg_lockstep_ready(const lgh_ctx *c); // the velocity solve of this context exchanges accumulator words and packs its halo itself
+constexpr int kYePad = 16; // doubles behind every Y_E plane of the CG; the first one (slot NE*ND) stays 0.0
+// tables of the node kernel K2 (lgh_vcg_tables.hip)
+int partition_nodes_by_cost(lgh_ctx *c, int W, DevPtr<int> &out, const std::vector<int> *valence = nullptr);
+int make_ellz(lgh_ctx *c, DevPtr<unsigned> &out, const int *ell = nullptr, int deg = 0);
+int make_essbits(lgh_ctx *c, DevPtr<uint8_t> &out);
+void vcg_free(lgh_ctx *c); // drops the tables of K2: the next solve builds them again (a communicator has changed)
+int vcg_test_merged_faces(lgh_ctx *c, unsigned char *mask, long *n_merged); // lgh_test_vcg_merged_faces
+int vcg_layout_stats(lgh_ctx *c, long out[4]); // lgh_vcg_layout_stats
 int vcg_test_k1(lgh_ctx *c, const double *r, const double *d_old, const double rz[3], const double rz_prev[3], int first,
                 double *YE_out, double den_out[3]); // one launch of K1 (test hook)
 int vcg_test_k2(lgh_ctx *c, int it, const double *YE_in, double *r, double *d, double *x, const double den[3], const double rz[3],
                 const double rz_prev[3], const double alpha_prev[3], double rz_out[3], int *deferred_x); // one launch of K2 (test hook)
 int vcg_test_exact_sum(lgh_ctx *c, int mode, long n, int G, int E, const double *scale, const double *v, const long long *w_in,
                        long long *w_out, double *d_out, int *i_out); // the exact accumulators of lgh_vcg.hpp on their own (test hook)
-int vcg_k1_form(lgh_ctx *c); // 0 column, 2 plane, 3 matrix cores, 4 slab, -1 none
-// multi-rank: flags / list of the nodes shared with other ranks (nullptr / 0 without neighbours)
-void comm_shared_nodes(const lgh_ctx *c, const uint8_t **hmask, const int **sh_node, int *n_shared);
+
+// ---- lgh_scg.hip, lgh_energy.hip: the scalar CG and the energy solve
+int cg_solve(lgh_ctx *c, int space, const double *b, double *x, double rel_tol, int max_iter,
+             int *iters, bool x_is_zero);
+int cg_l2_begin(lgh_ctx *c, const double *b, double *x, double rel_tol, int max_iter);
+int cg_l2_end(lgh_ctx *c, int *iters);
 // Completes the energy solve that lgh_solve_energy_begin enqueued on the second stream - its host looks and, if it has not
 // converged, its further iterations - from INSIDE the velocity solve, while the main stream still has the velocity
 // solve's first chunk of iterations in front of it: lgh_solve_energy_end then only joins the streams (round 6: the looks of
 // the energy solve used to sit between the end of the velocity solve and the RK combination, with the GPU idle).
 int energy_overlap_poll(lgh_ctx *c);
-// Host look without a copy kernel and without the wake-up latency of a blocking stream synchronisation: the one-thread
-// kernel that finishes the scalars writes them, then `token`, into pinned host memory (a.k.a. host_pinned_dev); the host
-// spins on the token word (falls back to hipStreamSynchronize after a while; LGH_SPIN=0: always synchronise).
-int host_wait_token(lgh_ctx *c, volatile unsigned long long *word, unsigned long long token);
-// ---- energy CG in lockstep with the velocity CG (several ranks, one stream, one communicator; round 6).  Its two dot products
+// Energy CG in lockstep with the velocity CG (several ranks, one stream, one communicator; round 6).  Its two dot products
 // per iteration ride on exchanges the velocity iteration makes anyway: (d, M d) as a fourth scalar behind the halo messages
 // (VcgScalars::den_e), (r, r) as a double in word kLsWord of the accumulator-word exchange.  No exchange of its own.
 constexpr int kLsWord = 50;             // (a padding word of an accumulator set: lgh_vcg.hpp checks it is one)
@@ -662,28 +674,11 @@ int l2_lockstep_apply(lgh_ctx *c, int it, const LockstepWords &prev, double *den
 int l2_lockstep_update(lgh_ctx *c, int it, const double *den_src, long long *word_out);
 int l2_lockstep_fold(lgh_ctx *c, int it, const LockstepWords &last); // commits the outcome of iteration it (what the next apply would)
 int cg_l2_end_lockstep(lgh_ctx *c, int *iters); // the rest of the solve on its own (exchanges of its own), the host look
+
+// ---- lgh_comm.hip: several ranks
+// multi-rank: flags / list of the nodes shared with other ranks (nullptr / 0 without neighbours)
+void comm_shared_nodes(const lgh_ctx *c, const uint8_t **hmask, const int **sh_node, int *n_shared);
 int comm_ranks_before(const lgh_ctx *c); // neighbours whose rank is lower than this rank's
-bool vcg_lockstep_ready(const lgh_ctx *c); // the velocity solve of this context exchanges accumulator words and packs its halo itself
-int cg_l2_begin(lgh_ctx *c, const double *b, double *x, double rel_tol, int max_iter);
-int cg_l2_end(lgh_ctx *c, int *iters);
-int cg_solve(lgh_ctx *c, int space, const double *b, double *x, double rel_tol, int max_iter,
-             int *iters, bool x_is_zero);
-int stress_on_hand(lgh_ctx *c, const char *who); // LGH_OK: the stress of the current quadrature data is in memory (lgh_api.hip)
-int qupdate(lgh_ctx *c, const double *S);
-int setup_rho0detj0(lgh_ctx *c, const double *x0, const double *rho0_l2, const double *rho0_q,
-                    double *volume);
-int interp_energy(lgh_ctx *c, int which, const double *vec, double *result);
-int tg_source_2d(lgh_ctx *c, const double *S, double *out);
-int test_eig(lgh_ctx *c, int dim, int n, const double *A, double *lambda, double *vec);
-int test_singular(lgh_ctx *c, int dim, int n, const double *A, double *sv);
-int test_sqrt(lgh_ctx *c, int n, const double *x, double *y);
-int vec_set(lgh_ctx *c, double *y, double a, long n);
-int vec_axpby(lgh_ctx *c, double *z, double a, const double *x, double b, const double *y, long n);
-int vec_axpby_pair(lgh_ctx *c, double *z1, double a1, const double *x1, double b1, double *z2, double a2, const double *x2, double b2,
-                   const double *y, long n);
-int vec_neg_inplace(lgh_ctx *c, double *y, long n);
-int vec_zero_list(lgh_ctx *c, double *y, const int *list, int n);
-int vec_dot(lgh_ctx *c, const double *x, const double *y, const double *w, long n, double *dev_out);
 // packed: the caller's own kernel has already put the node values / scalars into the send buffer of the main channel
 // (HaloPackTables: what it needs for that) - the exchange then starts without a pack kernel
 struct HaloNodeAlias { const int *nodes, *sh_node; }; // the exchange's node lists in another numbering of the SAME nodes (the velocity solve's own)
@@ -709,9 +704,28 @@ int comm_word_peers(lgh_ctx *c, int nwords, const long long **peers, int *n_peer
 int allreduce_dev_n(lgh_ctx *c, double *dev, long count, int op); // any count: in pieces of what the transport takes at a time
 int allreduce_dev(lgh_ctx *c, double *dev, int count, int op, bool packed = false); // packed: as halo_sum (sums that travel as one exchange with every peer only)
 
+// ---- lgh_vec.hip
+int vec_set(lgh_ctx *c, double *y, double a, long n);
+int vec_axpby(lgh_ctx *c, double *z, double a, const double *x, double b, const double *y, long n);
+int vec_axpby_pair(lgh_ctx *c, double *z1, double a1, const double *x1, double b1, double *z2, double a2, const double *x2, double b2,
+                   const double *y, long n);
+int vec_neg_inplace(lgh_ctx *c, double *y, long n);
+int vec_zero_list(lgh_ctx *c, double *y, const int *list, int n);
+int vec_dot(lgh_ctx *c, const double *x, const double *y, const double *w, long n, double *dev_out);
+
+// ---- lgh_api.hip
+// Host look without a copy kernel and without the wake-up latency of a blocking stream synchronisation: the one-thread
+// kernel that finishes the scalars writes them, then `token`, into pinned host memory (a.k.a. host_pinned_dev); the host
+// spins on the token word (falls back to hipStreamSynchronize after a while; LGH_SPIN=0: always synchronise).
+int host_wait_token(lgh_ctx *c, volatile unsigned long long *word, unsigned long long token);
+int stress_on_hand(lgh_ctx *c, const char *who); // LGH_OK: the stress of the current quadrature data is in memory
+int no_1d(const lgh_ctx *c, const char *who);   // LGH_OK: not a 1D context (entry points with no 1D form refuse one)
+
+// ---- lgh_context.hip
+int create_common(const lgh_config *cfg, lgh_ctx *c, std::vector<int> &t_off, std::vector<int> &t_idx); // what create_1d and the 2D/3D create share
+
 // ---- lgh_1d.hip: the 1D path (the entry points send a context with dim == 1 there; the 2D/3D kernels never see one)
 bool kernel_id_supported_1d(int kid);
-int create_common(const lgh_config *cfg, lgh_ctx *c, std::vector<int> &t_off, std::vector<int> &t_idx); // (lgh_api.hip) what create_1d and the 2D/3D create share
 int create_1d(const lgh_config *cfg, lgh_ctx *c);
 int setup_1d(lgh_ctx *c, const double *x0, const double *rho0_l2, const double *rho0_q, double *volume);
 int mass_changed_1d(lgh_ctx *c); // Jacobi diagonal and zone mass factors from the current mass data
@@ -729,6 +743,7 @@ int sedov_density_error_1d(lgh_ctx *c, const double *x_h1, const double *rho_l2,
                            const double origin[3], int n1d, const double *weights, const double *B_h1, const double *G_h1,
                            const double *B_l2, double *err2);
 
+// ---- lgh_timing.hip
 // bracket one launch of kernel `id` with an event pair when sampling is on
 inline void kt_begin(lgh_ctx *c, int id)
 {
@@ -754,6 +769,7 @@ struct KtScope
 
 void timer_start(lgh_ctx *c);
 void timer_stop(lgh_ctx *c, int which);
+void roctx_enable(); // (lgh_create, with LGH_ROCTX=1)
 // roctx range around a region of the host timeline, named after the reference's Caliper regions
 // (/root/reference/laghos_solver.cpp:353-356 "SolveVelocity-ForcePA", :387-390 "SolveVelocity-CGVMass", :472-475
 // "SolveEnergy-ForcePA", :480-483 "SolveEnergy-CGEMass", :1358 "QUpdate-UpdateQuadratureData"): a `rocprofv3 --marker-trace

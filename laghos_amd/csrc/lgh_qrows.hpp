@@ -276,7 +276,7 @@ qrows_kernel(const QArgs a, unsigned long long *trace = nullptr)
    const bool do_f = (a.force_e != nullptr), do_t = (a.erhs_q != nullptr);
    // F.1 of a zone whose outputs are provably flushed.  P7 replaces every output with |v| < eps^2 by +0.0.  An output is a
    // sum of at most 648 terms sjw * (product of three table entries), so |v| <= C_F max|sjw| over the zone (C_F:
-   // q_force_bound, lgh_api.hip), and with a factor 2 for the rounding of the sum: if every |sjw| of the zone is below
+   // q_force_bound, lgh_context.hip), and with a factor 2 for the rounding of the sum: if every |sjw| of the zone is below
    // a.f1_quiet = eps^2 / (2 C_F), all 3 D^3 outputs are +0.0 whatever P5 - P7 compute - they store the zeros and skip the
    // three contractions.  A comparison per value rather than a maximum: a NaN fails it (a maximum would drop it), and a
    // zone with a NaN in its stress keeps computing NaN outputs as before.  Every wavefront writes its verdict to a word of

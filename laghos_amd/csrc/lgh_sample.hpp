@@ -125,11 +125,4 @@ __device__ __forceinline__ void derived_grad(const double (&V)[DIM][DIM], const 
    }
 }
 
-inline int ipow(int b, int e)
-{
-   int r = 1;
-   for (int i = 0; i < e; i++) { r *= b; }
-   return r;
-}
-
 } // namespace lgh

@@ -25,19 +25,19 @@ CSRC = {os.path.basename(p): _read(p) for p in sorted(glob.glob(os.path.join(ROO
 
 
 def library_switches():
-    """names handed to getenv or to one of the parsers of read_switches (lgh_api.hip)"""
-    pattern = r'\b(?:getenv|env_flag|env_long|env_double|env_string)\("(' + NAME + r')"'
+    """names handed to getenv or to one of the parsers of read_switches (lgh_switches.hip)"""
+    pattern = r'\b(?:getenv|env_flag|env_long|env_double|env_string|env_present)\("(' + NAME + r')"'
     return {n for text in CSRC.values() for n in re.findall(pattern, text)}
 
 
 def test_getenv_only_where_the_switches_are_read():
-    """read_switches and the parsers in front of it (lgh_api.hip) - and the two properties of the shared-memory transport,
-    read where it is opened (lgh_comm_transport.hip)"""
+    """the parsers of lgh_switches.hip, each asking for the name it was given - and the two properties of the shared-memory
+    transport, read where it is opened (lgh_comm_transport.hip)"""
+    assert "lgh_switches.hip" in CSRC, "the scan is broken"
     for base, text in CSRC.items():
-        if base == "lgh_api.hip":
-            head, tail = text.split("Switches read_switches()")
-            assert "getenv(" not in tail[tail.index("\n}\n"):], "lgh_api.hip reads the environment behind read_switches"
-            assert set(re.findall(r"getenv\(([^)]*)\)", head)) == {"name"}, "only the parsers call getenv in front of it"
+        if base == "lgh_switches.hip":
+            assert set(re.findall(r"getenv\(([^)]*)\)", text)) == {"name"}, "only the parsers call getenv, with the name they were given"
+            assert text.count("getenv(") == len(re.findall(r"getenv\(name\)", text)), "every getenv of lgh_switches.hip is getenv(name)"
         elif base == "lgh_comm_transport.hip":
             assert sorted(re.findall(r"getenv\(([^)]*)\)", text)) == ['"LGH_SHM_MB"', '"LGH_SHM_TIMEOUT"']
         else:
