@@ -480,6 +480,37 @@ typedef struct lgh_map_spec {
 int lgh_map(lgh_ctx *ctx, const double *S, const lgh_map_spec *spec,
             double *out /* HOST, (ncells + 1) x LGH_MAP_COLS, row-major */, long *n_excluded);
 
+/* ---- pressure loads on lists of zone faces (the driver's `-loads`): the integral of p n dA over walls and logical planes of
+ * the mesh, with the area, the power and the swept volume beside it.  A face is (zone e, local face f = 2a + s) as in
+ * lgh_sample_faces, e the CALLER's zone id; faces[3k], faces[3k+1], faces[3k+2] = e, f and the row the face is summed into.
+ * A face may be listed any number of times, in any order, under any row in 0..nrows-1.  Its points are the tensor Gauss
+ * points of the context's own 1-D rule on the dim - 1 tangential axes (ascending, the lower axis fastest), w the product of
+ * the 1-D weights.  At a point: x, v the H1 traces; N the outward area vector per unit reference area (the an_out of
+ * lgh_sample_faces: Nanson, sign + for s = 1 and - for s = 0, no branch on a determinant); e, rho the traces of the e block
+ * of S and of rho_l2 (the density lgh_compute_density projects) IN ZONE e - the thermodynamic fields are discontinuous, the
+ * zone a face is listed under is part of the definition; p = (gamma_e - 1) rho max(e, 0).  Both 1-D bases interpolate at the
+ * end points, so every trace is a contraction of the face layer of dofs alone.  Columns of a row:
+ *    0 n (points, exact)   1 area = sum w |N|   2-4 force_c = sum w p N_c (exactly +0.0 for c >= dim)   5 pa = sum w p |N|
+ *    6 power = sum w p (v.N)   7 flux = sum w (v.N)   8 xn = sum w (x.N) (dim x the enclosed volume over a closed surface)
+ *    9 p_min, 10 p_max over the row's points, right for negative and zero p (+inf / -inf for an empty row)
+ * A point where a component of x, v or N below dim, or e or rho, is not finite enters no row and is counted in *n_excluded
+ * (summed over the ranks).  Columns 1-8 go through the two-set exact accumulators of lgh_profile / lgh_map, counts and
+ * extremes through integer atomics: no floating-point atomic, and the same bits for every face order, numbering, launch
+ * grid and rank count.  An addend that overflows from finite factors turns its own (row, column) into NaN.
+ * out: HOST, nrows rows of LGH_LOADS_COLS doubles, row-major.  Synchronous; collective over the ranks of the context (a rank
+ * with nfaces == 0 takes part).  Reads S, rho_l2, h1_map, gamma and the tables and writes its outputs only.  2D and 3D.
+ * LGH_ERR_ARG without a launch, the value in the message: dim == 1, a NULL argument, nrows outside 1..LGH_LOADS_MAX_ROWS,
+ * nfaces < 0, a zone, local face or row out of range.  LGH_ERR_UNSUPPORTED: a rule that is no tensor product, a face that
+ * does not fit 64 KB of LDS (the bytes in the message). */
+#define LGH_LOADS_COLS 11
+#define LGH_LOADS_MAX_ROWS 64
+int lgh_loads(lgh_ctx *ctx, const double *S, const double *rho_l2, int nrows,
+              int nfaces, const int *faces /* HOST, 3*nfaces: zone e, local face f = 2a+s, row */,
+              double *out /* HOST, nrows x LGH_LOADS_COLS, row-major */, long *n_excluded);
+/* Faces per workgroup of that kernel for lists long enough (lists of FPB - 1, FPB, FPB + 1 faces are the edges of the launch):
+ * as many as fit 256 points and 48 KB of LDS.  Refuses what lgh_loads refuses of a context. */
+int lgh_loads_fpb(lgh_ctx *ctx, int *fpb);
+
 /* ---- timing data (TimingData, laghos_solver.hpp:39-56): seconds measured with
  * HIP events around the same regions as the reference stopwatches.
  * t[0..3] = cgH1, cgL2, force, qdata; c[0..2] = H1iter, L2iter, quad_tstep */
@@ -506,6 +537,7 @@ int lgh_enable_timers(lgh_ctx *ctx, int on);
 #define LGH_KERNEL_DERIVED 12     /* lgh_sample_derived */
 #define LGH_KERNEL_MAP 13         /* lgh_map: as LGH_KERNEL_PROFILE */
 #define LGH_KERNEL_FACES 14       /* lgh_sample_faces */
+#define LGH_KERNEL_LOADS 15       /* lgh_loads: both passes over the faces and the kernels between and behind them */
 int lgh_ktime_begin(lgh_ctx *ctx, int which, int max_samples);
 int lgh_ktime_end(lgh_ctx *ctx, int *launches, double *mean_seconds);
 /* Whether lgh_create found the 1-D H1 / L2 tables mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (any nodal or

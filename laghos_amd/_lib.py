@@ -104,6 +104,8 @@ SYMBOLS = {
     "lgh_diagnostics": (_I, [_P, _P, c_dbl_p]),
     "lgh_profile": (_I, [_P, _P, ctypes.POINTER(LghProfileSpec), c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
     "lgh_map": (_I, [_P, _P, ctypes.POINTER(LghMapSpec), c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
+    "lgh_loads": (_I, [_P, _P, _P, _I, _I, c_int_p, c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
+    "lgh_loads_fpb": (_I, [_P, ctypes.POINTER(_I)]),
     "lgh_get_timers": (_I, [_P, c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
     "lgh_reset_timers": (_I, [_P]),
     "lgh_enable_timers": (_I, [_P, _I]),

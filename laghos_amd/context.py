@@ -121,6 +121,19 @@ def map_dict(rows, n_excluded, dim, n, lo, hi):
                 p=ratio(col["pv"], col["vol"]))
 
 
+# lgh_loads: the columns of a row (include/laghos_hip.h)
+LOADS_COLS = ("n", "area", "force_x", "force_y", "force_z", "pa", "power", "flux", "xn", "p_min", "p_max")
+LOADS_MAX_ROWS = 64
+
+
+def loads_dict(names, rows, n_excluded, dim):
+    """what HydroOperator.loads and Sim.loads return, from the (nrows, 11) rows of lgh_loads: the names of the rows, the raw
+    rows, `force` (rows[:, 2:2+dim]) and `p_mean` = pa / area, NaN for an empty row"""
+    p_mean = np.full(rows.shape[0], np.nan)
+    np.divide(rows[:, 5], rows[:, 1], out=p_mean, where=(rows[:, 0] != 0))
+    return dict(names=list(names), rows=rows, n_excluded=int(n_excluded), force=rows[:, 2:2 + dim], p_mean=p_mean)
+
+
 def diagnostics_dict(out):
     """the 20 doubles of lgh_diagnostics by name"""
     return {k: (int(out[i]) if k in _DIAG_INTS else float(out[i])) for i, k in enumerate(DIAG_NAMES)}
@@ -596,6 +609,26 @@ class Context:
         n_excl = ctypes.c_long(-1)
         check(self.lib.lgh_map(self.h, _ptr(S), ctypes.byref(spec), _dbl(rows), ctypes.byref(n_excl)))
         return map_dict(rows, n_excl.value, self.dim, n, a, b)
+
+    def loads(self, S, rho_l2, faces, nrows):
+        """lgh_loads: pressure loads on zone faces - `faces` (nfaces, 3) ints (zone, local face 2 axis + side, row), a host array;
+        S and the density dofs rho_l2 device tensors: (rows, n_excluded), rows (nrows, 11) by LOADS_COLS.  Exact, order-free sums:
+        the same bits for every face order, numbering, launch grid and rank count.  Synchronous; 2D and 3D."""
+        f = np.ascontiguousarray(np.asarray(faces, dtype=np.int32).reshape(-1))
+        assert f.size % 3 == 0
+        fp = f.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if f.size else None
+        n_rows = max(1, min(int(nrows), LOADS_MAX_ROWS))   # (a buffer also for a count the library refuses)
+        rows = np.full((n_rows, len(LOADS_COLS)), np.nan)   # (an entry the library did not write would show)
+        n_excl = ctypes.c_long(-1)
+        check(self.lib.lgh_loads(self.h, _ptr(S), _ptr(rho_l2) if rho_l2 is not None else None, int(nrows), f.size // 3, fp, _dbl(rows),
+                                 ctypes.byref(n_excl)))
+        return rows, n_excl.value
+
+    def loads_faces_per_block(self):
+        """lgh_loads_fpb: faces per workgroup of `loads`, for lists long enough."""
+        n = ctypes.c_int(-1)
+        check(self.lib.lgh_loads_fpb(self.h, ctypes.byref(n)))
+        return n.value
 
     def solve_energy_begin(self, S, v, dS, e_rhs, rel_tol, max_iter, e_source=None):
         check(self.lib.lgh_solve_energy_begin(self.h, _ptr(S), _ptr(v), _ptr(dS), _ptr(e_rhs),

@@ -340,6 +340,9 @@ struct lgh_ctx : lgh::CtxHandles
    int map_rows = 0;
    lgh::DevPtr<int> faces_dev; // lgh_sample_faces (lgh_faces.hip): the device copy of the caller's face list, 2 * faces_cap ints; regrown only when a longer list comes
    int faces_cap = 0;
+   lgh::DevPtr<char> loads_dev; // lgh_loads (lgh_loads.hip): the scratch of lgh_map for LGH_LOADS_MAX_ROWS rows, allocated at the first call
+   lgh::DevPtr<int> loads_faces; // ... and the device copy of the caller's list, 3 * loads_cap ints; regrown only when a longer list comes
+   int loads_cap = 0;
    lgh::DevPtr<unsigned long long> fp_dev; // lgh_vec_fingerprint (lgh_fingerprint.hip): the two words of the result and the workgroups' partial words, allocated on first use
 };
 

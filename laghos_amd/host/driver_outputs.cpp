@@ -519,9 +519,34 @@ static bool MapRecord(laghos_sim *s, int cycle)
    return ok;
 }
 
+// The lines of the `-loads` file for the state as it stands, cycle `cycle`: the density and the loads on the GPU (collective; a rank
+// without faces takes part), the lines by rank 0, flushed.
+static bool LoadsRecord(laghos_sim *s, int cycle)
+{
+   long n_excl = 0;
+   s->hydro->ComputeDensity(s->S, s->loads_rho);
+   s->hydro->Loads(s->S, s->loads_rho, (int)s->loads_names.size(), s->loads_faces, s->loads_rows.data(), &n_excl);
+   const bool ok = WriteAndAgree(s, false, "cannot write the -loads file: ", "rank 0 could not write the -loads file", [&](std::string &err) {
+      return HistoryAppend(s->loads_file, LoadsText(cycle, s->t, s->loads_names, s->loads_rows.data()), err);
+   });
+   if (ok) { s->loads_when.Written(cycle); }
+   return ok;
+}
+
+// Opens the `-loads` file on rank 0 as HistoryOpen opens the `-hist` file
+static bool LoadsOpen(laghos_sim *s, int resume_cycle)
+{
+   return WriteAndAgree(s, false, "cannot write the -loads file: ", "rank 0 could not open the -loads file", [&](std::string &err) {
+      const std::string path = LoadsPath(s->opt.basename);
+      LoadsFileInit(s->loads_file);
+      return (resume_cycle < 0) ? HistoryStart(s->loads_file, path, err) : HistoryResume(s->loads_file, path, resume_cycle, err);
+   });
+}
+
 // The periodic outputs in the order a step writes them
 static const struct { Periodic laghos_sim::*when; bool (*write)(laghos_sim *, int cycle); } kPeriodic[] = {
-   {&laghos_sim::ckpt, PeriodicCheckpoint}, {&laghos_sim::hist_when, HistoryRecord}, {&laghos_sim::prof_when, ProfileRecord}, {&laghos_sim::map_when, MapRecord}};
+   {&laghos_sim::ckpt, PeriodicCheckpoint}, {&laghos_sim::hist_when, HistoryRecord}, {&laghos_sim::prof_when, ProfileRecord}, {&laghos_sim::map_when, MapRecord},
+   {&laghos_sim::loads_when, LoadsRecord}};
 
 void SetUpOutputs(laghos_sim *s, const std::vector<double> &S0)
 {
@@ -534,6 +559,12 @@ void SetUpOutputs(laghos_sim *s, const std::vector<double> &S0)
    s->map_when.every = o.map_steps;
    if (o.prof_steps > 0) { ProfileSetup(s, S0); }
    if (o.map_steps > 0) { MapSetup(s, S0); }
+   s->loads_when.every = o.loads_steps;
+   if (o.loads_steps > 0)
+   {
+      LoadsRows(*s->disc, o.loads_planes, s->loads_names, s->loads_faces);
+      s->loads_rows.assign(s->loads_names.size() * LGH_LOADS_COLS, 0.0);
+   }
    auto face_set = [&](const std::string &tag, int axis, int K) {
       s->pv_faces.emplace_back();
       s->pv_faces.back().tag = tag;
@@ -546,7 +577,7 @@ void SetUpOutputs(laghos_sim *s, const std::vector<double> &S0)
 bool OpenPeriodicOutputs(laghos_sim *s, int resume_cycle)
 {
    for (const auto &out : kPeriodic) { (s->*out.when).last = resume_cycle; } // (a restart: the run that wrote the checkpoint has them)
-   return s->hist_when.every <= 0 || HistoryOpen(s, resume_cycle);
+   return (s->hist_when.every <= 0 || HistoryOpen(s, resume_cycle)) && (s->loads_when.every <= 0 || LoadsOpen(s, resume_cycle));
 }
 
 bool WritePeriodicOutputs(laghos_sim *s, Periodic::Moment m, int cycle)

@@ -1,5 +1,5 @@
 // driver_outputs.hpp — the simulation object of the driver and everything it writes: the -paraview / -pv-surface / -pv-slice
-// dumps, -print, checkpoints, and the -hist / -prof / -map recorders with the one cadence they and -ckpt share.
+// dumps, -print, checkpoints, and the -hist / -prof / -map / -loads recorders with the one cadence they and -ckpt share.
 #pragma once
 
 #include <chrono>
@@ -10,6 +10,7 @@
 #include "checkpoint.hpp"
 #include "history.hpp"
 #include "laghos_solver.hpp"
+#include "loads_output.hpp"
 #include "options.hpp"
 
 // When a periodic output is written: at cycle 0, after every accepted step ti with ti % every == 0, after the last step, and -
@@ -102,6 +103,13 @@ struct laghos_sim
    Periodic map_when;
    lgh_map_spec map_spec = {};
    std::vector<double> map_rows;
+   // -loads: the file (rank 0), the rows and the faces listed under them (fixed at the start), the table and the density
+   Periodic loads_when;
+   laghos::HistoryFile loads_file;
+   std::vector<std::string> loads_names;
+   std::vector<int> loads_faces;
+   std::vector<double> loads_rows;
+   laghos::Vector loads_rho;
    int steps_at_start = 0;             // RK steps the checkpoint of a restart had taken: timing / FOM cover the restarted segment
 };
 
@@ -117,7 +125,7 @@ std::string Hex32(const unsigned long long fp[2]);
 void SetUpOutputs(laghos_sim *s, const std::vector<double> &S0);
 // The first thing the periodic outputs do: a restart resumes from cycle resume_cycle >= 0, which has its outputs; -1 starts anew
 bool OpenPeriodicOutputs(laghos_sim *s, int resume_cycle);
-// Writes the periodic outputs due at this moment for the state as it stands, cycle `cycle`: -ckpt, -hist, -prof, -map
+// Writes the periodic outputs due at this moment for the state as it stands, cycle `cycle`: -ckpt, -hist, -prof, -map, -loads
 bool WritePeriodicOutputs(laghos_sim *s, Periodic::Moment m, int cycle);
 
 // `-print`: basename_<ti>_{mesh,rho,v,e} from host copies of the state and the density

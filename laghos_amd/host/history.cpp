@@ -17,14 +17,14 @@ const char *const kHistoryHeader = "# cycle t dt rk_steps repeats mass volume ie
 
 std::string HistoryPath(const std::string &basename) { return basename + "_history.csv"; }
 
-static void AddDouble(std::string &s, double v)
+void AppendDouble(std::string &s, double v)
 {
    char buf[40];
    if (std::isnan(v)) { std::snprintf(buf, sizeof(buf), " nan"); } // (one spelling, whatever the sign bit)
    else { std::snprintf(buf, sizeof(buf), " %.17g", v); }
    s += buf;
 }
-static void AddInt(std::string &s, long long v, bool first = false)
+void AppendInt(std::string &s, long long v, bool first)
 {
    char buf[32];
    std::snprintf(buf, sizeof(buf), first ? "%lld" : " %lld", v);
@@ -34,20 +34,20 @@ static void AddInt(std::string &s, long long v, bool first = false)
 std::string HistoryRow(long cycle, double t, double dt, long rk_steps, long repeats, const double *d, double energy_init)
 {
    std::string s;
-   AddInt(s, cycle, true);
-   AddDouble(s, t);
-   AddDouble(s, dt);
-   AddInt(s, rk_steps);
-   AddInt(s, repeats);
+   AppendInt(s, cycle, true);
+   AppendDouble(s, t);
+   AppendDouble(s, dt);
+   AppendInt(s, rk_steps);
+   AppendInt(s, repeats);
    const double total = d[2] + d[3];
-   for (int k = 0; k < 4; k++) { AddDouble(s, d[k]); } // mass volume ie ke
-   AddDouble(s, total);
-   AddDouble(s, total - energy_init);
-   for (int k = 4; k <= 7; k++) { AddDouble(s, d[k]); } // px py pz detj_min
-   AddInt(s, (long long)d[18]);
-   AddInt(s, (long long)d[17]);
-   for (int k = 8; k <= 13; k++) { AddDouble(s, d[k]); } // rho_min rho_max e_min e_max p_max v_max
-   for (int k = 14; k <= 16; k++) { AddInt(s, (long long)d[k]); }
+   for (int k = 0; k < 4; k++) { AppendDouble(s, d[k]); } // mass volume ie ke
+   AppendDouble(s, total);
+   AppendDouble(s, total - energy_init);
+   for (int k = 4; k <= 7; k++) { AppendDouble(s, d[k]); } // px py pz detj_min
+   AppendInt(s, (long long)d[18]);
+   AppendInt(s, (long long)d[17]);
+   for (int k = 8; k <= 13; k++) { AppendDouble(s, d[k]); } // rho_min rho_max e_min e_max p_max v_max
+   for (int k = 14; k <= 16; k++) { AppendInt(s, (long long)d[k]); }
    s += "\n";
    return s;
 }
@@ -71,7 +71,7 @@ static void MakeDirs(const std::string &path)
 
 static bool Fail(HistoryFile &h, std::string &err, const std::string &what)
 {
-   err = "history " + h.path + ": " + what + (errno ? std::string(": ") + std::strerror(errno) : std::string());
+   err = std::string(h.what) + " " + h.path + ": " + what + (errno ? std::string(": ") + std::strerror(errno) : std::string());
    h.Close();
    return false;
 }
@@ -97,7 +97,7 @@ bool HistoryStart(HistoryFile &h, const std::string &path, std::string &err)
    h.path = path;
    h.rows = 0;
    MakeDirs(path);
-   return Rewrite(h, std::string(kHistoryHeader) + "\n", err);
+   return Rewrite(h, std::string(h.header) + "\n", err);
 }
 
 bool HistoryResume(HistoryFile &h, const std::string &path, long keep_upto, std::string &err)
@@ -128,7 +128,7 @@ bool HistoryResume(HistoryFile &h, const std::string &path, long keep_upto, std:
       if (first)
       {
          first = false;
-         if (line != kHistoryHeader) { errno = 0; return Fail(h, err, "its first line is not the header of a history file: not touched"); }
+         if (line != h.header) { errno = 0; return Fail(h, err, std::string("its first line is not the header of a ") + h.what + " file: not touched"); }
          keep += line + "\n";
          continue;
       }

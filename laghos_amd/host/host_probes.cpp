@@ -11,6 +11,7 @@
 #include "checkpoint.hpp"
 #include "fem.hpp"
 #include "history.hpp"
+#include "loads_output.hpp"
 #include "map_output.hpp"
 #include "vtk_output.hpp"
 
@@ -197,6 +198,37 @@ int laghos_host_history_write(const char *path, long keep_upto, const char *rows
       ok = HistoryAppend(h, all.substr(pos, end - pos), err);
       pos = end;
    }
+   CkptMsg(err, msg, msg_len);
+   if (rows_in_file) { *rows_in_file = h.rows; }
+   return ok ? 0 : -1;
+}
+// host-only: the `-loads` file (loads_output.hpp) the same way.  The header line; the lines of one cycle for nrows rows named by
+// `names` (blank-separated) from nrows x LGH_LOADS_COLS doubles (returns the length, -1 when buf is too small); and the file
+// operation of laghos_host_history_write on a file with the header of the loads file.
+const char *laghos_host_loads_header() { return kLoadsHeader; }
+int laghos_host_loads_text(long cycle, double t, const char *names, const double *rows, char *buf, int len)
+{
+   std::vector<std::string> nm;
+   const std::string all = names ? names : "";
+   for (size_t pos = 0; pos < all.size();)
+   {
+      const size_t sp = std::min(all.find(' ', pos), all.size());
+      if (sp > pos) { nm.push_back(all.substr(pos, sp - pos)); }
+      pos = sp + 1;
+   }
+   const std::string r = LoadsText(cycle, t, nm, rows);
+   if ((int)r.size() + 1 > len) { return -1; }
+   std::memcpy(buf, r.c_str(), r.size() + 1);
+   return (int)r.size();
+}
+int laghos_host_loads_write(const char *path, long keep_upto, const char *lines, long *rows_in_file, char *msg, int msg_len)
+{
+   HistoryFile h;
+   LoadsFileInit(h);
+   std::string err;
+   bool ok = (keep_upto < 0) ? HistoryStart(h, path, err) : HistoryResume(h, path, keep_upto, err);
+   const std::string all = lines ? lines : "";
+   if (ok && !all.empty()) { ok = HistoryAppend(h, all, err); }
    CkptMsg(err, msg, msg_len);
    if (rows_in_file) { *rows_in_file = h.rows; }
    return ok ? 0 : -1;

@@ -443,6 +443,34 @@ int laghos_sim_map(laghos_sim *s, const int *n, const double *lo, const double *
    if (rc != 0) { s->error = lgh_last_error(); }
    return rc;
 }
+// lgh_loads of the state as it stands on the driver's rows (LoadsRows: surface, walls, then nplanes planes given as (axis 0..2, K)
+// pairs; collective on several ranks): rows = (1 + 2 dim + nplanes) x LGH_LOADS_COLS doubles.  0 = ok; otherwise laghos_sim_error()
+// has the message and nothing was written.
+int laghos_sim_loads(laghos_sim *s, int nplanes, const int *planes, double *rows, long *n_excluded)
+{
+   const Discretization &d = *s->disc;
+   if (d.dim == 1) { s->error = "laghos_sim_loads: pressure loads are taken on zone faces in 2D and 3D"; return LGH_ERR_ARG; }
+   if (nplanes < 0 || nplanes > 8 || (nplanes > 0 && !planes) || !rows || !n_excluded) { s->error = "laghos_sim_loads: 0 to 8 planes, no NULL argument"; return LGH_ERR_ARG; }
+   std::vector<std::pair<int, int>> pl;
+   for (int k = 0; k < nplanes; k++)
+   {
+      const int axis = planes[2 * k], K = planes[2 * k + 1];
+      if (axis < 0 || axis >= d.dim || K < 0 || K > d.mesh.ne(axis))
+      {
+         s->error = "laghos_sim_loads: axis " + std::to_string(axis) + ", K " + std::to_string(K) + " is no plane of this mesh";
+         return LGH_ERR_ARG;
+      }
+      pl.emplace_back(axis, K);
+   }
+   std::vector<std::string> names;
+   std::vector<int> faces;
+   LoadsRows(d, pl, names, faces);
+   Vector rho;
+   s->hydro->ComputeDensity(s->S, rho);
+   const int rc = lgh_loads(s->hydro->Context(), s->S.Read(), rho.Read(), (int)names.size(), (int)(faces.size() / 3), faces.data(), rows, n_excluded);
+   if (rc != 0) { s->error = lgh_last_error(); }
+   return rc;
+}
 // lgh_sample_derived of the state as it stands on the lattice of R cells per zone and direction (1 <= R <= 8), into host arrays
 // in the layouts of that entry: detj, div, cs NP = NE (R+1)^dim doubles, gradv dim^2 NP, vort NP (2D) or 3 NP (3D); each may be
 // NULL.  0 = ok; -1 with laghos_sim_error() set for an R out of range or vort in 1D, and nothing was written.
@@ -586,6 +614,7 @@ int laghos_main(int argc, const char *const *argv)
    if (o.hist_steps > 0 && !o.quiet) { std::cout << "History: " << s->hist.path << ", " << s->hist.rows << " rows" << std::endl; }
    if (o.prof_steps > 0 && !o.quiet) { std::cout << "Profiles: " << s->prof_when.count << " files, " << o.basename << "_profile_*.csv" << std::endl; }
    if (o.map_steps > 0 && !o.quiet) { std::cout << "Maps: " << s->map_when.count << " files, " << MapDir(o.basename) << "/cycle_*.vti" << std::endl; }
+   if (o.loads_steps > 0 && !o.quiet) { std::cout << "Loads: " << s->loads_file.path << ", " << s->loads_when.count << " cycles x " << s->loads_names.size() << " rows" << std::endl; }
    int ret = 0;
    if (o.check_exact_sedov)
    {

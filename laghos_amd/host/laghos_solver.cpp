@@ -317,6 +317,11 @@ void LagrangianHydroOperator::Map(const Vector &S, const lgh_map_spec &spec, dou
    LGH_VERIFY(lgh_map(ctx, S.Read(), &spec, rows, n_excluded));
 }
 
+void LagrangianHydroOperator::Loads(const Vector &S, const Vector &rho, int nrows, const std::vector<int> &faces, double *rows, long *n_excluded) const
+{
+   LGH_VERIFY(lgh_loads(ctx, S.Read(), rho.Read(), nrows, (int)(faces.size() / 3), faces.data(), rows, n_excluded));
+}
+
 void LagrangianHydroOperator::SedovEval(const double par[21], double t, const std::vector<double> &r, std::vector<double> &rho,
                                         std::vector<double> &v, std::vector<double> &p) const
 {

@@ -131,6 +131,10 @@ public:
    // The state S binned onto a fixed Cartesian grid (lgh_map; the driver's `-map` files): rows = (ncells + 1) x LGH_MAP_COLS host
    // doubles.  Collective over the ranks.
    void Map(const Vector &S, const lgh_map_spec &spec, double *rows, long *n_excluded) const;
+   // Pressure loads of the state S on lists of zone faces (lgh_loads; the driver's `-loads`): faces holds 3 ints per listed face -
+   // zone, local face, row; rho the density ComputeDensity projects on the mesh of S; rows: HOST, nrows x LGH_LOADS_COLS doubles.
+   // Collective over the ranks (a rank without faces takes part).  Reads S and rho only.
+   void Loads(const Vector &S, const Vector &rho, int nrows, const std::vector<int> &faces, double *rows, long *n_excluded) const;
    // The exact Sedov solution `par` at time t at n radii (host arrays in and out; lgh_sedov_eval on the GPU)
    void SedovEval(const double par[21], double t, const std::vector<double> &r, std::vector<double> &rho, std::vector<double> &v,
                   std::vector<double> &p) const;

@@ -57,7 +57,7 @@ const FlagOpt kFlags[] = {
 const CountOpt kCounts[] = {
    {"-ckpt", "--checkpoint-steps", &Options::ckpt_steps, 1}, {"-ckpt-keep", "--checkpoint-keep", &Options::ckpt_keep, 0},
    {"-hist", "--history-steps", &Options::hist_steps, 1}, {"-prof", "--profile-steps", &Options::prof_steps, 1},
-   {"-map", "--map-steps", &Options::map_steps, 1}};
+   {"-map", "--map-steps", &Options::map_steps, 1}, {"-loads", "--loads-steps", &Options::loads_steps, 1}};
 
 template <class Opt, size_t N> const Opt *Find(const Opt (&table)[N], const std::string &a)
 {
@@ -108,17 +108,17 @@ bool ParseFieldList(const std::string &list, Options &o, std::string &err)
    return true;
 }
 
-// -pv-slice AXIS K, v = AXIS
-bool ParseSlice(const std::string &ax, const char *v, Options &o, std::string &err)
+// -pv-slice AXIS K and -loads-plane AXIS K (opt; its planes are `noun`), v = K: one more entry of `planes`
+bool ParsePlane(const std::string &opt, const char *noun, const std::string &ax, const char *v, std::vector<std::pair<int, int>> &planes, std::string &err)
 {
    char *end = nullptr;
    const long K = std::strtol(v, &end, 10);
-   if (end == v || *end || K < 0 || K > 1000000000L) { return Refuse(err, "-pv-slice " + ax + " K: K must be a node plane 0 <= K <= n of the zone grid, got " + v); }
+   if (end == v || *end || K < 0 || K > 1000000000L) { return Refuse(err, opt + " " + ax + " K: K must be a node plane 0 <= K <= n of the zone grid, got " + v); }
    const std::pair<int, int> sl(ax[0] - 'x', (int)K);
-   const std::string which = "-pv-slice " + ax + " " + std::to_string(K);
-   if (std::find(o.pv_slices.begin(), o.pv_slices.end(), sl) != o.pv_slices.end()) { return Refuse(err, which + " is given twice"); }
-   if (o.pv_slices.size() == 8) { return Refuse(err, which + ": at most 8 slices, this is the ninth"); }
-   o.pv_slices.push_back(sl);
+   const std::string which = opt + " " + ax + " " + std::to_string(K);
+   if (std::find(planes.begin(), planes.end(), sl) != planes.end()) { return Refuse(err, which + " is given twice"); }
+   if (planes.size() == 8) { return Refuse(err, which + ": at most 8 " + noun + ", this is the ninth"); }
+   planes.push_back(sl);
    return true;
 }
 
@@ -227,12 +227,14 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
          if (!ParseFieldList(v, o, err)) { return false; }
          continue;
       }
-      if (a == "-pv-slice" || a == "--paraview-slice")
+      const bool slice = a == "-pv-slice" || a == "--paraview-slice";
+      if (slice || a == "-loads-plane" || a == "--loads-plane")
       {
+         const std::string opt = slice ? "-pv-slice" : "-loads-plane";
          if (i + 2 >= argc) { return Refuse(err, "missing value for " + a + " AXIS K"); }
          const std::string ax = argv[++i];
-         if (ax != "x" && ax != "y" && ax != "z") { return Refuse(err, "-pv-slice AXIS K: the axis must be x, y or z, got " + ax); }
-         if (!ParseSlice(ax, argv[++i], o, err)) { return false; }
+         if (ax != "x" && ax != "y" && ax != "z") { return Refuse(err, opt + " AXIS K: the axis must be x, y or z, got " + ax); }
+         if (!ParsePlane(opt, slice ? "slices" : "planes", ax, argv[++i], slice ? o.pv_slices : o.loads_planes, err)) { return false; }
          continue;
       }
       if (a == "-d" || a == "--device") { if (!need(i)) { return false; } continue; } // always the HIP path
@@ -245,6 +247,7 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
    if (o.pv_fields_set && !o.paraview && !o.FaceDumps()) { return Refuse(err, "-pv-fields adds fields to the -paraview dumps: it needs -paraview"); }
    const char *map_detail = o.map_cells_n > 0 ? "-map-cells" : (o.map_box_n > 0 ? "-map-box" : nullptr);
    if (map_detail && o.map_steps == 0) { return Refuse(err, std::string(map_detail) + " describes the -map files: it needs -map"); }
+   if (!o.loads_planes.empty() && o.loads_steps == 0) { return Refuse(err, "-loads-plane adds rows to the -loads file: it needs -loads"); }
    if (o.check_exact_sedov) // laghos.cpp:303-309, in the reference's words
    {
       if (o.problem != 1) { err = "Can only compare problem 1 (Sedov) against the exact solution"; return false; }
@@ -275,6 +278,13 @@ bool CheckAgainstMesh(Options &o, const CartMesh &mesh, std::string &err)
       if (sl.first >= o.dim) { return Refuse(err, which + ": the mesh has " + dims + " dimensions, there is no " + ax + " axis"); }
       const std::string planes = std::to_string(mesh.ne(sl.first));
       if (sl.second > mesh.ne(sl.first)) { return Refuse(err, which + ": K is out of range, the zone grid has node planes 0.." + planes + " along " + ax); }
+   }
+   if (o.loads_steps > 0 && o.dim == 1) { return Refuse(err, "-loads: pressure loads are taken on zone faces in 2D and 3D, this mesh is 1D"); }
+   for (const auto &pl : o.loads_planes)
+   {
+      const std::string ax(1, (char)('x' + pl.first)), which = "-loads-plane " + ax + " " + std::to_string(pl.second);
+      if (pl.first >= o.dim) { return Refuse(err, which + ": the mesh has " + dims + " dimensions, there is no " + ax + " axis"); }
+      if (pl.second > mesh.ne(pl.first)) { return Refuse(err, which + ": K is out of range, the zone grid has node planes 0.." + std::to_string(mesh.ne(pl.first)) + " along " + ax); }
    }
    if (o.prof_axis.empty()) { o.prof_axis = (o.problem == 1) ? "r" : "x"; }
    const int prof_dims = (o.prof_axis == "r") ? 1 : o.prof_axis[0] - 'x' + 1; // the dimensions the axis needs

@@ -78,6 +78,13 @@ struct Options
    int map_cells_n = 0, map_cells[3] = {64, 64, 64}; // -map-cells NX [NY [NZ]] (default: 64 per axis of the mesh)
    int map_box_n = 0;                                // -map-box X0 X1 [Y0 Y1 [Z0 Z1]] (default: the extent of the initial mesh)
    double map_box[6] = {0, 0, 0, 0, 0, 0};
+   // -loads N: pressure loads (lgh_loads) in <basename>_loads.csv; loads_output.hpp, DESIGN.md §7i.  Per recorded cycle one line for
+   // the boundary of the global mesh, one per wall (x0 x1 y0 y1 [z0 z1]) and one per -loads-plane AXIS K (repeatable, at most 8): node
+   // plane K of the global zone grid along x, y or z by the -pv-slice rule - 0 <= K <= n, the side-0 faces of zone layer K, for K = n the
+   // side-1 faces of the last layer.  The normal on a plane is the OUTWARD normal of the zone a face belongs to: it points towards
+   // lower AXIS for K < n, towards higher AXIS for K = n.  2D and 3D.
+   int loads_steps = 0;
+   std::vector<std::pair<int, int>> loads_planes; // (axis, K)
    bool fingerprint = false;       // -fp: rank 0 prints the state fingerprint after the last step and per checkpoint
 };
 

@@ -102,6 +102,14 @@ def load():
         L.laghos_sim_profile.argtypes = [P, I, I, D, D, P, P, ctypes.POINTER(Lg)]
         L.laghos_sim_map.restype = I
         L.laghos_sim_map.argtypes = [P, P, P, P, P, ctypes.POINTER(Lg)]
+        L.laghos_sim_loads.restype = I
+        L.laghos_sim_loads.argtypes = [P, I, P, P, ctypes.POINTER(Lg)]
+        L.laghos_host_loads_header.restype = ctypes.c_char_p
+        L.laghos_host_loads_header.argtypes = []
+        L.laghos_host_loads_text.restype = I
+        L.laghos_host_loads_text.argtypes = [Lg, D, ctypes.c_char_p, P, ctypes.c_char_p, I]
+        L.laghos_host_loads_write.restype = I
+        L.laghos_host_loads_write.argtypes = [ctypes.c_char_p, Lg, ctypes.c_char_p, ctypes.POINTER(Lg), ctypes.c_char_p, I]
         L.laghos_host_write_vti.restype = I
         L.laghos_host_write_vti.argtypes = [ctypes.c_char_p, I, P, P, P, P, Lg, I, D]
         L.laghos_host_history_header.restype = ctypes.c_char_p
@@ -208,6 +216,21 @@ class Sim:
         if rc != 0:
             raise RuntimeError(f"laghos_sim_map: error {rc}: {self.L.laghos_sim_error(self.h).decode()}")
         return map_dict(rows, n_excl.value, self.sizes()["dim"], n, a, b)
+
+    def loads(self, planes=()):
+        """The pressure loads of the state as it stands on the rows of a `-loads` file (lgh_loads): the boundary of the global
+        mesh, its walls, and the planes given as (axis "x" | "y" | "z", K) in their order - the dict of HydroOperator.loads;
+        every rank calls it."""
+        from .context import LOADS_COLS, loads_dict
+        dim = self.sizes()["dim"]
+        pl = np.asarray([("xyz".index(a), int(K)) for a, K in planes], dtype=np.int32).reshape(-1, 2)
+        names = ["surface"] + [f"{'xyz'[f // 2]}{f % 2}" for f in range(2 * dim)] + [f"plane_{a}{int(K)}" for a, K in planes]
+        rows = np.full((len(names), len(LOADS_COLS)), np.nan)
+        n_excl = ctypes.c_long(-1)
+        rc = self.L.laghos_sim_loads(self.h, len(pl), pl.ctypes.data if len(pl) else None, rows.ctypes.data, ctypes.byref(n_excl))
+        if rc != 0:
+            raise RuntimeError(f"laghos_sim_loads: error {rc}: {self.L.laghos_sim_error(self.h).decode()}")
+        return loads_dict(names, rows, n_excl.value, dim)
 
     def derived_fields(self, R):
         """The derived fields of the state as it stands on the lattice of R cells per zone and direction (lgh_sample_derived;
@@ -498,6 +521,36 @@ def host_history_write(path, rows="", keep_upto=None):
     n = ctypes.c_long(-1)
     msg = ctypes.create_string_buffer(1024)
     rc = load().laghos_host_history_write(str(path).encode(), -1 if keep_upto is None else int(keep_upto), rows.encode(), ctypes.byref(n), msg, len(msg))
+    if rc != 0:
+        raise RuntimeError(msg.value.decode())
+    return n.value
+
+
+LOADS_FILE_COLUMNS = ("cycle", "t", "name", "n", "area", "fx", "fy", "fz", "pa", "p_mean", "power", "flux", "xn", "p_min", "p_max")
+
+
+def host_loads_header():
+    """The first line of a `-loads` file (loads_output.hpp), without its newline."""
+    return load().laghos_host_loads_header().decode()
+
+
+def host_loads_text(cycle, t, names, rows):
+    """The lines of one cycle of a `-loads` file, each with its newline, from the (len(names), 11) rows of lgh_loads."""
+    r = _f64(rows)
+    assert r.size == 11 * len(names)
+    buf = ctypes.create_string_buffer(512 * max(1, len(names)))
+    n = load().laghos_host_loads_text(int(cycle), float(t), " ".join(names).encode(), r.ctypes.data, buf, len(buf))
+    if n < 0:
+        raise RuntimeError("host_loads_text: the lines do not fit")
+    return buf.value.decode()
+
+
+def host_loads_write(path, lines="", keep_upto=None):
+    """The file operations of `-loads` without a GPU, as host_history_write: start anew or resume as `-restart` from cycle
+    keep_upto does, then append `lines` (the lines of a cycle) at once.  Returns lines kept + appends; RuntimeError otherwise."""
+    n = ctypes.c_long(-1)
+    msg = ctypes.create_string_buffer(1024)
+    rc = load().laghos_host_loads_write(str(path).encode(), -1 if keep_upto is None else int(keep_upto), lines.encode(), ctypes.byref(n), msg, len(msg))
     if rc != 0:
         raise RuntimeError(msg.value.decode())
     return n.value

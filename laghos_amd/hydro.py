@@ -139,6 +139,18 @@ class HydroOperator:
         res["faces"] = faces
         return res
 
+    def loads(self, S, groups):
+        """Pressure loads of the state S on groups of zone faces (Context.loads; what `-loads` writes): `groups` a list of
+        (name, faces), faces (n, 2) ints (zone, local face 2 axis + side); a face may stand in several groups.  A dict with `names`,
+        `rows` ((ngroups, 11) by context.LOADS_COLS), `n_excluded`, `force` (rows[:, 2:2+dim]) and `p_mean` (pa / area, NaN for an
+        empty row).  The density is projected on the mesh of S as the dumps do.  Reads S and the set-up data only; 2D and 3D."""
+        import numpy as np
+        from .context import loads_dict
+        lists = [np.asarray(f, dtype=np.int32).reshape(-1, 2) for _, f in groups]
+        faces = np.concatenate([np.concatenate([f, np.full((len(f), 1), r, np.int32)], 1) for r, f in enumerate(lists)]) if lists else np.zeros((0, 3), np.int32)
+        rows, n_excl = self.ctx.loads(S, self.compute_density(S), faces, len(lists))
+        return loads_dict([name for name, _ in groups], rows, n_excl, self.p.dim)
+
     def reset_time_step_estimate(self):
         self.ctx.set_dt_est(float("inf"))
 
