@@ -511,6 +511,55 @@ int lgh_loads(lgh_ctx *ctx, const double *S, const double *rho_l2, int nrows,
  * as many as fit 256 points and 48 KB of LDS.  Refuses what lgh_loads refuses of a context. */
 int lgh_loads_fpb(lgh_ctx *ctx, int *fpb);
 
+/* ---- contours of a lattice scalar: iso-surfaces, and cut planes that are no zone faces (the plane n.x = d is the contour of the
+ * lattice scalar n.x at d).  Marching tetrahedra (3D) / marching triangles (2D) over the volume lattice of lgh_sample_fields;
+ * nothing is located in the moving mesh.  2D and 3D.
+ * INPUT  scalar[NP], a device array on that lattice: R1 points per direction, 2 <= R1 <= 9, NP = NE * R1^dim,
+ *   pt = e * R1^dim + rx + R1 * (ry + R1 * rz), e the CALLER's zone index; and a value iso.
+ * INSIDE  a lattice point is inside when scalar[pt] >= iso (a NaN is outside; see SKIPPED).
+ * SIMPLICES  a sub-cell is the lattice cell with lower corner (rx, ry, rz), r* < R1 - 1, index rx + (R1-1) * (ry + (R1-1) * rz).
+ *   3D: six tetrahedra, the Kuhn split along the diagonal 000-111: tetrahedron k is the path 000 -> e_a -> e_a + e_b -> 111 of
+ *   the k-th permutation (a, b, c) of the axes in lexicographic order (012, 021, 102, 120, 201, 210).  2D: two triangles,
+ *   k = 0: (00, 10, 11), k = 1: (00, 01, 11) - the paths of (x, y) and (y, x).  Corners are numbered 0..dim along the path; their
+ *   lattice indices ascend with it.  The split is translation invariant: neighbouring sub-cells of a zone share diagonals.
+ * VERTEX  on a lattice edge (p0, p1) of a simplex whose ends differ in side, always stored with p0 < p1 as lattice indices, with
+ *   the weight t = (iso - scalar[p0]) / (scalar[p1] - scalar[p0]) in this form in IEEE double: simplices that share an edge
+ *   produce the same (p0, p1, t) to the bit.  A vertex is named by the corners of its edge below: "ab" is the edge of corners a, b.
+ * PRIMITIVES of a simplex (triangles in 3D, segments in 2D; `<` is the path order):
+ *   one corner a inside, o1 < o2 (< o3) outside:      (a o1, a o2 (, a o3))
+ *   one corner o outside, i1 < i2 (< i3) inside:      (i1 o, i2 o (, i3 o))
+ *   3D, a < b inside and c < d outside:               the quad (ac, ad, bd, bc) split along ac-bd: (ac, ad, bd), then (ac, bd, bc)
+ *   ORIENTATION in reference (lattice) coordinates - 3D: the normal by the right-hand rule points from the inside corners to the
+ *   outside ones; 2D: the inside lies to the left of the segment.  Where the order above has the other sense, the LAST TWO
+ *   vertices of the primitive are swapped.  Primitives with coincident vertices (t = 0 or 1) are kept.
+ * SKIPPED  a simplex with a corner value that is not finite produces nothing and is counted in *n_skipped: no NaN reaches an output.
+ * ORDER  ascending (zone in the caller's order, sub-cell, simplex k, primitive as listed): the output is a function of the input
+ *   alone, the same for every launch grid, and a second call gives the same bytes.  No atomic decides a position: a count pass,
+ *   a scan of the workgroup totals, and an emit pass that recomputes the cases and writes at its offset.
+ * OUTPUT per primitive q, device arrays: edges_out[2 dim q + 2 j], [.. + 1] = p0, p1 of vertex j < dim; t_out[dim q + j];
+ *   zone_out[q] = e (may be NULL).  Points are not shared between primitives.
+ * Synchronous in its counts: *n_prims is always the number the input produces.  If *n_prims > capacity NOTHING is written and
+ * the call is still LGH_OK: the caller sizes the buffers and calls again; capacity == 0 with NULL outputs is the counting call.
+ * The emit pass is asynchronous on the context's stream.  LGH_ERR_ARG without a launch, the value in the message: dim == 1, R1
+ * out of range, scalar NULL, capacity < 0, capacity > 0 with edges_out or t_out NULL.  LGH_ERR_UNSUPPORTED: NP above 2^31 - 1.
+ * Reads scalar; writes its outputs and a scratch buffer the context owns (three words per workgroup): the quadrature data,
+ * its generation counter and the fused force products are untouched. */
+int lgh_contour(lgh_ctx *ctx, int R1, const double *scalar, double iso, long capacity,
+                int *edges_out /* 2 dim per primitive */, double *t_out /* dim per primitive */, int *zone_out /* or NULL */,
+                long *n_prims, long *n_skipped);
+/* Any lattice array at the vertices: out[c * n_verts + k] = a + t[k] * (b - a), in this form, with a = field[c * NP + edges[2k]]
+ * and b = field[c * NP + edges[2k + 1]], c < ncomp (exactly a where t == 0).  n_verts = dim * n_prims for the arrays of
+ * lgh_contour.  Device arrays; asynchronous on the context's stream. */
+int lgh_contour_gather(lgh_ctx *ctx, long n_verts, const int *edges, const double *t, int ncomp, long NP,
+                       const double *field /* [c * NP + pt] */, double *out /* [c * n_verts + k] */);
+/* The two scalars that are no block of the sampling kernels, from the x or v block `in` ([c * NP + pt], c < dim; dim 2 or 3):
+ * mode 0: coef[0] * x + coef[1] * y (+ coef[2] * z), each product rounded, summed in this order (the plane family; x, y, z
+ * themselves with unit coefficients); mode 1: sqrt(x^2 + y^2 (+ z^2)) in the same order (|v|; coef may be NULL).  Asynchronous. */
+int lgh_contour_scalar(lgh_ctx *ctx, int mode, long NP, int dim, const double *in, const double coef[4], double *out);
+/* Zones per workgroup of the count and emit kernels: min(16, 1024 / R1^dim), at least 1.  Grids of ZPB - 1, ZPB, ZPB + 1 zones
+ * are the edges of a launch.  LGH_ERR_ARG where lgh_contour refuses dim or R1. */
+int lgh_contour_zpb(lgh_ctx *ctx, int R1, int *zpb);
+
 /* ---- timing data (TimingData, laghos_solver.hpp:39-56): seconds measured with
  * HIP events around the same regions as the reference stopwatches.
  * t[0..3] = cgH1, cgL2, force, qdata; c[0..2] = H1iter, L2iter, quad_tstep */
@@ -538,6 +587,7 @@ int lgh_enable_timers(lgh_ctx *ctx, int on);
 #define LGH_KERNEL_MAP 13         /* lgh_map: as LGH_KERNEL_PROFILE */
 #define LGH_KERNEL_FACES 14       /* lgh_sample_faces */
 #define LGH_KERNEL_LOADS 15       /* lgh_loads: both passes over the faces and the kernels between and behind them */
+#define LGH_KERNEL_CONTOUR 16     /* lgh_contour: the count pass, the scan, the look at the totals and the emit pass of one call */
 int lgh_ktime_begin(lgh_ctx *ctx, int which, int max_samples);
 int lgh_ktime_end(lgh_ctx *ctx, int *launches, double *mean_seconds);
 /* Whether lgh_create found the 1-D H1 / L2 tables mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (any nodal or

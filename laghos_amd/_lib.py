@@ -106,6 +106,10 @@ SYMBOLS = {
     "lgh_map": (_I, [_P, _P, ctypes.POINTER(LghMapSpec), c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
     "lgh_loads": (_I, [_P, _P, _P, _I, _I, c_int_p, c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
     "lgh_loads_fpb": (_I, [_P, ctypes.POINTER(_I)]),
+    "lgh_contour": (_I, [_P, _I, _P, _D, _L, _P, _P, _P, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_long)]),
+    "lgh_contour_gather": (_I, [_P, _L, _P, _P, _I, _L, _P, _P]),
+    "lgh_contour_scalar": (_I, [_P, _I, _L, _I, _P, c_dbl_p, _P]),
+    "lgh_contour_zpb": (_I, [_P, _I, ctypes.POINTER(_I)]),
     "lgh_get_timers": (_I, [_P, c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
     "lgh_reset_timers": (_I, [_P]),
     "lgh_enable_timers": (_I, [_P, _I]),

@@ -630,6 +630,67 @@ class Context:
         check(self.lib.lgh_loads_fpb(self.h, ctypes.byref(n)))
         return n.value
 
+    # ---- contours of a lattice scalar (include/laghos_hip.h: lgh_contour) ----
+    def contour_into(self, scalar, iso, R1, capacity, edges=None, t=None, zone=None):
+        """lgh_contour as it is: `scalar` a device tensor on the lattice of sample_fields (NE * R1^dim), room for `capacity`
+        primitives in the device tensors edges (int32, 2 dim per primitive), t (float64, dim per primitive) and zone (int32, or
+        None); (n_prims, n_skipped).  Nothing is written when n_prims > capacity; capacity 0 without outputs counts."""
+        opt = lambda x, ptr: ptr(x) if x is not None else None
+        n, ns = ctypes.c_long(-1), ctypes.c_long(-1)
+        check(self.lib.lgh_contour(self.h, int(R1), opt(scalar, _ptr), float(iso), int(capacity), opt(edges, self._int_ptr), opt(t, _ptr),
+                                   opt(zone, self._int_ptr), ctypes.byref(n), ctypes.byref(ns)))
+        return n.value, ns.value
+
+    @staticmethod
+    def _int_ptr(x):
+        assert x.is_cuda and x.dtype == torch.int32 and x.is_contiguous()
+        return ctypes.c_void_p(x.data_ptr())
+
+    def contour(self, scalar, iso, R1):
+        """The contour of the lattice scalar at `iso` (marching tetrahedra in 3D, triangles in 2D): the counting call, buffers of
+        the size it names, the emitting call.  (edges, t, zone, n_skipped): device tensors edges (n, dim, 2) int32 - the lattice
+        edge (p0 < p1) of every vertex -, t (n, dim) float64 - its weight on that edge -, zone (n,) int32, in the fixed order of
+        the definition; n_skipped the simplices left out for a value that is not finite.  Synchronous."""
+        dim = self.dim
+        n, ns = self.contour_into(scalar, iso, R1, 0)
+        edges = torch.zeros((n, dim, 2), dtype=torch.int32, device=self.device)
+        t = torch.zeros((n, dim), dtype=torch.float64, device=self.device)
+        zone = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self._torch_done()
+        if n:
+            assert self.contour_into(scalar, iso, R1, n, edges, t, zone) == (n, ns)
+            self.sync()
+        return edges, t, zone, ns
+
+    def contour_gather(self, edges, t, field, ncomp=1):
+        """lgh_contour_gather: the lattice array `field` (device, ncomp * NP, component-major) at the vertices of a contour,
+        a + t (b - a) along each vertex's lattice edge: a device tensor (ncomp, n_verts), vertices in the order of t.reshape(-1).
+        Asynchronous."""
+        nv = int(t.numel())
+        assert edges.numel() == 2 * nv and field.numel() % ncomp == 0
+        out = self.empty(ncomp * nv)
+        check(self.lib.lgh_contour_gather(self.h, nv, self._int_ptr(edges) if nv else None, _ptr(t) if nv else None, int(ncomp),
+                                          field.numel() // ncomp, _ptr(field), _ptr(out) if nv else None))
+        return out.reshape(ncomp, nv)
+
+    def contour_scalar(self, mode, block, coef=None, out=None):
+        """lgh_contour_scalar: from the lattice block `block` (device, dim * NP: x or v of sample_fields) the scalar
+        coef[0] x + coef[1] y (+ coef[2] z) (mode 0 or "plane") or |block| (mode 1 or "norm"), NP values.  Asynchronous."""
+        mode = {"plane": 0, "norm": 1}.get(mode, mode)
+        NP = block.numel() // self.dim
+        c = np.zeros(4)
+        if coef is not None:
+            c[:len(coef)] = coef
+        out = self.empty(NP) if out is None else out
+        check(self.lib.lgh_contour_scalar(self.h, int(mode), NP, self.dim, _ptr(block), _dbl(c), _ptr(out)))
+        return out
+
+    def contour_zpb(self, R1):
+        """lgh_contour_zpb: zones per workgroup of the count and emit kernels of `contour` on R1 lattice points per direction."""
+        n = ctypes.c_int(-1)
+        check(self.lib.lgh_contour_zpb(self.h, int(R1), ctypes.byref(n)))
+        return n.value
+
     def solve_energy_begin(self, S, v, dS, e_rhs, rel_tol, max_iter, e_source=None):
         check(self.lib.lgh_solve_energy_begin(self.h, _ptr(S), _ptr(v), _ptr(dS), _ptr(e_rhs),
                                               _ptr(e_source) if e_source is not None else None,

@@ -343,6 +343,8 @@ struct lgh_ctx : lgh::CtxHandles
    lgh::DevPtr<char> loads_dev; // lgh_loads (lgh_loads.hip): the scratch of lgh_map for LGH_LOADS_MAX_ROWS rows, allocated at the first call
    lgh::DevPtr<int> loads_faces; // ... and the device copy of the caller's list, 3 * loads_cap ints; regrown only when a longer list comes
    int loads_cap = 0;
+   lgh::DevPtr<long long> contour_dev; // lgh_contour (lgh_contour.hip): counts, skipped counts and offsets of contour_cap workgroups (3 n + 2 words); regrown only when the grid grows
+   int contour_cap = 0;
    lgh::DevPtr<unsigned long long> fp_dev; // lgh_vec_fingerprint (lgh_fingerprint.hip): the two words of the result and the workgroups' partial words, allocated on first use
 };
 

@@ -147,7 +147,8 @@ std::string FaceSetDir(const std::string &basename, const std::string &tag) { re
 
 // What rank 0 adds to the pieces of a dump under <basename>_<tag>: the .pvtu of a multi-rank cycle, and the collection `pvd`
 // rewritten with all dumps so far (it names the pieces relative to its own directory).
-static bool WriteCollection(const laghos_sim *s, const std::string &tag, const std::string &pvd, bool faces, const std::vector<VtuField> &extra,
+enum PieceKind { VOLUME_PIECES, FACE_PIECES, CONTOUR_PIECES };
+static bool WriteCollection(const laghos_sim *s, const std::string &tag, const std::string &pvd, PieceKind kind, const std::vector<VtuField> &extra,
                             int cycle)
 {
    const Options &o = s->opt;
@@ -155,7 +156,13 @@ static bool WriteCollection(const laghos_sim *s, const std::string &tag, const s
    const std::string dir = FaceSetDir(o.basename, tag);
    const size_t slash = o.basename.find_last_of('/');
    const std::string rel_dir = FaceSetDir(slash == std::string::npos ? o.basename : o.basename.substr(slash + 1), tag);
-   if (o.nranks > 1 && !(faces ? WritePvtuFaces(dir, cycle, s->t, o.nranks, extra) : WritePvtuFields(dir, cycle, s->t, o.nranks, extra))) { return false; }
+   if (o.nranks > 1)
+   {
+      const bool ok = (kind == FACE_PIECES)      ? WritePvtuFaces(dir, cycle, s->t, o.nranks, extra)
+                      : (kind == CONTOUR_PIECES) ? WritePvtuContour(dir, cycle, s->t, o.nranks, extra)
+                                                 : WritePvtuFields(dir, cycle, s->t, o.nranks, extra);
+      if (!ok) { return false; }
+   }
    return WritePvd(pvd, rel_dir, s->pv_times, s->pv_cycles, o.nranks);
 }
 
@@ -190,7 +197,7 @@ static bool DumpParaview(laghos_sim *s, int cycle, const Vector *rho)
    if (o.pv_fields) { extra = DerivedVtuFields(o.pv_fields, dim, NP, DerivedBlocks<const double>(h + base, dim, NP), vort_buf, grad_buf); }
    const bool ok = WriteVtuFields(dir, dim, s->disc->NE, R + 1, h, h + dim * NP, h + 2 * dim * NP, h + (2 * dim + 1) * NP,
                                   h + (2 * dim + 2) * NP, extra, cycle, s->t, o.rank, o.nranks) &&
-                   WriteCollection(s, "paraview", o.basename + ".pvd", false, extra, cycle);
+                   WriteCollection(s, "paraview", o.basename + ".pvd", VOLUME_PIECES, extra, cycle);
    laps.Lap();
    if (!ok)
    {
@@ -261,7 +268,7 @@ static bool DumpFaces(laghos_sim *s, int cycle, const Vector &rho)
       const std::vector<VtuField> extra = DerivedVtuFields(o.pv_fields, dim, NPt, b, vort_buf, grad_buf);
       const std::string dir = FaceSetDir(o.basename, fs.tag);
       const bool ok = WriteVtuFaces(dir, dim, nfaces, fs.faces.data(), R + 1, x, v, e, r, p, extra, b.end, cycle, s->t, o.rank, o.nranks) &&
-                      WriteCollection(s, fs.tag, dir + ".pvd", true, extra, cycle);
+                      WriteCollection(s, fs.tag, dir + ".pvd", FACE_PIECES, extra, cycle);
       laps.Lap();
       if (!ok)
       {
@@ -273,19 +280,62 @@ static bool DumpFaces(laghos_sim *s, int cycle, const Vector &rho)
    return true;
 }
 
+void SampleContour(laghos_sim *s, const laghos_sim::ContourSet &cs, const Vector &rho, int R, unsigned mask, std::vector<double> &host,
+                   std::vector<int> &zone, long *n_prims, long *n_skipped, Laps &laps)
+{
+   s->hydro->Contour(s->S, rho, R, cs.field, cs.spec.coef, cs.spec.value, mask, s->pvc_lattice, s->pvc_work, s->pvc_dev, zone, n_prims, n_skipped);
+   laps.Lap();
+   s->pvc_dev.ToHost(host);
+   laps.Lap();
+}
+
+// The `-pv-iso` / `-pv-plane` files of the state at cycle `cycle`: per contour the lattice values, the contour and the vertex values
+// on the GPU, one copy to the host, <basename>_<tag>/cycle_<cycle>[.<rank>].vtu (a rank the surface does not touch writes an
+// empty piece); rank 0 adds the .pvtu of a multi-rank cycle and rewrites <basename>_<tag>.pvd.
+static bool DumpContours(laghos_sim *s, int cycle, const Vector &rho)
+{
+   const Options &o = s->opt;
+   const int dim = s->disc->dim, R = o.vis_refine;
+   s->pvc_prims = 0;
+   for (const laghos_sim::ContourSet &cs : s->pv_contours)
+   {
+      Laps laps(s->pvc_seconds);
+      long n = 0, nskip = 0;
+      SampleContour(s, cs, rho, R, o.pv_fields, s->pv_host, s->pvc_zone, &n, &nskip, laps);
+      s->pvc_prims += n;
+      const long nv = dim * n;
+      const double *x = s->pv_host.data(), *v = x + dim * nv, *e = v + dim * nv, *r = e + nv, *p = r + nv;
+      const DerivedBlocks<const double> b(p + nv, dim, nv);
+      std::vector<double> vort_buf, grad_buf;
+      const std::vector<VtuField> extra = DerivedVtuFields(o.pv_fields, dim, nv, b, vort_buf, grad_buf);
+      const std::string dir = FaceSetDir(o.basename, cs.spec.tag);
+      const bool ok = WriteVtuContour(dir, dim, n, s->pvc_zone.data(), x, v, e, r, p, extra, cs.spec.value, cycle, s->t, o.rank, o.nranks) &&
+                      WriteCollection(s, cs.spec.tag, dir + ".pvd", CONTOUR_PIECES, extra, cycle);
+      laps.Lap();
+      if (!ok)
+      {
+         s->error = "cannot write the -pv-" + std::string(cs.spec.field == "plane" ? "plane" : "iso") + " files under " + dir;
+         std::fprintf(stderr, "%s\n", s->error.c_str());
+         return false;
+      }
+   }
+   return true;
+}
+
 bool DumpVis(laghos_sim *s, int cycle, const Vector *rho)
 {
    const Options &o = s->opt;
-   if (!o.paraview && !o.FaceDumps()) { return true; }
+   if (!o.paraview && !o.LatticeDumps()) { return true; }
    s->pv_times.push_back(s->t);
    s->pv_cycles.push_back(cycle);
-   if (o.FaceDumps() && !rho)
+   if (o.LatticeDumps() && !rho)
    {
       s->hydro->ComputeDensity(s->S, s->pv_rho); // (one projection for all)
       rho = &s->pv_rho;
    }
    if (o.paraview && !DumpParaview(s, cycle, rho)) { return false; }
-   return !o.FaceDumps() || DumpFaces(s, cycle, *rho);
+   if (o.FaceDumps() && !DumpFaces(s, cycle, *rho)) { return false; }
+   return !o.ContourDumps() || DumpContours(s, cycle, *rho);
 }
 
 // The fingerprint of this rank's state (own, lgh_vec_fingerprint at offset 0) and of the whole run (all): on one rank the
@@ -571,6 +621,15 @@ void SetUpOutputs(laghos_sim *s, const std::vector<double> &S0)
       s->pv_faces.back().faces = SelectFaces(*s->disc, axis, K);
    };
    if (o.pv_surface) { face_set("surface", -1, 0); }
+   for (const std::vector<Options::Contour> *list : {&o.pv_isos, &o.pv_planes})
+   {
+      for (const Options::Contour &c : *list)
+      {
+         s->pv_contours.emplace_back();
+         s->pv_contours.back().spec = c;
+         s->pv_contours.back().field = (c.field == "plane") ? (int)H::CONTOUR_PLANE : H::ContourField(c.field);
+      }
+   }
    for (const auto &sl : o.pv_slices) { face_set(std::string("slice_") + (char)('x' + sl.first) + std::to_string(sl.second), sl.first, sl.second); }
 }
 

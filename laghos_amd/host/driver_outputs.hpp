@@ -1,5 +1,5 @@
-// driver_outputs.hpp — the simulation object of the driver and everything it writes: the -paraview / -pv-surface / -pv-slice
-// dumps, -print, checkpoints, and the -hist / -prof / -map / -loads recorders with the one cadence they and -ckpt share.
+// driver_outputs.hpp — the simulation object of the driver and everything it writes: the -paraview / -pv-surface / -pv-slice /
+// -pv-iso / -pv-plane dumps, -print, checkpoints, and the -hist / -prof / -map / -loads recorders with the one cadence they and -ckpt share.
 #pragma once
 
 #include <chrono>
@@ -80,6 +80,18 @@ struct laghos_sim
    };
    std::vector<FaceSet> pv_faces;
    double pvf_seconds[3] = {0, 0, 0};
+   // -pv-iso / -pv-plane: the contours in the order of the command line, the iso-surfaces first; scratch (lattice values, the
+   // contour's own arrays, the gathered vertex values); the primitives of this rank in the last dump; where the time goes
+   struct ContourSet
+   {
+      laghos::Options::Contour spec;
+      int field = 0; // LagrangianHydroOperator::CONTOUR_*
+   };
+   std::vector<ContourSet> pv_contours;
+   laghos::Vector pvc_lattice, pvc_work, pvc_dev;
+   std::vector<int> pvc_zone;
+   long pvc_prims = 0;
+   double pvc_seconds[3] = {0, 0, 0};
    // The periodic outputs, each with its cadence (`every` is set by SetUpOutputs)
    // -ckpt / -restart: the fingerprint of the set-up arrays, the pieces this run wrote (oldest first; -ckpt-keep removes from
    // this list only), scratch, and where the time of a checkpoint goes
@@ -131,13 +143,16 @@ bool WritePeriodicOutputs(laghos_sim *s, Periodic::Moment m, int cycle);
 // `-print`: basename_<ti>_{mesh,rho,v,e} from host copies of the state and the density
 bool WriteFields(const std::string &basename, int ti, const Discretization &d, int nranks, int rank, const std::vector<double> &S,
                  const std::vector<double> &rho);
-// Everything that is written when -paraview writes (cycle 0, ti % vs == 0, the last step): the volume dump and the face dumps, one
+// Everything that is written when -paraview writes (cycle 0, ti % vs == 0, the last step): the volume dump, the face dumps and the contour dumps, one
 // entry of pv_times / pv_cycles (which the collections list and a checkpoint carries) and one density projection for all.
 // rho: the density of this state where the caller (`-print`) has projected it already.
 bool DumpVis(laghos_sim *s, int cycle, const Vector *rho = nullptr);
 std::string FaceSetDir(const std::string &basename, const std::string &tag);
 // The faces of this rank's zones on the boundary of the GLOBAL mesh (axis < 0), or on node plane K of the global zone grid along `axis`
 std::vector<int> SelectFaces(const Discretization &d, int axis, int K);
+// One contour of the state as it stands into host arrays: the blocks of LagrangianHydroOperator::Contour and the zones (two laps)
+void SampleContour(laghos_sim *s, const laghos_sim::ContourSet &cs, const Vector &rho, int R, unsigned mask, std::vector<double> &host,
+                   std::vector<int> &zone, long *n_prims, long *n_skipped, Laps &laps);
 // One face set of the state as it stands into host arrays: the blocks of LagrangianHydroOperator::SampleFaces (two laps)
 void SampleFaceSet(laghos_sim *s, laghos_sim::FaceSet &fs, const Vector &rho, int R, unsigned mask, std::vector<double> &host, Laps &laps);
 

@@ -107,6 +107,18 @@ int laghos_host_write_pvtu_faces(const char *dir, int cycle, double time, int nr
 {
    return WritePvtuFaces(dir, cycle, time, nranks, HostExtra(n_extra, names, comps, nullptr)) ? 0 : -1;
 }
+// host-only: the writers of the `-pv-iso` / `-pv-plane` pieces (WriteVtuContour, WritePvtuContour); 0 = written.  The arrays are
+// host arrays in the layout of LagrangianHydroOperator::Contour over dim * nprims points
+int laghos_host_write_vtu_contour(const char *dir, int dim, long nprims, const int *zone, const double *x, const double *v, const double *e,
+                                  const double *rho, const double *p, int n_extra, const char *const *names, const int *comps,
+                                  const double *const *data, double iso_value, int cycle, double time, int rank, int nranks)
+{
+   return WriteVtuContour(dir, dim, nprims, zone, x, v, e, rho, p, HostExtra(n_extra, names, comps, data), iso_value, cycle, time, rank, nranks) ? 0 : -1;
+}
+int laghos_host_write_pvtu_contour(const char *dir, int cycle, double time, int nranks, int n_extra, const char *const *names, const int *comps)
+{
+   return WritePvtuContour(dir, cycle, time, nranks, HostExtra(n_extra, names, comps, nullptr)) ? 0 : -1;
+}
 // host-only: the derivatives of the H1 basis at the lattice abscissae, G_h1_lat[r + (R+1)*d] ((R+1)*(order_v+1))
 int laghos_host_lattice_grad_table(int order_v, int R, double *G_h1_lat)
 {

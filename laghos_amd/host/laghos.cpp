@@ -539,6 +539,52 @@ int laghos_sim_face_fields(laghos_sim *s, int R, int nfaces, const int *faces, d
    std::memcpy(out, h.data(), (size_t)s->hydro->FacesSize(R, nfaces) * sizeof(double));
    return 0;
 }
+// A contour of the state as it stands on the lattice of R cells per direction (1 <= R <= 8), as the driver's `-pv-iso` / `-pv-plane`
+// form it: `field` a name of LagrangianHydroOperator::ContourField or "plane" (then coef holds the dim components of the normal and
+// value is D); mask the DERIVED_* blocks to interpolate.  Returns the number of primitives of this rank and keeps the result in the
+// simulation object until the next call; -1 with laghos_sim_error() set.  laghos_sim_contour_get copies it out: out takes
+// LagrangianHydroOperator::ContourSize(n) doubles in the blocks of Contour, zone n ints.
+long laghos_sim_contour(laghos_sim *s, int R, const char *field, const double *coef, double value, unsigned mask, long *n_skipped)
+{
+   using H = hydrodynamics::LagrangianHydroOperator;
+   const Discretization &d = *s->disc;
+   const std::string name = field ? field : "";
+   const int id = (name == "plane") ? (int)H::CONTOUR_PLANE : H::ContourField(name);
+   if (R < 1 || R > 8) { s->error = "laghos_sim_contour: R = " + std::to_string(R) + " is out of range (1 <= R <= 8)"; return -1; }
+   if (d.dim == 1) { s->error = "laghos_sim_contour: contours are formed in 2D and 3D"; return -1; }
+   if (id < 0 || (id == H::CONTOUR_Z && d.dim == 2)) { s->error = "laghos_sim_contour: unknown field " + name; return -1; }
+   if (!std::isfinite(value) || !n_skipped || (id == H::CONTOUR_PLANE && !coef)) { s->error = "laghos_sim_contour: a value that is not finite, or a NULL argument"; return -1; }
+   laghos_sim::ContourSet cs;
+   cs.field = id;
+   cs.spec.value = value;
+   bool zero = true;
+   for (int k = 0; k < d.dim && id == H::CONTOUR_PLANE; k++)
+   {
+      if (!std::isfinite(coef[k])) { s->error = "laghos_sim_contour: the normal is not finite"; return -1; }
+      cs.spec.coef[k] = coef[k];
+      zero = zero && coef[k] == 0.0;
+   }
+   if (id == H::CONTOUR_PLANE && zero) { s->error = "laghos_sim_contour: the normal is zero"; return -1; }
+   if ((mask & H::DERIVED_VORT) && d.dim == 1) { mask &= ~(unsigned)H::DERIVED_VORT; }
+   s->hydro->ComputeDensity(s->S, s->pv_rho);
+   double secs[3] = {0, 0, 0};
+   Laps laps(secs);
+   long n = 0;
+   SampleContour(s, cs, s->pv_rho, R, mask & H::DERIVED_ALL, s->pv_host, s->pvc_zone, &n, n_skipped, laps);
+   return n;
+}
+int laghos_sim_contour_get(laghos_sim *s, double *out, int *zone)
+{
+   const long n = (long)s->pvc_zone.size(), words = s->hydro->ContourSize(n);
+   if ((long)s->pv_host.size() < words) { s->error = "laghos_sim_contour_get: no contour on hand"; return -1; }
+   if (n > 0 && (!out || !zone)) { s->error = "laghos_sim_contour_get: a NULL argument"; return -1; }
+   if (n > 0)
+   {
+      std::memcpy(out, s->pv_host.data(), (size_t)words * sizeof(double));
+      std::memcpy(zone, s->pvc_zone.data(), (size_t)n * sizeof(int));
+   }
+   return 0;
+}
 double laghos_sim_energy(laghos_sim *s) { return s->hydro->InternalEnergy(s->S) + s->hydro->KineticEnergy(s->S); }
 void laghos_sim_sync(laghos_sim *s) { s->hydro->Sync(); }
 void laghos_sim_enable_timers(laghos_sim *s, int on) { s->hydro->EnableTimers(on != 0); }
@@ -604,6 +650,13 @@ int laghos_main(int argc, const char *const *argv)
       std::cout << "Face dumps: " << s->pv_cycles.size() << " x " << s->pv_faces.size() << " (sample " << s->pvf_seconds[0] << " s, copy " << s->pvf_seconds[1]
                 << " s, write " << s->pvf_seconds[2] << " s) ->";
       for (const auto &fs : s->pv_faces) { std::cout << " " << FaceSetDir(o.basename, fs.tag) << ".pvd"; }
+      std::cout << std::endl;
+   }
+   if (o.ContourDumps() && !o.quiet)
+   {
+      std::cout << "Contour dumps: " << s->pv_cycles.size() << " x " << s->pv_contours.size() << ", " << s->pvc_prims << " primitives in the last (GPU "
+                << s->pvc_seconds[0] << " s, copy " << s->pvc_seconds[1] << " s, write " << s->pvc_seconds[2] << " s) ->";
+      for (const auto &cs : s->pv_contours) { std::cout << " " << FaceSetDir(o.basename, cs.spec.tag) << ".pvd"; }
       std::cout << std::endl;
    }
    if (o.ckpt_steps > 0 && !o.quiet)

@@ -9,6 +9,7 @@
 #include <iomanip>
 #include <iostream>
 #include <limits>
+#include <stdexcept>
 
 namespace laghos
 {
@@ -300,6 +301,86 @@ void LagrangianHydroOperator::SampleFaces(const Vector &S, const Vector &rho, in
    LGH_VERIFY(lgh_sample_faces(ctx, S.Read(), rho.Read(), R + 1, Bh.data(), Gh.data(), Bl.data(), (int)nfaces, faces.data(), x, v, e, r, p,
                                (mask & DERIVED_DETJ) ? b.detj : nullptr, (mask & DERIVED_GRAD) ? b.grad : nullptr, (mask & DERIVED_DIV) ? b.div : nullptr,
                                (mask & DERIVED_VORT) ? b.vort : nullptr, (mask & DERIVED_CS) ? b.cs : nullptr, b.end));
+}
+
+static const char *const kContourFields[] = {"density", "energy", "pressure", "speed", "x", "y", "z", "div_v", "detj", "sound_speed"};
+
+int LagrangianHydroOperator::ContourField(const std::string &name)
+{
+   for (int k = 0; k < CONTOUR_PLANE; k++) { if (name == kContourFields[k]) { return k; } }
+   return -1;
+}
+const char *LagrangianHydroOperator::ContourFieldList() { return "density, energy, pressure, speed, x, y, z, div_v, detj or sound_speed"; }
+
+long LagrangianHydroOperator::ContourSize(long n_prims) const
+{
+   const int nv3 = (dim == 3) ? 3 : (dim == 2 ? 1 : 0);
+   return (2 * dim + 3 + 3 + dim * dim + nv3) * (long)dim * n_prims;
+}
+
+void LagrangianHydroOperator::Contour(const Vector &S, const Vector &rho, int R, int field, const double coef[3], double value, unsigned mask,
+                                      Vector &lattice, Vector &work, Vector &out, std::vector<int> &zone, long *n_prims, long *n_skipped) const
+{
+   const int R1 = R + 1;
+   const long NP = SamplePoints(R), base = (2 * dim + 3) * NP;
+   const unsigned need = mask | (field == CONTOUR_DIV ? DERIVED_DIV : 0) | (field == CONTOUR_DETJ ? DERIVED_DETJ : 0) | (field == CONTOUR_CS ? DERIVED_CS : 0);
+   // lattice = [the blocks of SampleFields | those of SampleDerived where one is needed | a scalar that is no block]
+   const long at_scalar = base + (need ? DerivedSize(R) : 0);
+   if (lattice.Size() < at_scalar + NP) { lattice.SetSize(at_scalar + NP); }
+   SampleFields(S, rho, R, lattice);
+   if (need) { SampleDerived(S, R, need, lattice, base); }
+   double *lat = lattice.Write();
+   const double *x = lat, *v = x + dim * NP, *e = v + dim * NP, *r = e + NP, *p = r + NP;
+   const DerivedBlocks<const double> lb(lat + base, dim, NP);
+   const double *scalar = lat + at_scalar;
+   double c4[4] = {0, 0, 0, 0};
+   switch (field)
+   {
+      case CONTOUR_DENSITY: scalar = r; break;
+      case CONTOUR_ENERGY: scalar = e; break;
+      case CONTOUR_PRESSURE: scalar = p; break;
+      case CONTOUR_DIV: scalar = lb.div; break;
+      case CONTOUR_DETJ: scalar = lb.detj; break;
+      case CONTOUR_CS: scalar = lb.cs; break;
+      case CONTOUR_SPEED: LGH_VERIFY(lgh_contour_scalar(ctx, 1, NP, dim, v, c4, lat + at_scalar)); break;
+      case CONTOUR_PLANE:
+         for (int k = 0; k < dim; k++) { c4[k] = coef[k]; }
+         LGH_VERIFY(lgh_contour_scalar(ctx, 0, NP, dim, x, c4, lat + at_scalar));
+         break;
+      default: // x, y, z: the plane of a unit normal
+         c4[field - CONTOUR_X] = 1.0;
+         LGH_VERIFY(lgh_contour_scalar(ctx, 0, NP, dim, x, c4, lat + at_scalar));
+   }
+   long n = 0, ns = 0;
+   LGH_VERIFY(lgh_contour(ctx, R1, scalar, value, 0, nullptr, nullptr, nullptr, &n, &ns));
+   *n_prims = n;
+   *n_skipped = ns;
+   zone.assign((size_t)n, 0);
+   if (out.Size() < ContourSize(n)) { out.SetSize(ContourSize(n)); }
+   if (n == 0) { return; }
+   // work = [t | edges | zone]: dim n doubles, 2 dim n ints, n ints
+   const long nv = (long)dim * n, words = 2 * nv + (n + 1) / 2;
+   if (work.Size() < words) { work.SetSize(words); }
+   double *t = work.Write();
+   int *edges = reinterpret_cast<int *>(t + nv), *zdev = edges + 2 * nv;
+   long n2 = 0;
+   LGH_VERIFY(lgh_contour(ctx, R1, scalar, value, n, edges, t, zdev, &n2, &ns));
+   if (n2 != n) { throw std::runtime_error("lgh_contour: the counting and the emitting call disagree"); }
+   double *o = out.Write();
+   auto gather = [&](const double *block, int ncomp, double *dst) { LGH_VERIFY(lgh_contour_gather(ctx, nv, edges, t, ncomp, NP, block, dst)); };
+   gather(x, dim, o);
+   gather(v, dim, o + dim * nv);
+   gather(e, 1, o + 2 * dim * nv);
+   gather(r, 1, o + (2 * dim + 1) * nv);
+   gather(p, 1, o + (2 * dim + 2) * nv);
+   const DerivedBlocks<double> ob(o + (2 * dim + 3) * nv, dim, nv);
+   if (mask & DERIVED_DETJ) { gather(lb.detj, 1, ob.detj); }
+   if (mask & DERIVED_GRAD) { gather(lb.grad, dim * dim, ob.grad); }
+   if (mask & DERIVED_DIV) { gather(lb.div, 1, ob.div); }
+   if ((mask & DERIVED_VORT) && dim > 1) { gather(lb.vort, dim == 3 ? 3 : 1, ob.vort); }
+   if (mask & DERIVED_CS) { gather(lb.cs, 1, ob.cs); }
+   Sync();
+   if (hipMemcpy(zone.data(), zdev, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { throw std::runtime_error("hipMemcpy of the contour's zones"); }
 }
 
 void LagrangianHydroOperator::Diagnostics(const Vector &S, double out[LGH_DIAG_COUNT]) const

@@ -121,6 +121,21 @@ public:
    void SampleFaces(const Vector &S, const Vector &rho, int R, const std::vector<int> &faces, unsigned mask, Vector &out) const;
    long FacePoints(int R, long nfaces) const;
    long FacesSize(int R, long nfaces) const; // (2 dim + 3 + 3 + dim^2 + nv + dim) NPt
+   // A contour of the state S, formed on the lattice of R + 1 points per direction (lgh_contour; the driver's `-pv-iso` / `-pv-plane`):
+   // the iso-surface field = value of one of the fields below, or - field CONTOUR_PLANE - the cut plane coef . x = value.  Runs, in
+   // this order, SampleFields (and SampleDerived where the field or the mask needs it) into `lattice`, the scalar, the counting and
+   // the emitting call into `work`, and the gathers: with nv = dim * n_prims vertices (triangles in 3D, segments in 2D, points not
+   // shared), out holds
+   //    [x | v | e | rho | p | detJ | grad v | div v | vorticity | sound speed]
+   // in blocks of dim, dim, 1, 1, 1, 1, dim^2, 1, nv3, 1 times nv values (ContourSize(n_prims) in all), the derived ones where the mask
+   // (DERIVED_*) names them; zone (host) the zone of every primitive.  The vectors are sized anew when they are smaller.  2D and
+   // 3D.  Synchronous; the quadrature data is not touched.
+   enum { CONTOUR_DENSITY, CONTOUR_ENERGY, CONTOUR_PRESSURE, CONTOUR_SPEED, CONTOUR_X, CONTOUR_Y, CONTOUR_Z, CONTOUR_DIV, CONTOUR_DETJ, CONTOUR_CS, CONTOUR_PLANE };
+   static int ContourField(const std::string &name); // the id of density, energy, pressure, speed, x, y, z, div_v, detj, sound_speed; -1 otherwise
+   static const char *ContourFieldList();
+   void Contour(const Vector &S, const Vector &rho, int R, int field, const double coef[3], double value, unsigned mask, Vector &lattice,
+                Vector &work, Vector &out, std::vector<int> &zone, long *n_prims, long *n_skipped) const;
+   long ContourSize(long n_prims) const; // (2 dim + 3 + 3 + dim^2 + nv3) dim n_prims
    // Conserved integrals, extremes of the point values and counts of bad points of the state S, folded over zones and ranks
    // (lgh_diagnostics; the rows of the driver's `-hist` file).  Synchronous, collective on several ranks; reads S and the
    // set-up data only - the quadrature data, the force products and dt_est stay as they are.

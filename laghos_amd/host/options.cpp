@@ -237,14 +237,57 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
          if (!ParsePlane(opt, slice ? "slices" : "planes", ax, argv[++i], slice ? o.pv_slices : o.loads_planes, err)) { return false; }
          continue;
       }
+      if (a == "-pv-iso" || a == "--paraview-iso")
+      {
+         if (i + 2 >= argc) { return Refuse(err, "missing value for " + a + " FIELD VALUE"); }
+         Options::Contour c;
+         c.field = argv[++i];
+         v = argv[++i];
+         if (H::ContourField(c.field) < 0) { return Refuse(err, "-pv-iso: unknown field " + c.field + " (" + H::ContourFieldList() + ")"); }
+         char *end = nullptr;
+         c.value = std::strtod(v, &end);
+         const std::string which = "-pv-iso " + c.field + " " + v;
+         if (end == v || *end || !std::isfinite(c.value)) { return Refuse(err, which + ": the value must be a finite number"); }
+         for (const auto &k : o.pv_isos) { if (k.field == c.field && k.value == c.value) { return Refuse(err, which + " is given twice"); } }
+         if (o.pv_isos.size() == 8) { return Refuse(err, which + ": at most 8 iso-surfaces, this is the ninth"); }
+         c.tag = "iso" + std::to_string(o.pv_isos.size()) + "_" + c.field;
+         o.pv_isos.push_back(c);
+         continue;
+      }
+      if (a == "-pv-plane" || a == "--paraview-plane")
+      {
+         const int n = TakeNumbers(argc, argv, i, 4, false, x);
+         if (n < 3) { return Refuse(err, "-pv-plane NX NY [NZ] D needs three numbers in 2D and four in 3D, got " + std::to_string(n)); }
+         Options::Contour c;
+         c.field = "plane";
+         c.ncoef = n - 1;
+         c.value = x[n - 1];
+         bool finite = std::isfinite(c.value), zero = true;
+         std::string which = "-pv-plane";
+         for (int k = 0; k < n; k++)
+         {
+            if (k < n - 1) { c.coef[k] = x[k]; finite = finite && std::isfinite(x[k]); zero = zero && x[k] == 0.0; }
+            which += std::string(" ") + argv[i - n + 1 + k];
+         }
+         if (!finite) { return Refuse(err, which + ": the normal and D must be finite numbers"); }
+         if (zero) { return Refuse(err, which + ": the normal is zero"); }
+         for (const auto &k : o.pv_planes)
+         {
+            if (k.ncoef == c.ncoef && k.value == c.value && std::equal(c.coef, c.coef + 3, k.coef)) { return Refuse(err, which + " is given twice"); }
+         }
+         if (o.pv_planes.size() == 8) { return Refuse(err, which + ": at most 8 planes, this is the ninth"); }
+         c.tag = "plane" + std::to_string(o.pv_planes.size());
+         o.pv_planes.push_back(c);
+         continue;
+      }
       if (a == "-d" || a == "--device") { if (!need(i)) { return false; } continue; } // always the HIP path
       if (a == "-no-vis" || a == "--no-visualization" || a == "-no-visit" || a == "-no-print") { continue; }
       return Refuse(err, "unsupported option: " + a);
    }
    if (!o.vis_refine_set) { o.vis_refine = o.order_v; }
-   const bool vr_used = o.vis_refine_set || o.paraview || o.FaceDumps();
+   const bool vr_used = o.vis_refine_set || o.paraview || o.LatticeDumps();
    if (vr_used && (o.vis_refine < 1 || o.vis_refine > 8)) { return Refuse(err, "-vr / --vis-refine must be between 1 and 8, got " + std::to_string(o.vis_refine)); }
-   if (o.pv_fields_set && !o.paraview && !o.FaceDumps()) { return Refuse(err, "-pv-fields adds fields to the -paraview dumps: it needs -paraview"); }
+   if (o.pv_fields_set && !o.paraview && !o.LatticeDumps()) { return Refuse(err, "-pv-fields adds fields to the -paraview dumps: it needs -paraview"); }
    const char *map_detail = o.map_cells_n > 0 ? "-map-cells" : (o.map_box_n > 0 ? "-map-box" : nullptr);
    if (map_detail && o.map_steps == 0) { return Refuse(err, std::string(map_detail) + " describes the -map files: it needs -map"); }
    if (!o.loads_planes.empty() && o.loads_steps == 0) { return Refuse(err, "-loads-plane adds rows to the -loads file: it needs -loads"); }
@@ -278,6 +321,21 @@ bool CheckAgainstMesh(Options &o, const CartMesh &mesh, std::string &err)
       if (sl.first >= o.dim) { return Refuse(err, which + ": the mesh has " + dims + " dimensions, there is no " + ax + " axis"); }
       const std::string planes = std::to_string(mesh.ne(sl.first));
       if (sl.second > mesh.ne(sl.first)) { return Refuse(err, which + ": K is out of range, the zone grid has node planes 0.." + planes + " along " + ax); }
+   }
+   if (o.ContourDumps() && o.dim == 1)
+   {
+      return Refuse(err, std::string(o.pv_isos.empty() ? "-pv-plane" : "-pv-iso") + ": contours are formed in 2D and 3D, this mesh is 1D");
+   }
+   for (const auto &c : o.pv_isos)
+   {
+      if (c.field == "z" && o.dim == 2) { return Refuse(err, "-pv-iso z: the mesh has 2 dimensions, there is no z axis"); }
+   }
+   for (const auto &c : o.pv_planes)
+   {
+      if (c.ncoef != o.dim)
+      {
+         return Refuse(err, "-pv-plane (" + c.tag + ") has " + std::to_string(c.ncoef + 1) + " numbers, a mesh of " + dims + " dimensions needs " + std::to_string(o.dim + 1));
+      }
    }
    if (o.loads_steps > 0 && o.dim == 1) { return Refuse(err, "-loads: pressure loads are taken on zone faces in 2D and 3D, this mesh is 1D"); }
    for (const auto &pl : o.loads_planes)

@@ -48,6 +48,22 @@ struct Options
    bool pv_surface = false;
    std::vector<std::pair<int, int>> pv_slices; // (axis, K)
    bool FaceDumps() const { return pv_surface || !pv_slices.empty(); }
+   // -pv-iso FIELD VALUE / -pv-plane NX NY [NZ] D: contours formed on the GPU (lgh_contour) - the iso-surface
+   // FIELD = VALUE of density, energy, pressure, speed, x, y, z, div_v, detj or sound_speed, and the cut plane NX x + NY y (+ NZ z) = D,
+   // which need not follow zone faces; up to 8 of each.  Written when -paraview writes, with or without it, under
+   // <basename>_iso<k>_<field>/ and <basename>_plane<k>/ (k = 0, 1, ...: the position among the options of its kind) with a
+   // collection each; -vr and -pv-fields apply.  2D and 3D.
+   struct Contour
+   {
+      std::string field; // a name of kContourFields, or "plane"
+      double value = 0;  // VALUE, or D
+      int ncoef = 0;     // plane: the numbers in front of D (the mesh's dimension decides whether they fit)
+      double coef[3] = {0, 0, 0};
+      std::string tag;   // "iso0_density", "plane1": the directory is <basename>_<tag>
+   };
+   std::vector<Contour> pv_isos, pv_planes;
+   bool ContourDumps() const { return !pv_isos.empty() || !pv_planes.empty(); }
+   bool LatticeDumps() const { return FaceDumps() || ContourDumps(); } // what -vr and -pv-fields apply to beside -paraview
    int dev = 0;
    // multi-rank (set by the launcher, not the reference CLI)
    int nranks = 1, rank = 0;

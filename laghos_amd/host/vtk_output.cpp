@@ -278,6 +278,69 @@ bool WritePvtuFaces(const std::string &dir, int cycle, double time, int nranks, 
    return !f.fail();
 }
 
+bool WriteVtuContour(const std::string &dir, int dim, long nprims, const int *zone, const double *x, const double *v, const double *e,
+                     const double *rho, const double *p, const std::vector<VtuField> &extra, double iso_value, int cycle, double time, int rank,
+                     int nranks)
+{
+   if (dim < 2 || dim > 3 || nprims < 0) { return false; }
+   if (nprims > 0 && (!zone || !x || !v || !e || !rho || !p)) { return false; }
+   for (const VtuField &f : extra)
+   {
+      if (f.name.empty() || f.components < 1 || (nprims > 0 && !f.data)) { return false; }
+   }
+   const size_t NC = (size_t)nprims, NP = NC * dim;
+   static const double none = 0.0; // (an empty piece: every block has zero bytes, the pointer is never read)
+   const std::vector<double> pts = NC ? Interleave3(x, dim, NP) : std::vector<double>(), vel = NC ? Interleave3(v, dim, NP) : std::vector<double>();
+   std::vector<int64_t> conn(NP), offs(NC);
+   std::vector<uint8_t> types(NC, (uint8_t)(dim == 3 ? 5 : 3)); // VTK_TRIANGLE, VTK_LINE
+   std::vector<int32_t> zn(NC), rnk(NC, (int32_t)rank);
+   for (size_t i = 0; i < NP; i++) { conn[i] = (int64_t)i; }
+   for (size_t q = 0; q < NC; q++)
+   {
+      offs[q] = (int64_t)((q + 1) * dim);
+      zn[q] = zone[q];
+   }
+   const int32_t cyc = cycle;
+   auto ptr = [&](const double *q) { return q ? q : &none; };
+   Appended ap;
+   std::ostringstream h;
+   h << "<?xml version=\"1.0\"?>\n<VTKFile type=\"UnstructuredGrid\" version=\"1.0\" byte_order=\"LittleEndian\" "
+        "header_type=\"UInt64\">\n<UnstructuredGrid>\n<FieldData>\n";
+   h << ap.Array("Float64", "TIME", 0, &time, sizeof(double), " NumberOfTuples=\"1\"");
+   h << ap.Array("Int32", "CYCLE", 0, &cyc, sizeof(int32_t), " NumberOfTuples=\"1\"");
+   h << ap.Array("Float64", "ISO_VALUE", 0, &iso_value, sizeof(double), " NumberOfTuples=\"1\"");
+   h << "</FieldData>\n<Piece NumberOfPoints=\"" << NP << "\" NumberOfCells=\"" << NC << "\">\n<Points>\n";
+   h << ap.Array("Float64", "Points", 3, pts.data(), pts.size() * sizeof(double));
+   h << "</Points>\n<Cells>\n";
+   h << ap.Array("Int64", "connectivity", 0, conn.data(), conn.size() * sizeof(int64_t));
+   h << ap.Array("Int64", "offsets", 0, offs.data(), offs.size() * sizeof(int64_t));
+   h << ap.Array("UInt8", "types", 0, types.data(), types.size());
+   h << "</Cells>\n<PointData Scalars=\"density\" Vectors=\"velocity\">\n";
+   h << ap.Array("Float64", "density", 1, ptr(rho), NP * sizeof(double));
+   h << ap.Array("Float64", "velocity", 3, vel.data(), vel.size() * sizeof(double));
+   h << ap.Array("Float64", "specific_internal_energy", 1, ptr(e), NP * sizeof(double));
+   h << ap.Array("Float64", "pressure", 1, ptr(p), NP * sizeof(double));
+   for (const VtuField &f : extra) { h << ap.Array("Float64", f.name.c_str(), f.components, ptr(f.data), NP * f.components * sizeof(double)); }
+   h << "</PointData>\n<CellData>\n";
+   h << ap.Array("Int32", "zone", 1, zn.data(), zn.size() * sizeof(int32_t));
+   h << ap.Array("Int32", "rank", 1, rnk.data(), rnk.size() * sizeof(int32_t));
+   h << "</CellData>\n</Piece>\n</UnstructuredGrid>\n";
+   MakeDirs(dir);
+   std::ofstream f((dir + "/" + VtuName(cycle, nranks, rank)).c_str(), std::ios::binary);
+   if (!f) { return false; }
+   f << h.str();
+   ap.Write(f);
+   f << "</VTKFile>\n";
+   f.close();
+   return !f.fail();
+}
+
+// (the pieces of a contour dump carry the point and cell arrays of a volume dump: the .pvtu is the same)
+bool WritePvtuContour(const std::string &dir, int cycle, double time, int nranks, const std::vector<VtuField> &extra)
+{
+   return WritePvtuFields(dir, cycle, time, nranks, extra);
+}
+
 bool WritePvd(const std::string &pvd_path, const std::string &rel_dir, const std::vector<double> &times,
               const std::vector<int> &cycles, int nranks)
 {

@@ -81,6 +81,17 @@ bool WriteVtuFaces(const std::string &dir, int dim, int nfaces, const int *faces
                    double time, int rank, int nranks);
 // <dir>/PvtuName() for such pieces
 bool WritePvtuFaces(const std::string &dir, int cycle, double time, int nranks, const std::vector<VtuField> &extra);
+// One piece of a contour dump (`-pv-iso`, `-pv-plane`) <dir>/VtuName(): nprims primitives of dim vertices each -
+// VTK_TRIANGLE in 3D, VTK_LINE in 2D - on NPt = dim * nprims points of their own (vertex j of primitive q is point dim q + j), in
+// the layout of LagrangianHydroOperator::Contour (x[c * NPt + pt], v[c * NPt + pt], e[pt], rho[pt], p[pt]).  PointData: the four
+// standing arrays, then `extra` as WriteVtuFields takes it; CellData zone[q] and rank (Int32); FieldData TIME, CYCLE and ISO_VALUE
+// (the value of the field, or D of a plane).  The raw appended layout of WriteVtuFields.  nprims == 0 writes an empty piece (the
+// arrays may then be null).
+bool WriteVtuContour(const std::string &dir, int dim, long nprims, const int *zone, const double *x, const double *v, const double *e,
+                     const double *rho, const double *p, const std::vector<VtuField> &extra, double iso_value, int cycle, double time, int rank,
+                     int nranks);
+// <dir>/PvtuName() for such pieces
+bool WritePvtuContour(const std::string &dir, int cycle, double time, int nranks, const std::vector<VtuField> &extra);
 // The collection <pvd_path>: one DataSet per dump so far, file = <rel_dir>/<piece or .pvtu>
 bool WritePvd(const std::string &pvd_path, const std::string &rel_dir, const std::vector<double> &times,
               const std::vector<int> &cycles, int nranks);

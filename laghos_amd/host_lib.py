@@ -81,6 +81,15 @@ def load():
         L.laghos_sim_select_faces.argtypes = [P, I, I, I, P]
         L.laghos_sim_face_fields.restype = I
         L.laghos_sim_face_fields.argtypes = [P, I, I, P, P]
+        L.laghos_host_write_vtu_contour.restype = I
+        L.laghos_host_write_vtu_contour.argtypes = [ctypes.c_char_p, I, Lg, P, P, P, P, P, P, I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(I),
+                                                    ctypes.POINTER(P), D, I, D, I, I]
+        L.laghos_host_write_pvtu_contour.restype = I
+        L.laghos_host_write_pvtu_contour.argtypes = [ctypes.c_char_p, I, D, I, I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(I)]
+        L.laghos_sim_contour.restype = Lg
+        L.laghos_sim_contour.argtypes = [P, I, ctypes.c_char_p, P, D, ctypes.c_uint, ctypes.POINTER(Lg)]
+        L.laghos_sim_contour_get.restype = I
+        L.laghos_sim_contour_get.argtypes = [P, P, P]
         L.laghos_sim_derived_fields.restype = I
         L.laghos_sim_derived_fields.argtypes = [P, I, P, P, P, P, P]
         ULL = ctypes.c_ulonglong
@@ -286,6 +295,44 @@ class Sim:
         out["faces"] = faces
         return out
 
+    CONTOUR_EXTRA = {"div_v": 1, "vorticity": 2, "grad_v": 4, "detj": 8, "sound_speed": 16}   # the driver's -pv-fields bits
+
+    def contour(self, R, field, value=None, fields=None):
+        """A contour of the state as it stands, formed on the lattice of R cells per direction as `-pv-iso` / `-pv-plane` form it
+        (LagrangianHydroOperator::Contour): `field` = `value` for density, energy, pressure, speed, x, y, z, div_v, detj or
+        sound_speed, or field = ("plane", normal, d).  This rank's primitives as a dict: points (dim, nv), cells (nprim, dim), zone,
+        v (dim, nv), e, rho, p (nv), the derived arrays named in `fields` (grad_v (dim^2, nv), vorticity (nv) or (3, nv)), and
+        n_skipped; nv = dim * nprim, vertex j of primitive q at dim q + j."""
+        dim = self.sizes()["dim"]
+        coef = None
+        if not isinstance(field, str):
+            field, normal, value = field
+            coef = np.zeros(3)
+            coef[:len(normal)] = normal
+            if len(normal) != dim:
+                raise RuntimeError(f"contour: a plane of a {dim}D mesh has {dim} normal components")
+        fields = tuple(fields or ())
+        mask = sum(self.CONTOUR_EXTRA[k] for k in fields)
+        ns = ctypes.c_long(-1)
+        n = self.L.laghos_sim_contour(self.h, int(R), str(field).encode(), coef.ctypes.data if coef is not None else None, float(value), mask,
+                                      ctypes.byref(ns))
+        if n < 0:
+            raise RuntimeError(f"laghos_sim_contour: {self.L.laghos_sim_error(self.h).decode()}")
+        nv, nvort = dim * n, 3 if dim == 3 else 1
+        blocks = [("points", dim), ("v", dim), ("e", 1), ("rho", 1), ("p", 1), ("detj", 1), ("grad_v", dim * dim), ("div_v", 1), ("vorticity", nvort),
+                  ("sound_speed", 1)]
+        buf, zone = np.full(sum(c for _, c in blocks) * nv, np.nan), np.zeros(n, np.int32)
+        if self.L.laghos_sim_contour_get(self.h, buf.ctypes.data if n else None, zone.ctypes.data if n else None) != 0:
+            raise RuntimeError(f"laghos_sim_contour_get: {self.L.laghos_sim_error(self.h).decode()}")
+        out, pos = {}, 0
+        for k, c in blocks:
+            if k in ("points", "v", "e", "rho", "p") or k in fields:
+                a = buf[pos:pos + c * nv]
+                out[k] = a.reshape(c, nv).copy() if c > 1 else a.copy()
+            pos += c * nv
+        out.update(cells=np.arange(nv, dtype=np.int64).reshape(n, dim), zone=zone, n_skipped=ns.value)
+        return out
+
     def sedov_error(self):
         """`-err`: L2 error of the density against the exact Sedov solution at t_final."""
         return self.L.laghos_sim_sedov_error(self.h)
@@ -474,6 +521,32 @@ def host_write_pvtu_faces(directory, cycle, time, nranks, extra):
     """The .pvtu of such pieces: extra = [(name, components)] (a third entry is ignored)."""
     n, names, comps, _, _ = _extra_args([(e[0], e[1], None) for e in extra])
     if load().laghos_host_write_pvtu_faces(str(directory).encode(), cycle, time, nranks, n, names, comps) != 0:
+        raise RuntimeError(f"cannot write a .pvtu under {directory}")
+    return os.path.join(str(directory), f"cycle_{cycle:06d}.pvtu")
+
+
+def host_write_vtu_contour(directory, dim, zone, x, v, e, rho, p, extra, iso_value, cycle, time, rank=0, nranks=1):
+    """One `-pv-iso` / `-pv-plane` piece from host arrays in the layout of LagrangianHydroOperator::Contour: zone (nprims) ints, x, v
+    dim * nv doubles, the others nv = dim * nprims; extra as host_write_vtu_fields takes it.  No primitives: an empty piece.
+    Returns the path written."""
+    L = load()
+    z = np.ascontiguousarray(np.asarray(zone, dtype=np.int32).reshape(-1))
+    nv = z.size * dim
+    arrs = [_f64(a).reshape(-1) for a in (x, v, e, rho, p)]
+    assert [a.size for a in arrs] == [dim * nv, dim * nv, nv, nv, nv]
+    n, names, comps, data, keep = _extra_args(extra, nv)
+    ptr = lambda a: a.ctypes.data if a.size else None
+    if L.laghos_host_write_vtu_contour(str(directory).encode(), dim, z.size, ptr(z), *[ptr(a) for a in arrs], n, names, comps, data, float(iso_value),
+                                       cycle, time, rank, nranks) != 0:
+        raise RuntimeError(f"cannot write a contour .vtu under {directory}")
+    tag = f"cycle_{cycle:06d}" + (f".{rank}" if nranks > 1 else "")
+    return os.path.join(str(directory), tag + ".vtu")
+
+
+def host_write_pvtu_contour(directory, cycle, time, nranks, extra):
+    """The .pvtu of such pieces: extra = [(name, components)] (a third entry is ignored)."""
+    n, names, comps, _, _ = _extra_args([(e[0], e[1], None) for e in extra])
+    if load().laghos_host_write_pvtu_contour(str(directory).encode(), cycle, time, nranks, n, names, comps) != 0:
         raise RuntimeError(f"cannot write a .pvtu under {directory}")
     return os.path.join(str(directory), f"cycle_{cycle:06d}.pvtu")
 

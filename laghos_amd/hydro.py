@@ -139,6 +139,64 @@ class HydroOperator:
         res["faces"] = faces
         return res
 
+    CONTOUR_FIELDS = ("density", "energy", "pressure", "speed", "x", "y", "z", "div_v", "detj", "sound_speed")
+    CONTOUR_EXTRA = ("detj", "grad_v", "div_v", "vorticity", "sound_speed")
+
+    def contour(self, S, R, field, value=None, fields=None):
+        """The contour `field` = `value` of the state S, formed on the lattice of R cells per zone and direction (Context.contour;
+        what `-pv-iso` / `-pv-plane` write): `field` one of CONTOUR_FIELDS, or ("plane", normal, d) for the cut plane normal . x = d.
+        Triangles in 3D, segments in 2D, points not shared: a dict with points (dim, nv), cells (nprim, dim) - indices into the
+        points -, zone (nprim), v (dim, nv), e, rho, p (nv), the derived arrays named in `fields` (of CONTOUR_EXTRA) interpolated the
+        same way, n_skipped, and the contour itself (edges (nprim, dim, 2), t (nprim, dim): Context.contour).  The density is projected on the mesh of S as the dumps do.  Reads S and the set-up data only."""
+        import numpy as np
+        from . import host_lib
+        p, ctx = self.p, self.ctx
+        dim, R1 = p.dim, R + 1
+        if dim == 1:
+            raise ValueError("contour: 2D and 3D")
+        plane = None
+        if not isinstance(field, str):
+            kind, normal, d = field
+            plane = np.asarray(normal, dtype=np.float64).reshape(-1)
+            if kind != "plane" or plane.size != dim or not np.all(np.isfinite(plane)) or not np.any(plane != 0):
+                raise ValueError(f"contour: {field!r} is no plane of a {dim}D mesh")
+            value = d
+        elif field not in self.CONTOUR_FIELDS or (field == "z" and dim == 2):
+            raise ValueError(f"contour: unknown field {field!r}")
+        if value is None or not np.isfinite(value):
+            raise ValueError(f"contour: the value {value!r} is not a finite number")
+        extra = tuple(fields or ())
+        unknown = [k for k in extra if k not in self.CONTOUR_EXTRA]
+        if unknown:
+            raise ValueError(f"contour: unknown fields {unknown}")
+        NP = p.NE * R1 ** dim
+        Bh, Bl = host_lib.host_lattice_tables(p.order_v, p.order_e, R)
+        lat = dict(x=ctx.empty(dim * NP), v=ctx.empty(dim * NP), e=ctx.empty(NP), rho=ctx.empty(NP), p=ctx.empty(NP))
+        ctx.sample_fields(S, self.compute_density(S), Bh, Bl, **lat)
+        ncomp = dict(x=dim, v=dim, grad_v=dim * dim, vorticity=3 if dim == 3 else 1)
+        need = set(extra) | ({field} if field in self.CONTOUR_EXTRA else set())
+        if need:
+            der = {k: ctx.empty(ncomp.get(k, 1) * NP) for k in self.CONTOUR_EXTRA if k in need}
+            ctx.sample_derived(S, Bh, host_lib.host_lattice_grad_table(p.order_v, R), Bl, **der)
+            lat.update(der)
+        if plane is not None:
+            scalar = ctx.contour_scalar("plane", lat["x"], plane)
+        elif field in ("x", "y", "z"):
+            scalar = ctx.contour_scalar("plane", lat["x"], np.eye(3)["xyz".index(field)][:dim])
+        elif field == "speed":
+            scalar = ctx.contour_scalar("norm", lat["v"])
+        else:
+            scalar = lat[dict(density="rho", energy="e", pressure="p").get(field, field)]
+        edges, t, zone, n_skipped = ctx.contour(scalar, value, R1)
+        out = {k: ctx.contour_gather(edges, t, lat[k], ncomp.get(k, 1)) for k in ("x", "v", "e", "rho", "p") + extra}
+        ctx.sync()
+        nprim = zone.numel()
+        res = {k: (a.cpu().numpy() if ncomp.get(k, 1) > 1 else a.cpu().numpy().reshape(-1)) for k, a in out.items()}
+        res["points"] = res.pop("x")
+        res.update(cells=np.arange(dim * nprim, dtype=np.int64).reshape(nprim, dim), zone=zone.cpu().numpy(), n_skipped=n_skipped,
+                   edges=edges.cpu().numpy(), t=t.cpu().numpy())
+        return res
+
     def loads(self, S, groups):
         """Pressure loads of the state S on groups of zone faces (Context.loads; what `-loads` writes): `groups` a list of
         (name, faces), faces (n, 2) ints (zone, local face 2 axis + side); a face may stand in several groups.  A dict with `names`,
