@@ -560,6 +560,33 @@ int lgh_contour_scalar(lgh_ctx *ctx, int mode, long NP, int dim, const double *i
  * are the edges of a launch.  LGH_ERR_ARG where lgh_contour refuses dim or R1. */
 int lgh_contour_zpb(lgh_ctx *ctx, int R1, int *zpb);
 
+/* ---- running records at material points (the driver's `-peaks`): a lattice point of lgh_sample_fields / lgh_sample_faces is
+ * the same particle in every cycle, so what happened THERE over time is kept per lattice point.  p, rho, e (n each) and
+ * v[c * n + i], c < dim, are the device arrays those calls wrote at time t; rec[c * n + i], c < LGH_RECORDS_COLS, is the record
+ * block (device), columns
+ *   0 p_max   1 t_p_max   2 impulse   3 p_last   4 rho_max   5 speed_max   6 e_max   7 t_arrival
+ * first != 0 starts the records (dtr must be 0; rec is written, not read): p_max = p_last = p, t_p_max = t, impulse = 0,
+ * rho_max = rho, speed_max = |v|, e_max = e, t_arrival = (p >= threshold) ? t : -1.  Otherwise, dtr the time since the last
+ * update: p > p_max (strictly: the first attainment keeps its time) sets p_max = p, t_p_max = t; impulse = impulse + (0.5 dtr)
+ * (p_last + p), the trapezoid rule with 0.5 dtr formed once on the host; p_last = p; rho_max, speed_max, e_max move by >;
+ * t_arrival < 0 && p >= threshold sets t_arrival = t.  threshold NaN: no threshold, t_arrival stays -1.
+ * |v| = sqrt(v_0^2 + v_1^2 (+ v_2^2)), summed in ascending order.  A NaN sample moves no extreme (comparisons with it are
+ * false) and makes the impulse NaN; nothing is trapped.  Every column but speed_max has the bits of these formulas evaluated
+ * operation by operation in IEEE double (no contraction into an fma); speed_max may be contracted.
+ * LGH_ERR_ARG with the value in the message, nothing launched: n < 0, a NULL array with n > 0, dim outside 1..3, t not finite,
+ * dtr negative or not finite, first with dtr != 0, threshold infinite.  n == 0: LGH_OK, no launch.  The arrays may start at
+ * any 8-byte aligned address (with n odd every second column does: such a column is read and written 8 bytes at a time).
+ * Asynchronous on the context's stream; reads its inputs, reads and writes rec only: the quadrature data, its generation
+ * counter and the fused force products are untouched.  dim is the caller's (the context's mesh is not looked at). */
+#define LGH_RECORDS_COLS 8
+int lgh_records_update(lgh_ctx *ctx, long n, int dim, const double *p, const double *rho, const double *e,
+                       const double *v /* v[c*n + i], c < dim */, double t, double dtr, double threshold /* NaN: none */,
+                       int first, double *rec /* rec[c*n + i], c < LGH_RECORDS_COLS */);
+/* The launch lgh_records_update makes for n points: out[0] = workgroups (0: no launch), out[1] = threads of a workgroup,
+ * out[2] = points a lane takes per trip, out[3] = trips of a lane's loop.  The grid is capped: for n large enough out[0] is
+ * the cap and out[0] * out[1] * out[2] the points of one trip. */
+int lgh_records_shape(lgh_ctx *ctx, long n, long out[4]);
+
 /* ---- timing data (TimingData, laghos_solver.hpp:39-56): seconds measured with
  * HIP events around the same regions as the reference stopwatches.
  * t[0..3] = cgH1, cgL2, force, qdata; c[0..2] = H1iter, L2iter, quad_tstep */
@@ -588,6 +615,7 @@ int lgh_enable_timers(lgh_ctx *ctx, int on);
 #define LGH_KERNEL_FACES 14       /* lgh_sample_faces */
 #define LGH_KERNEL_LOADS 15       /* lgh_loads: both passes over the faces and the kernels between and behind them */
 #define LGH_KERNEL_CONTOUR 16     /* lgh_contour: the count pass, the scan, the look at the totals and the emit pass of one call */
+#define LGH_KERNEL_RECORDS 17     /* lgh_records_update */
 int lgh_ktime_begin(lgh_ctx *ctx, int which, int max_samples);
 int lgh_ktime_end(lgh_ctx *ctx, int *launches, double *mean_seconds);
 /* Whether lgh_create found the 1-D H1 / L2 tables mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (any nodal or

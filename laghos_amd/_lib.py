@@ -110,6 +110,8 @@ SYMBOLS = {
     "lgh_contour_gather": (_I, [_P, _L, _P, _P, _I, _L, _P, _P]),
     "lgh_contour_scalar": (_I, [_P, _I, _L, _I, _P, c_dbl_p, _P]),
     "lgh_contour_zpb": (_I, [_P, _I, ctypes.POINTER(_I)]),
+    "lgh_records_update": (_I, [_P, _L, _I, _P, _P, _P, _P, _D, _D, _D, _I, _P]),
+    "lgh_records_shape": (_I, [_P, _L, ctypes.POINTER(ctypes.c_long)]),
     "lgh_get_timers": (_I, [_P, c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
     "lgh_reset_timers": (_I, [_P]),
     "lgh_enable_timers": (_I, [_P, _I]),

@@ -728,6 +728,23 @@ class Context:
         check(self.lib.lgh_vec_fingerprint_shape(self.h, _ptr(t), t.numel(), out))
         return tuple(out)
 
+    RECORD_COLS = ("p_max", "t_p_max", "impulse", "p_last", "rho_max", "speed_max", "e_max", "t_arrival")   # LGH_RECORDS_COLS = 8
+
+    def records_update(self, dim, p, rho, e, v, t, dtr, rec, threshold=None, first=False):
+        """lgh_records_update: folds the sample p, rho, e (n each) and v (dim * n, component-major) taken at time t, dtr after the
+        last update, into the record block rec (8 * n, column-major, RECORD_COLS); threshold None: none; first: start the records
+        (dtr must be 0).  All device tensors, each may start at any 8-byte aligned address.  Asynchronous."""
+        n = p.numel()
+        assert rho.numel() == n and e.numel() == n and v.numel() == dim * n and rec.numel() == len(self.RECORD_COLS) * n
+        check(self.lib.lgh_records_update(self.h, n, int(dim), _ptr(p), _ptr(rho), _ptr(e), _ptr(v), float(t), float(dtr),
+                                          float("nan") if threshold is None else float(threshold), int(bool(first)), _ptr(rec)))
+
+    def records_shape(self, n):
+        """(workgroups, threads, points per lane per trip, trips) of the launch records_update makes for n points"""
+        out = (ctypes.c_long * 4)()
+        check(self.lib.lgh_records_shape(self.h, int(n), out))
+        return tuple(out)
+
     def internal_energy(self, e):
         v = ctypes.c_double()
         check(self.lib.lgh_internal_energy(self.h, _ptr(e), ctypes.byref(v)))

@@ -11,6 +11,7 @@
 
 #include "map_output.hpp"
 #include "profile.hpp"
+#include "records_sidecar.hpp"
 #include "sedov_exact.hpp"
 #include "vtk_output.hpp"
 
@@ -143,6 +144,100 @@ static std::vector<VtuField> DerivedVtuFields(unsigned mask, int dim, long NP, c
    return extra;
 }
 
+// -peaks: the records of point set `face_set` (-1: the volume) as the PointData arrays of its dump, behind the -pv-fields arrays:
+// one copy of the block to `host`, which the returned fields point into.  p_last is not written; arrival_time only with
+// -peaks-arrival.  (The caller has synchronised the stream since the last update.)
+static void AppendRecordFields(const laghos_sim *s, int face_set, std::vector<double> &host, std::vector<VtuField> &extra)
+{
+   static const struct { const char *name; int col; } kFields[] = {{"peak_pressure", 0}, {"peak_pressure_time", 1}, {"pressure_impulse", 2}, {"peak_density", 4},
+                                                                   {"peak_speed", 5}, {"peak_energy", 6}, {"arrival_time", 7}};
+   for (const laghos_sim::RecordSet &rs : s->records)
+   {
+      if (rs.face_set != face_set) { continue; }
+      rs.dev.ToHost(host);
+      for (const auto &f : kFields)
+      {
+         if (f.col == 7 && !s->opt.peaks_arrival_set) { continue; }
+         extra.push_back({f.name, 1, host.data() + (size_t)f.col * rs.n});
+      }
+   }
+}
+
+void UpdateRecords(laghos_sim *s, const Vector &rho, bool first)
+{
+   const Options &o = s->opt;
+   const double threshold = o.peaks_arrival_set ? o.peaks_arrival : NAN;
+   const double dtr = first ? 0.0 : s->t - s->rec_time; // (the time since the last update, whatever the cadence was)
+   for (laghos_sim::RecordSet &rs : s->records)
+   {
+      s->hydro->UpdateRecords(s->S, rho, o.vis_refine, rs.face_set < 0 ? nullptr : &s->pv_faces[rs.face_set].faces, s->t, dtr, threshold, first, s->rec_scratch,
+                              rs.dev);
+   }
+   s->rec_time = s->t;
+   s->rec_updates++;
+}
+
+// What a sidecar of this run's records must say about the point sets
+static void RecordSetLists(const laghos_sim *s, std::vector<std::string> &tags, std::vector<long> &points)
+{
+   for (const laghos_sim::RecordSet &rs : s->records)
+   {
+      tags.push_back(rs.tag);
+      points.push_back(rs.n);
+   }
+}
+
+std::string RecordsFromSidecar(laghos_sim *s, const std::string &piece, const CheckpointHeader &h)
+{
+   const Options &o = s->opt;
+   const std::string path = RecordsSidecarPath(piece);
+   if (o.peaks_steps <= 0)
+   {
+      std::FILE *f = (o.rank == 0) ? std::fopen(path.c_str(), "rb") : nullptr;
+      if (f)
+      {
+         std::fclose(f);
+         std::cout << "Restart: " << path << " holds -peaks records; this run has no -peaks and ignores them" << std::endl;
+      }
+      return "";
+   }
+   RecordsSidecar sc;
+   std::string err;
+   std::vector<std::string> tags;
+   std::vector<long> points;
+   RecordSetLists(s, tags, points);
+   int rc = ReadRecordsSidecar(path, sc, err);
+   if (rc == REC_OK) { rc = MatchRecordsSidecar(path, sc, h.state_fp, o.vis_refine, o.peaks_arrival_set ? 1 : 0, o.peaks_arrival, tags, points, err); }
+   if (rc == REC_OK && sc.ti != h.ti) { rc = REC_ERR_STATE_FP; err = "records sidecar " + path + ": state_fp: it belongs to cycle " + std::to_string(sc.ti) + ", the checkpoint to cycle " + std::to_string(h.ti); }
+   const bool all_ok = o.nranks == 1 || s->hydro->AllReduce(rc == REC_OK ? 1.0 : 0.0, 1) == 1.0;
+   if (rc != REC_OK) { return "laghos: -restart with -peaks: " + err + ": restart refused"; }
+   if (!all_ok) { return "laghos: -restart with -peaks: another rank refused its records sidecar"; }
+   for (size_t k = 0; k < s->records.size(); k++)
+   {
+      if (s->records[k].n > 0) { s->records[k].dev.FromHost(sc.blocks[k]); }
+   }
+   s->rec_time = sc.time;
+   return "";
+}
+
+// The sidecar of checkpoint piece `piece` (state fingerprint state_fp, cycle ti_now): the blocks to the host, then the file
+static bool WriteRecordsBeside(laghos_sim *s, const std::string &piece, int ti_now, const unsigned long long state_fp[2], std::string &err)
+{
+   const Options &o = s->opt;
+   RecordsSidecar sc;
+   sc.state_fp[0] = state_fp[0]; sc.state_fp[1] = state_fp[1];
+   sc.ti = ti_now; sc.time = s->rec_time; sc.R = o.vis_refine;
+   sc.threshold_set = o.peaks_arrival_set ? 1 : 0; sc.threshold = o.peaks_arrival;
+   RecordSetLists(s, sc.tags, sc.points);
+   s->hydro->Sync();
+   for (const laghos_sim::RecordSet &rs : s->records)
+   {
+      sc.blocks.emplace_back();
+      if (rs.n > 0) { rs.dev.ToHost(sc.blocks.back()); }
+   }
+   return WriteRecordsSidecar(RecordsSidecarPath(piece), sc, err) == REC_OK;
+}
+
 std::string FaceSetDir(const std::string &basename, const std::string &tag) { return basename + "_" + tag; }
 
 // What rank 0 adds to the pieces of a dump under <basename>_<tag>: the .pvtu of a multi-rank cycle, and the collection `pvd`
@@ -195,6 +290,7 @@ static bool DumpParaview(laghos_sim *s, int cycle, const Vector *rho)
    std::vector<VtuField> extra;
    std::vector<double> vort_buf, grad_buf;
    if (o.pv_fields) { extra = DerivedVtuFields(o.pv_fields, dim, NP, DerivedBlocks<const double>(h + base, dim, NP), vort_buf, grad_buf); }
+   AppendRecordFields(s, -1, s->rec_host, extra);
    const bool ok = WriteVtuFields(dir, dim, s->disc->NE, R + 1, h, h + dim * NP, h + 2 * dim * NP, h + (2 * dim + 1) * NP,
                                   h + (2 * dim + 2) * NP, extra, cycle, s->t, o.rank, o.nranks) &&
                    WriteCollection(s, "paraview", o.basename + ".pvd", VOLUME_PIECES, extra, cycle);
@@ -256,8 +352,9 @@ static bool DumpFaces(laghos_sim *s, int cycle, const Vector &rho)
 {
    const Options &o = s->opt;
    const int dim = s->disc->dim, R = o.vis_refine;
-   for (laghos_sim::FaceSet &fs : s->pv_faces)
+   for (size_t k = 0; k < s->pv_faces.size(); k++)
    {
+      laghos_sim::FaceSet &fs = s->pv_faces[k];
       const int nfaces = (int)fs.faces.size() / 2;
       const long NPt = s->hydro->FacePoints(R, nfaces);
       Laps laps(s->pvf_seconds);
@@ -265,7 +362,8 @@ static bool DumpFaces(laghos_sim *s, int cycle, const Vector &rho)
       const double *x = s->pv_host.data(), *v = x + dim * NPt, *e = v + dim * NPt, *r = e + NPt, *p = r + NPt;
       const DerivedBlocks<const double> b(p + NPt, dim, NPt); // (the area vectors follow them)
       std::vector<double> vort_buf, grad_buf;
-      const std::vector<VtuField> extra = DerivedVtuFields(o.pv_fields, dim, NPt, b, vort_buf, grad_buf);
+      std::vector<VtuField> extra = DerivedVtuFields(o.pv_fields, dim, NPt, b, vort_buf, grad_buf);
+      AppendRecordFields(s, (int)k, s->rec_host, extra);
       const std::string dir = FaceSetDir(o.basename, fs.tag);
       const bool ok = WriteVtuFaces(dir, dim, nfaces, fs.faces.data(), R + 1, x, v, e, r, p, extra, b.end, cycle, s->t, o.rank, o.nranks) &&
                       WriteCollection(s, fs.tag, dir + ".pvd", FACE_PIECES, extra, cycle);
@@ -404,6 +502,8 @@ bool WriteCheckpointPiece(laghos_sim *s, const std::string &stem, int ti_now, st
          h.setup_fp[0] = s->setup_fp[0]; h.setup_fp[1] = s->setup_fp[1];
          std::vector<long long> cyc(s->pv_cycles.begin(), s->pv_cycles.end());
          written = WriteCheckpoint(piece, h, s->ckpt_host.data(), (long)s->ckpt_host.size(), s->pv_times.data(), cyc.data(), (long)cyc.size(), err) == CKPT_OK;
+         // -peaks: the records beside the piece, before anything (`latest`) names the checkpoint
+         if (written && o.peaks_steps > 0) { written = WriteRecordsBeside(s, piece, ti_now, own, err); }
       }
       laps.Lap();
       return written;
@@ -429,6 +529,7 @@ static bool PeriodicCheckpoint(laghos_sim *s, int ti_now)
    while (o.ckpt_keep > 0 && (int)s->ckpt_mine.size() > o.ckpt_keep)
    {
       (void)std::remove(s->ckpt_mine.front().c_str());
+      if (o.peaks_steps > 0) { (void)std::remove(RecordsSidecarPath(s->ckpt_mine.front()).c_str()); }
       s->ckpt_mine.erase(s->ckpt_mine.begin());
    }
    return true;
@@ -631,6 +732,22 @@ void SetUpOutputs(laghos_sim *s, const std::vector<double> &S0)
       }
    }
    for (const auto &sl : o.pv_slices) { face_set(std::string("slice_") + (char)('x' + sl.first) + std::to_string(sl.second), sl.first, sl.second); }
+   if (o.peaks_steps > 0) // one record block per material point set, and scratch for the largest (sized once: no allocation between updates)
+   {
+      long most = 0;
+      auto record_set = [&](const std::string &tag, int k) {
+         s->records.emplace_back();
+         laghos_sim::RecordSet &rs = s->records.back();
+         rs.tag = tag;
+         rs.face_set = k;
+         rs.n = s->hydro->RecordPoints(o.vis_refine, k < 0 ? nullptr : &s->pv_faces[k].faces);
+         rs.dev.SetSize(LGH_RECORDS_COLS * rs.n);
+         most = std::max(most, rs.n);
+      };
+      if (o.paraview) { record_set("volume", -1); }
+      for (size_t k = 0; k < s->pv_faces.size(); k++) { record_set(s->pv_faces[k].tag, (int)k); }
+      s->rec_scratch.SetSize((s->disc->dim + 3) * most);
+   }
 }
 
 bool OpenPeriodicOutputs(laghos_sim *s, int resume_cycle)

@@ -1,5 +1,6 @@
 // driver_outputs.hpp — the simulation object of the driver and everything it writes: the -paraview / -pv-surface / -pv-slice /
-// -pv-iso / -pv-plane dumps, -print, checkpoints, and the -hist / -prof / -map / -loads recorders with the one cadence they and -ckpt share.
+// -pv-iso / -pv-plane dumps, -print, checkpoints, the -hist / -prof / -map / -loads recorders with the one cadence they and -ckpt share,
+// and the -peaks records that live across steps (in the material dumps, and beside every checkpoint piece).
 #pragma once
 
 #include <chrono>
@@ -122,6 +123,21 @@ struct laghos_sim
    std::vector<int> loads_faces;
    std::vector<double> loads_rows;
    laghos::Vector loads_rho;
+   // -peaks: one block of running records per material point set (the volume lattice of -paraview first, then the face sets in
+   // their order), on the device; the time of the last update; scratch (the sampled fields; a block on the host); the updates of
+   // this run
+   struct RecordSet
+   {
+      std::string tag;   // "volume", or the tag of the face set
+      int face_set = -1; // index into pv_faces, -1: the volume
+      long n = 0;        // points
+      laghos::Vector dev; // LGH_RECORDS_COLS x n, column-major
+   };
+   std::vector<RecordSet> records;
+   double rec_time = 0.0;
+   int rec_updates = 0;
+   laghos::Vector rec_scratch;
+   std::vector<double> rec_host;
    int steps_at_start = 0;             // RK steps the checkpoint of a restart had taken: timing / FOM cover the restarted segment
 };
 
@@ -155,6 +171,14 @@ void SampleContour(laghos_sim *s, const laghos_sim::ContourSet &cs, const Vector
                    std::vector<int> &zone, long *n_prims, long *n_skipped, Laps &laps);
 // One face set of the state as it stands into host arrays: the blocks of LagrangianHydroOperator::SampleFaces (two laps)
 void SampleFaceSet(laghos_sim *s, laghos_sim::FaceSet &fs, const Vector &rho, int R, unsigned mask, std::vector<double> &host, Laps &laps);
+
+// -peaks: one update of every record block with the state as it stands (first: the update that starts them, at cycle 0); rho the
+// density of this state.  Asynchronous.
+void UpdateRecords(laghos_sim *s, const Vector &rho, bool first);
+// -peaks on a restart from checkpoint piece `piece` (header h): reads <piece>.rec, holds it against the checkpoint and this run
+// (collective on several ranks) and only then takes the blocks and the time of the last update.  Returns the line for stderr when it
+// refuses, "" otherwise.  Without -peaks: one line by rank 0 when a sidecar lies there, nothing else.
+std::string RecordsFromSidecar(laghos_sim *s, const std::string &piece, const CheckpointHeader &h);
 
 // The fingerprint of this rank's state (own) and of the whole run (all).  Collective on several ranks.
 bool StateFingerprint(laghos_sim *s, unsigned long long own[2], unsigned long long all[2]);

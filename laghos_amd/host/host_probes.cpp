@@ -13,6 +13,7 @@
 #include "history.hpp"
 #include "loads_output.hpp"
 #include "map_output.hpp"
+#include "records_sidecar.hpp"
 #include "vtk_output.hpp"
 
 using namespace laghos;
@@ -185,6 +186,85 @@ int laghos_host_read_checkpoint(const char *path, long *ints, double *dbls, unsi
    std::copy(c.pv_times.begin(), c.pv_times.end(), pv_times);
    std::copy(c.pv_cycles.begin(), c.pv_cycles.end(), pv_cycles);
    return CKPT_OK;
+}
+// host-only: the `-peaks` sidecar of a checkpoint piece (records_sidecar.hpp); 0 = done, else a RecordsSidecarError with its message
+// in msg.  tags: the nsets tags, blank-separated; points[nsets]; blocks: the record blocks one after the other (LGH_RECORDS_COLS x
+// points[k] doubles each).
+static std::vector<std::string> SplitBlanks(const char *s)
+{
+   std::vector<std::string> out;
+   const std::string all = s ? s : "";
+   for (size_t pos = 0; pos < all.size();)
+   {
+      const size_t sp = std::min(all.find(' ', pos), all.size());
+      if (sp > pos) { out.push_back(all.substr(pos, sp - pos)); }
+      pos = sp + 1;
+   }
+   return out;
+}
+int laghos_host_write_records_sidecar(const char *path, const unsigned long long *state_fp, long ti, double time, int R, int threshold_set, double threshold,
+                                      int nsets, const char *tags, const long *points, const double *blocks, char *msg, int msg_len)
+{
+   RecordsSidecar r;
+   r.state_fp[0] = state_fp[0]; r.state_fp[1] = state_fp[1];
+   r.ti = ti; r.time = time; r.R = R; r.threshold_set = threshold_set; r.threshold = threshold;
+   r.tags = SplitBlanks(tags);
+   std::string err;
+   int rc = REC_OK;
+   if ((int)r.tags.size() != nsets) { rc = REC_ERR_IO; err = std::string("records sidecar ") + path + ": write: " + std::to_string(r.tags.size()) + " tags for " + std::to_string(nsets) + " point sets"; }
+   for (int k = 0; k < nsets && rc == REC_OK; k++)
+   {
+      const long words = kRecordCols * std::max(points[k], 0L);
+      r.points.push_back(points[k]);
+      r.blocks.emplace_back(blocks, blocks + words);
+      blocks += words;
+   }
+   if (rc == REC_OK) { rc = WriteRecordsSidecar(path, r, err); }
+   CkptMsg(err, msg, msg_len);
+   return rc;
+}
+// ints[4]: ti R threshold_set nsets; dbls[2]: time threshold; tags (tags_len chars) blank-separated; the arrays are written only when
+// every check has passed and they fit
+int laghos_host_read_records_sidecar(const char *path, unsigned long long *state_fp, long *ints, double *dbls, char *tags, int tags_len, long *points,
+                                     int cap_sets, double *blocks, long cap_words, char *msg, int msg_len)
+{
+   RecordsSidecar r;
+   std::string err, all;
+   int rc = ReadRecordsSidecar(path, r, err);
+   long words = 0;
+   for (size_t k = 0; k < r.tags.size(); k++)
+   {
+      all += (k ? " " : "") + r.tags[k];
+      words += (long)r.blocks[k].size();
+   }
+   if (rc == REC_OK && ((int)r.tags.size() > cap_sets || words > cap_words || (int)all.size() + 1 > tags_len))
+   {
+      rc = REC_ERR_CAPACITY;
+      err = std::string("records sidecar ") + path + ": capacity: " + std::to_string(r.tags.size()) + " point sets and " + std::to_string(words) + " words do not fit the caller's arrays";
+   }
+   CkptMsg(err, msg, msg_len);
+   if (rc != REC_OK) { return rc; }
+   state_fp[0] = r.state_fp[0]; state_fp[1] = r.state_fp[1];
+   ints[0] = r.ti; ints[1] = r.R; ints[2] = r.threshold_set; ints[3] = (long)r.tags.size();
+   dbls[0] = r.time; dbls[1] = r.threshold;
+   std::memcpy(tags, all.c_str(), all.size() + 1);
+   for (size_t k = 0; k < r.tags.size(); k++)
+   {
+      points[k] = r.points[k];
+      blocks = std::copy(r.blocks[k].begin(), r.blocks[k].end(), blocks);
+   }
+   return REC_OK;
+}
+// reads <path> and holds it against what a restarting run expects, as the driver does
+int laghos_host_match_records_sidecar(const char *path, const unsigned long long *state_fp, int R, int threshold_set, double threshold, int nsets,
+                                      const char *tags, const long *points, char *msg, int msg_len)
+{
+   RecordsSidecar r;
+   std::string err;
+   int rc = ReadRecordsSidecar(path, r, err);
+   if (rc == REC_OK) { rc = MatchRecordsSidecar(path, r, state_fp, R, threshold_set, threshold, SplitBlanks(tags), std::vector<long>(points, points + nsets), err); }
+   CkptMsg(err, msg, msg_len);
+   return rc;
 }
 // host-only: the `-hist` file logic (history.hpp).  The header line; one formatted row (returns its length, -1 when buf is too
 // small); and a whole file operation: keep_upto < 0 starts <path> anew, else the existing file is resumed as a restart from cycle

@@ -270,7 +270,11 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
       if (refusal.empty())
       {
          SetUpOutputs(s.get(), init.S0);
-         if (restarting) { refusal = StateFromCheckpoint(*s, ck, ck_piece); }
+         if (restarting)
+         {
+            refusal = StateFromCheckpoint(*s, ck, ck_piece);
+            if (refusal.empty()) { refusal = RecordsFromSidecar(s.get(), ck_piece, ck.h); }
+         }
          else { StateFromInitial(*s, init); }
       }
    }
@@ -281,8 +285,16 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
    }
    // The first outputs say themselves what they could not write, as they do during the run.  A restart resumes from a cycle
    // whose outputs the run that wrote the checkpoint has; a fresh start writes those of cycle 0 (laghos.cpp:691-701).
+   // -peaks: the records start at cycle 0, before its dump shows them (one density projection for both).
+   const Vector *rho0 = nullptr;
+   if (!restarting && o.peaks_steps > 0)
+   {
+      s->hydro->ComputeDensity(s->S, s->pv_rho);
+      UpdateRecords(s.get(), s->pv_rho, true);
+      rho0 = &s->pv_rho;
+   }
    const bool started = restarting ? OpenPeriodicOutputs(s.get(), ck.h.ti)
-                                   : DumpVis(s.get(), 0) && OpenPeriodicOutputs(s.get(), -1) && WritePeriodicOutputs(s.get(), Periodic::START, 0);
+                                   : DumpVis(s.get(), 0, rho0) && OpenPeriodicOutputs(s.get(), -1) && WritePeriodicOutputs(s.get(), Periodic::START, 0);
    return started ? s.release() : nullptr;
 }
 
@@ -360,7 +372,22 @@ int laghos_sim_step(laghos_sim *s)
                return -1;
             }
          }
-         if (!DumpVis(s, s->ti, o.gfprint ? &rho : nullptr)) { return -1; } // laghos.cpp:845-871 (one projection for all)
+         const Vector *rho_now = o.gfprint ? &rho : nullptr;
+         if (o.peaks_steps > 0) // a step that dumps (the last one does) updates the records first: a dump never shows stale ones
+         {
+            if (!rho_now)
+            {
+               hydro.ComputeDensity(s->S, s->pv_rho);
+               rho_now = &s->pv_rho;
+            }
+            UpdateRecords(s, *rho_now, false);
+         }
+         if (!DumpVis(s, s->ti, rho_now)) { return -1; } // laghos.cpp:845-871 (one projection for all)
+      }
+      else if (o.peaks_steps > 0 && (s->ti % o.peaks_steps) == 0) // -peaks N between the dumps
+      {
+         hydro.ComputeDensity(s->S, s->pv_rho);
+         UpdateRecords(s, s->pv_rho, false);
       }
       if (o.check)
       {
@@ -585,6 +612,28 @@ int laghos_sim_contour_get(laghos_sim *s, double *out, int *zone)
    }
    return 0;
 }
+// The `-peaks` records as they stand of the point set `tag` ("volume", "surface", "slice_x2": the tag of its dump): returns its
+// number of points n, -1 with laghos_sim_error() set when the run keeps no such set.  out (may be NULL: count only) takes the block,
+// LGH_RECORDS_COLS x n doubles, column-major; *time (may be NULL) the time of the last update.
+long laghos_sim_records(laghos_sim *s, const char *tag, double *out, double *time)
+{
+   const std::string want = tag ? tag : "";
+   for (const laghos_sim::RecordSet &rs : s->records)
+   {
+      if (rs.tag != want) { continue; }
+      if (time) { *time = s->rec_time; }
+      if (out && rs.n > 0)
+      {
+         std::vector<double> h;
+         s->hydro->Sync();
+         rs.dev.ToHost(h);
+         std::memcpy(out, h.data(), (size_t)(LGH_RECORDS_COLS * rs.n) * sizeof(double));
+      }
+      return rs.n;
+   }
+   s->error = "laghos_sim_records: this run keeps no records at " + want + (s->opt.peaks_steps > 0 ? " (no such dump is on)" : " (no -peaks)");
+   return -1;
+}
 double laghos_sim_energy(laghos_sim *s) { return s->hydro->InternalEnergy(s->S) + s->hydro->KineticEnergy(s->S); }
 void laghos_sim_sync(laghos_sim *s) { s->hydro->Sync(); }
 void laghos_sim_enable_timers(laghos_sim *s, int on) { s->hydro->EnableTimers(on != 0); }
@@ -658,6 +707,10 @@ int laghos_main(int argc, const char *const *argv)
                 << s->pvc_seconds[0] << " s, copy " << s->pvc_seconds[1] << " s, write " << s->pvc_seconds[2] << " s) ->";
       for (const auto &cs : s->pv_contours) { std::cout << " " << FaceSetDir(o.basename, cs.spec.tag) << ".pvd"; }
       std::cout << std::endl;
+   }
+   if (o.peaks_steps > 0 && !o.quiet)
+   {
+      std::cout << "Peaks: " << s->rec_updates << " updates of " << s->records.size() << " point sets, the last at t = " << s->rec_time << std::endl;
    }
    if (o.ckpt_steps > 0 && !o.quiet)
    {

@@ -303,6 +303,24 @@ void LagrangianHydroOperator::SampleFaces(const Vector &S, const Vector &rho, in
                                (mask & DERIVED_VORT) ? b.vort : nullptr, (mask & DERIVED_CS) ? b.cs : nullptr, b.end));
 }
 
+void LagrangianHydroOperator::UpdateRecords(const Vector &S, const Vector &rho, int R, const std::vector<int> *faces, double t, double dtr, double threshold,
+                                            bool first, Vector &scratch, Vector &rec) const
+{
+   const long n = RecordPoints(R, faces);
+   if (n == 0) { return; }
+   if (scratch.Size() < (dim + 3) * n) { scratch.SetSize((dim + 3) * n); }
+   std::vector<double> Bh, Bl;
+   LatticeTables(disc.tab.order_v, disc.tab.order_e, R, Bh, Bl);
+   double *v = scratch.Write(), *e = v + dim * n, *r = e + n, *p = r + n;
+   if (faces)
+   {
+      LGH_VERIFY(lgh_sample_faces(ctx, S.Read(), rho.Read(), R + 1, Bh.data(), nullptr, Bl.data(), (int)(faces->size() / 2), faces->data(), nullptr, v, e, r, p,
+                                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+   }
+   else { LGH_VERIFY(lgh_sample_fields(ctx, S.Read(), rho.Read(), R + 1, Bh.data(), Bl.data(), nullptr, v, e, r, p)); }
+   LGH_VERIFY(lgh_records_update(ctx, n, dim, p, r, e, v, t, dtr, threshold, first ? 1 : 0, rec.ReadWrite()));
+}
+
 static const char *const kContourFields[] = {"density", "energy", "pressure", "speed", "x", "y", "z", "div_v", "detj", "sound_speed"};
 
 int LagrangianHydroOperator::ContourField(const std::string &name)

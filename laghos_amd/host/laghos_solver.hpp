@@ -121,6 +121,14 @@ public:
    void SampleFaces(const Vector &S, const Vector &rho, int R, const std::vector<int> &faces, unsigned mask, Vector &out) const;
    long FacePoints(int R, long nfaces) const;
    long FacesSize(int R, long nfaces) const; // (2 dim + 3 + 3 + dim^2 + nv + dim) NPt
+   // One update of a block of running records (lgh_records_update; the driver's `-peaks`) at the n = RecordPoints(R,
+   // faces) lattice points of the volume (faces == nullptr) or of a face list: p, rho, e and v of S are sampled into `scratch`
+   // ([v | e | rho | p], sized anew when smaller than (dim + 3) n) by the sampling calls above - the same bits a dump of this state
+   // holds - and folded into rec (LGH_RECORDS_COLS x n, column-major; the caller sizes it) at time t, dtr since the last update;
+   // threshold NaN: none; first: start the records (dtr 0).  Asynchronous on the context's stream; the quadrature data is not touched.
+   void UpdateRecords(const Vector &S, const Vector &rho, int R, const std::vector<int> *faces, double t, double dtr, double threshold, bool first,
+                      Vector &scratch, Vector &rec) const;
+   long RecordPoints(int R, const std::vector<int> *faces) const { return faces ? FacePoints(R, (long)faces->size() / 2) : SamplePoints(R); }
    // A contour of the state S, formed on the lattice of R + 1 points per direction (lgh_contour; the driver's `-pv-iso` / `-pv-plane`):
    // the iso-surface field = value of one of the fields below, or - field CONTOUR_PLANE - the cut plane coef . x = value.  Runs, in
    // this order, SampleFields (and SampleDerived where the field or the mask needs it) into `lattice`, the scalar, the counting and

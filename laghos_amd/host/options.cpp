@@ -57,7 +57,8 @@ const FlagOpt kFlags[] = {
 const CountOpt kCounts[] = {
    {"-ckpt", "--checkpoint-steps", &Options::ckpt_steps, 1}, {"-ckpt-keep", "--checkpoint-keep", &Options::ckpt_keep, 0},
    {"-hist", "--history-steps", &Options::hist_steps, 1}, {"-prof", "--profile-steps", &Options::prof_steps, 1},
-   {"-map", "--map-steps", &Options::map_steps, 1}, {"-loads", "--loads-steps", &Options::loads_steps, 1}};
+   {"-map", "--map-steps", &Options::map_steps, 1}, {"-loads", "--loads-steps", &Options::loads_steps, 1},
+   {"-peaks", "--peaks-steps", &Options::peaks_steps, 1}};
 
 template <class Opt, size_t N> const Opt *Find(const Opt (&table)[N], const std::string &a)
 {
@@ -207,6 +208,15 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
          }
          continue;
       }
+      if (a == "-peaks-arrival" || a == "--peaks-arrival")
+      {
+         if (!(v = need(i))) { return false; }
+         char *end = nullptr;
+         o.peaks_arrival = std::strtod(v, &end);
+         o.peaks_arrival_set = true;
+         if (end == v || *end || !std::isfinite(o.peaks_arrival)) { return Refuse(err, "-peaks-arrival P: the pressure threshold must be a finite number, got " + std::string(v)); }
+         continue;
+      }
       if (a == "-restart" || a == "--restart")
       {
          if (!(v = need(i))) { return false; }
@@ -291,6 +301,11 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
    const char *map_detail = o.map_cells_n > 0 ? "-map-cells" : (o.map_box_n > 0 ? "-map-box" : nullptr);
    if (map_detail && o.map_steps == 0) { return Refuse(err, std::string(map_detail) + " describes the -map files: it needs -map"); }
    if (!o.loads_planes.empty() && o.loads_steps == 0) { return Refuse(err, "-loads-plane adds rows to the -loads file: it needs -loads"); }
+   if (o.peaks_arrival_set && o.peaks_steps == 0) { return Refuse(err, "-peaks-arrival adds the arrival time to the -peaks records: it needs -peaks"); }
+   if (o.peaks_steps > 0 && !o.paraview && !o.FaceDumps())
+   {
+      return Refuse(err, "-peaks keeps its records at the points of the material dumps: it needs -paraview, -pv-surface or -pv-slice");
+   }
    if (o.check_exact_sedov) // laghos.cpp:303-309, in the reference's words
    {
       if (o.problem != 1) { err = "Can only compare problem 1 (Sedov) against the exact solution"; return false; }

@@ -101,6 +101,13 @@ struct Options
    // lower AXIS for K < n, towards higher AXIS for K = n.  2D and 3D.
    int loads_steps = 0;
    std::vector<std::pair<int, int>> loads_planes; // (axis, K)
+   // -peaks N: running records at the lattice points of the material dumps that are on (-paraview, -pv-surface, -pv-slice) - peak
+   // pressure and its time, the pressure impulse, peak density, speed and energy (lgh_records_update) - updated at cycle
+   // 0, every N accepted steps, after the last one and whenever a dump is written, and written into those dumps as PointData.
+   // -peaks-arrival P adds the time at which the pressure first reached P.
+   int peaks_steps = 0;
+   bool peaks_arrival_set = false;
+   double peaks_arrival = 0;       // (meaningful with peaks_arrival_set)
    bool fingerprint = false;       // -fp: rank 0 prints the state fingerprint after the last step and per checkpoint
 };
 

@@ -106,6 +106,14 @@ def load():
         L.laghos_host_write_checkpoint.argtypes = [ctypes.c_char_p, P, P, P, P, Lg, P, P, Lg, ctypes.c_char_p, I]
         L.laghos_host_read_checkpoint.restype = I
         L.laghos_host_read_checkpoint.argtypes = [ctypes.c_char_p, P, P, P, P, Lg, P, P, Lg, ctypes.c_char_p, I]
+        L.laghos_sim_records.restype = Lg
+        L.laghos_sim_records.argtypes = [P, ctypes.c_char_p, P, ctypes.POINTER(D)]
+        L.laghos_host_write_records_sidecar.restype = I
+        L.laghos_host_write_records_sidecar.argtypes = [ctypes.c_char_p, P, Lg, D, I, I, D, I, ctypes.c_char_p, P, P, ctypes.c_char_p, I]
+        L.laghos_host_read_records_sidecar.restype = I
+        L.laghos_host_read_records_sidecar.argtypes = [ctypes.c_char_p, P, P, P, ctypes.c_char_p, I, P, I, P, Lg, ctypes.c_char_p, I]
+        L.laghos_host_match_records_sidecar.restype = I
+        L.laghos_host_match_records_sidecar.argtypes = [ctypes.c_char_p, P, I, I, D, I, ctypes.c_char_p, P, ctypes.c_char_p, I]
         L.laghos_sim_diagnostics.argtypes = [P, P]
         L.laghos_sim_profile.restype = I
         L.laghos_sim_profile.argtypes = [P, I, I, D, D, P, P, ctypes.POINTER(Lg)]
@@ -389,6 +397,85 @@ class Sim:
         if self.L.laghos_sim_write_checkpoint(self.h, str(stem).encode()) != 0:
             raise RuntimeError(self.L.laghos_sim_error(self.h).decode())
         return str(stem)
+
+    RECORD_COLS = ("p_max", "t_p_max", "impulse", "p_last", "rho_max", "speed_max", "e_max", "t_arrival")   # lgh_records_update
+
+    def records(self, which):
+        """The `-peaks` records as they stand at a point set of the run: which = "volume" (the lattice of `-paraview`), or as
+        select_faces takes it ("surface", (axis, K)).  A dict of the seven arrays a dump holds - peak_pressure, peak_pressure_time,
+        pressure_impulse, peak_density, peak_speed, peak_energy, arrival_time (-1 where the threshold was not reached, or none was
+        given) - over the points of that dump, and "time", the time of the last update."""
+        tag = which if isinstance(which, str) else f"slice_{which[0]}{int(which[1])}"
+        t = ctypes.c_double(np.nan)
+        n = self.L.laghos_sim_records(self.h, tag.encode(), None, ctypes.byref(t))
+        if n < 0:
+            raise RuntimeError(self.L.laghos_sim_error(self.h).decode())
+        buf = np.full((len(self.RECORD_COLS), n), np.nan)   # (an entry the library did not write would show)
+        if n:
+            self.L.laghos_sim_records(self.h, tag.encode(), buf.ctypes.data, None)
+        names = {"p_max": "peak_pressure", "t_p_max": "peak_pressure_time", "impulse": "pressure_impulse", "rho_max": "peak_density",
+                 "speed_max": "peak_speed", "e_max": "peak_energy", "t_arrival": "arrival_time"}
+        out = {names[c]: buf[k].copy() for k, c in enumerate(self.RECORD_COLS) if c in names}
+        out["time"] = t.value
+        return out
+
+
+class RecordsSidecarError(RuntimeError):
+    """A records sidecar that was refused: .code is the RecordsSidecarError of records_sidecar.hpp, the text names the file and the check."""
+
+    def __init__(self, code, msg):
+        super().__init__(msg)
+        self.code = code
+
+
+def host_write_records_sidecar(path, state_fp, ti, time, R, threshold, sets):
+    """records_sidecar.hpp WriteRecordsSidecar through the host probe: state_fp = (word, word), threshold a number or None, sets a
+    list of (tag, block) with block a float64 array (8, points)."""
+    L = load()
+    fp = np.array(state_fp, dtype=np.uint64)
+    blocks = [_f64(b).reshape(8, -1) for _, b in sets]
+    pts = np.array([b.shape[1] for b in blocks], dtype=np.int64)
+    allb = np.concatenate([b.reshape(-1) for b in blocks]) if blocks else np.zeros(0)
+    msg = ctypes.create_string_buffer(1024)
+    rc = L.laghos_host_write_records_sidecar(str(path).encode(), fp.ctypes.data, int(ti), float(time), int(R), int(threshold is not None),
+                                             0.0 if threshold is None else float(threshold), len(sets), " ".join(t for t, _ in sets).encode(), pts.ctypes.data,
+                                             allb.ctypes.data if allb.size else None, msg, len(msg))
+    if rc != 0:
+        raise RecordsSidecarError(rc, msg.value.decode())
+
+
+def host_read_records_sidecar(path, capacity_words=1 << 22, capacity_sets=64):
+    """records_sidecar.hpp ReadRecordsSidecar through the host probe: a dict state_fp, ti, time, R, threshold (None: none) and sets,
+    the list of (tag, block (8, points)); RecordsSidecarError when the file is refused."""
+    L = load()
+    fp, ints, dbls = np.zeros(2, np.uint64), np.zeros(4, np.int64), np.zeros(2, np.float64)
+    tags = ctypes.create_string_buffer(64 * capacity_sets)
+    pts, blocks = np.zeros(capacity_sets, np.int64), np.full(capacity_words, np.nan)
+    msg = ctypes.create_string_buffer(1024)
+    rc = L.laghos_host_read_records_sidecar(str(path).encode(), fp.ctypes.data, ints.ctypes.data, dbls.ctypes.data, tags, len(tags), pts.ctypes.data,
+                                            capacity_sets, blocks.ctypes.data, capacity_words, msg, len(msg))
+    if rc != 0:
+        raise RecordsSidecarError(rc, msg.value.decode())
+    sets, pos = [], 0
+    for k, tag in enumerate(tags.value.decode().split()):
+        n = int(pts[k])
+        sets.append((tag, blocks[pos:pos + 8 * n].reshape(8, n).copy()))
+        pos += 8 * n
+    return dict(state_fp=(int(fp[0]), int(fp[1])), ti=int(ints[0]), time=float(dbls[0]), R=int(ints[1]),
+                threshold=float(dbls[1]) if ints[2] else None, sets=sets)
+
+
+def host_match_records_sidecar(path, state_fp, R, threshold, sets):
+    """Reads the sidecar and holds it against what a restarting run expects, as the driver does (MatchRecordsSidecar): sets a list
+    of (tag, points).  RecordsSidecarError when it is refused."""
+    L = load()
+    fp = np.array(state_fp, dtype=np.uint64)
+    pts = np.array([n for _, n in sets], dtype=np.int64)
+    msg = ctypes.create_string_buffer(1024)
+    rc = L.laghos_host_match_records_sidecar(str(path).encode(), fp.ctypes.data, int(R), int(threshold is not None), 0.0 if threshold is None else float(threshold),
+                                             len(sets), " ".join(t for t, _ in sets).encode(), pts.ctypes.data, msg, len(msg))
+    if rc != 0:
+        raise RecordsSidecarError(rc, msg.value.decode())
 
 
 def host_partition(dim, nx, ny, nz, nranks):

@@ -139,6 +139,30 @@ class HydroOperator:
         res["faces"] = faces
         return res
 
+    def update_records(self, S, R, rec, t, dtr=0.0, threshold=None, first=False, faces=None):
+        """One update of a block of running records (Context.records_update; the driver's `-peaks`): p, rho, e and v of the state S are
+        sampled on the volume lattice of R cells per zone and direction - or, with `faces` ((nfaces, 2) ints), on those face
+        lattices - as the dumps sample them, and folded into rec, a device tensor of 8 n doubles (column-major, the columns of
+        Context.RECORD_COLS), at time t, dtr since the last update.  first: the update that starts the records.  Returns n.
+        Asynchronous; reads S and the set-up data, writes rec only."""
+        import numpy as np
+        from . import host_lib
+        p, ctx = self.p, self.ctx
+        dim = p.dim
+        if faces is not None:
+            faces = np.ascontiguousarray(np.asarray(faces, dtype=np.int32).reshape(-1, 2))
+        n = p.NE * (R + 1) ** dim if faces is None else faces.shape[0] * (R + 1) ** (dim - 1)
+        Bh, Bl = host_lib.host_lattice_tables(p.order_v, p.order_e, R)
+        rho_l2 = self.compute_density(S)
+        f = dict(v=ctx.empty(dim * n), e=ctx.empty(n), rho=ctx.empty(n), p=ctx.empty(n))
+        if faces is None:
+            ctx.sample_fields(S, rho_l2, Bh, Bl, **f)
+        elif n:
+            ctx.sample_faces(S, rho_l2, Bh, None, Bl, faces, **f)
+        ctx.records_update(dim, f["p"], f["rho"], f["e"], f["v"], t, dtr, rec, threshold=threshold, first=first)
+        ctx.sync()   # (the scratch tensors go out of scope here)
+        return n
+
     CONTOUR_FIELDS = ("density", "energy", "pressure", "speed", "x", "y", "z", "div_v", "detj", "sound_speed")
     CONTOUR_EXTRA = ("detj", "grad_v", "div_v", "vorticity", "sound_speed")
 
