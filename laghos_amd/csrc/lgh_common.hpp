@@ -340,7 +340,8 @@ struct lgh_ctx : lgh::CtxHandles
    int map_rows = 0;
    lgh::DevPtr<int> faces_dev; // lgh_sample_faces (lgh_faces.hip): the device copy of the caller's face list, 2 * faces_cap ints; regrown only when a longer list comes
    int faces_cap = 0;
-   lgh::DevPtr<char> loads_dev; // lgh_loads (lgh_loads.hip): the scratch of lgh_map for LGH_LOADS_MAX_ROWS rows, allocated at the first call
+   lgh::DevPtr<char> loads_dev; // lgh_loads (lgh_loads.hip): the same for loads_rows = LGH_LOADS_MAX_ROWS rows, allocated at the first call
+   int loads_rows = 0;
    lgh::DevPtr<int> loads_faces; // ... and the device copy of the caller's list, 3 * loads_cap ints; regrown only when a longer list comes
    int loads_cap = 0;
    lgh::DevPtr<long long> contour_dev; // lgh_contour (lgh_contour.hip): counts, skipped counts and offsets of contour_cap workgroups (3 n + 2 words); regrown only when the grid grows

@@ -6,17 +6,12 @@
 //   integrals ............. InternalEnergy / KineticEnergy, the reference's laghos_solver.cpp:640-697, and mass, volume,
 //                          momentum with the same rule
 //
-// One workgroup per zone at a time.  Phase A gathers the zone's x dofs through h1_map into LDS (as offsets from the zone's
-// first node: what the gradient needs, without the cancellation of absolute coordinates) and contracts them with
-// the 1-D tables direction by direction (sum factorisation, as lgh_sample.hip: D^dim -> Q D^(dim-1) -> ... with B or G
-// per axis); the last axis is contracted by the thread that owns the point, which forms the dim x dim Jacobian in
-// registers and leaves detJ in LDS.  Phase B does the same for v and e (through B_l2) and every thread folds its points
-// into 17 partials: fixed order in the thread, DPP tree in the wavefront, wavefronts in order - no atomics, the same
-// bits whatever the grid.  `TC` dof sets go through the staging buffers at a time (all of them where 64 KB of LDS
-// allow, one at Q5Q4 in 3D); every value is the same serial sum either way.
+// One workgroup per zone at a time evaluates the zone's points (ZoneEval, lgh_zone_eval.hpp: the sum factorisation that the
+// profiles and maps use too; the positions it keeps are not read here) and every thread folds its points into 17 partials:
+// fixed order in the thread, DPP tree in the wavefront, wavefronts in order - no atomics, the same bits whatever the grid.
 // diag_fold_k then folds each of the 17 zone arrays in ascending zone id with one workgroup of fixed shape.
 #include "lgh_common.hpp"
-#include "lgh_diag.hpp"
+#include "lgh_zone_eval.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -28,12 +23,9 @@ namespace lgh
 constexpr int kDiagZone = LGH_DIAG_ZONE_COUNT;
 constexpr int kDiagFoldThreads = 1024;
 
-struct DiagArgs
+struct DiagArgs : ZoneArgs
 {
-   const double *S, *B, *G, *Bl, *W, *gamma, *m;
-   const int *map, *zorder; // zorder: the library's own order of the zones (nullptr: the caller's)
-   double *out;             // [k * NE + z]
-   int NE, N, D, Q, L, TC;
+   double *out; // [k * NE + z]
 };
 
 // 0 sum, 1 min, 2 max
@@ -46,144 +38,26 @@ template <int DIM>
 __global__ void __launch_bounds__(256) diag_zones_k(const DiagArgs a)
 {
    extern __shared__ double sm[];
-   const int D = a.D, Q = a.Q, L = a.L, TC = a.TC, N = a.N, NE = a.NE;
-   const int ND = ipow_c<DIM>(D), NL = ipow_c<DIM>(L), NQ = ipow_c<DIM>(Q);
-   const int Qlow = NQ / Q;                      // points of the axes below the last one
-   const int S1 = (DIM == 3) ? D * D * Q : 0;    // one array after the first of two staged axes (3D)
-   const int S2 = (DIM == 1) ? ND : D * Qlow;    // one array in front of the last axis: [qlow + Qlow * d]
-   double *B = sm, *G = B + Q * D, *Bl = G + Q * D, *dj = Bl + Q * L, *red = dj + NQ, *U = red + kDiagZone * 4;
-   double *T1 = U + TC * ND, *P = T1 + 2 * TC * S1;
-   const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wid = t >> 6, nw = nt >> 6;
-   for (int i = t; i < Q * D; i += nt) { B[i] = a.B[i]; G[i] = a.G[i]; }
-   for (int i = t; i < Q * L; i += nt) { Bl[i] = a.Bl[i]; }
+   ZoneEval<DIM, kDiagZone * 4> zn(a, sm);
+   const int NE = a.NE, NQ = zn.NQ, nt = zn.nt, t = zn.t, lane = t & 63, wid = t >> 6, nw = nt >> 6;
+   double *red = zn.red;
    const double inf = INFINITY;
    for (int iz = blockIdx.x; iz < NE; iz += gridDim.x)
    {
       const int z = a.zorder ? a.zorder[iz] : iz;
-      const int *zmap = a.map + (size_t)z * ND;
-      // ---- phase A: J = grad x -> detJ at every point
-      for (int c0 = 0; c0 < DIM; c0 += TC)
-      {
-         const int nc = min(TC, DIM - c0);
-         __syncthreads(); // (the staging buffers are free: their last readers are behind this barrier)
-         for (int i = t; i < nc * ND; i += nt)
-         {
-            const int cc = i / ND, d = i - cc * ND;
-            // relative to the zone's first node: J = sum G x is a sum of differences (the rows of G sum to zero), and with x
-            // of O(1) and J of O(h) the absolute coordinates would cost J log2(1 / h) bits
-            const double *xc = a.S + (size_t)(c0 + cc) * N;
-            U[i] = xc[zmap[d]] - xc[zmap[0]];
-         }
-         __syncthreads();
-         if (DIM == 3)
-         {
-            for (int i = t; i < nc * 2 * S1; i += nt) // x axis: B u and G u, [qx + Q (dy + D dz)]
-            {
-               const int job = i / S1, o = i - job * S1, cc = job >> 1, r = o % Q, hi = o / Q;
-               T1[i] = diag_dot(D, Q, ((job & 1) ? G : B) + r, U + cc * ND + D * hi, 1);
-            }
-            __syncthreads();
-            for (int i = t; i < nc * 3 * S2; i += nt) // y axis: j = 0: B G u (d/dx), 1: G B u (d/dy), 2: B B u, [qx + Q (qy + Q dz)]
-            {
-               const int job = i / S2, o = i - job * S2, cc = job / 3, j = job - 3 * cc;
-               const int lo = o % Q, r = (o / Q) % Q, hi = o / (Q * Q);
-               const double *src = T1 + (cc * 2 + (j == 0 ? 1 : 0)) * S1 + lo + Q * D * hi;
-               P[((c0 + cc) * 3 + j) * S2 + o] = diag_dot(D, Q, ((j == 1) ? G : B) + r, src, Q);
-            }
-         }
-         else if (DIM == 2)
-         {
-            for (int i = t; i < nc * 2 * S2; i += nt) // x axis: j = 0: G u (d/dx), 1: B u, [qx + Q dy]
-            {
-               const int job = i / S2, o = i - job * S2, cc = job >> 1, j = job & 1, r = o % Q, hi = o / Q;
-               P[((c0 + cc) * 2 + j) * S2 + o] = diag_dot(D, Q, ((j == 0) ? G : B) + r, U + cc * ND + D * hi, 1);
-            }
-         }
-      }
-      __syncthreads();
-      for (int q = t; q < NQ; q += nt)
-      {
-         const int qlow = q % Qlow, qhi = q / Qlow;
-         double J[DIM * DIM]; // J[c * DIM + j] = d x_c / d xi_j
-         for (int c = 0; c < DIM; c++)
-         {
-            for (int j = 0; j < DIM; j++)
-            {
-               const double *src = (DIM == 1) ? U : P + (c * DIM + j) * S2;
-               J[c * DIM + j] = diag_dot(D, Q, ((j == DIM - 1) ? G : B) + qhi, src + qlow, Qlow);
-            }
-         }
-         double det;
-         if (DIM == 1) { det = J[0]; }
-         else if (DIM == 2) { det = J[0] * J[3] - J[1] * J[2]; }
-         else
-         {
-            det = J[0] * (J[4] * J[8] - J[5] * J[7]) - J[1] * (J[3] * J[8] - J[5] * J[6]) + J[2] * (J[3] * J[7] - J[4] * J[6]);
-         }
-         dj[q] = det;
-      }
-      // ---- phase B: v and e at every point (fields 0 .. DIM-1: v_c through B_h1, field DIM: e through B_l2)
-      for (int f0 = 0; f0 < DIM + 1; f0 += TC)
-      {
-         const int nf = min(TC, DIM + 1 - f0);
-         __syncthreads();
-         for (int i = t; i < nf * ND; i += nt)
-         {
-            const int ff = i / ND, d = i - ff * ND, f = f0 + ff;
-            if (f < DIM) { U[i] = a.S[(size_t)(DIM + f) * N + zmap[d]]; }
-            else if (d < NL) { U[i] = a.S[(size_t)2 * DIM * N + (size_t)z * NL + d]; }
-         }
-         if (DIM == 1) { continue; } // (TC = 2 in 1D: one pass, the last axis reads U)
-         __syncthreads();
-         if (DIM == 3)
-         {
-            for (int i = t; i < nf * S1; i += nt)
-            {
-               const int ff = i / S1, o = i - ff * S1, n = (f0 + ff < DIM) ? D : L;
-               if (o >= n * n * Q) { continue; }
-               const int r = o % Q, hi = o / Q;
-               T1[i] = diag_dot(n, Q, ((f0 + ff < DIM) ? B : Bl) + r, U + ff * ND + n * hi, 1);
-            }
-            __syncthreads();
-            for (int i = t; i < nf * S2; i += nt)
-            {
-               const int ff = i / S2, o = i - ff * S2, n = (f0 + ff < DIM) ? D : L;
-               if (o >= n * Q * Q) { continue; }
-               const int lo = o % Q, r = (o / Q) % Q, hi = o / (Q * Q);
-               P[(f0 + ff) * S2 + o] = diag_dot(n, Q, ((f0 + ff < DIM) ? B : Bl) + r, T1 + ff * S1 + lo + Q * n * hi, Q);
-            }
-         }
-         else
-         {
-            for (int i = t; i < nf * S2; i += nt)
-            {
-               const int ff = i / S2, o = i - ff * S2, n = (f0 + ff < DIM) ? D : L;
-               if (o >= n * Q) { continue; }
-               const int r = o % Q, hi = o / Q;
-               P[(f0 + ff) * S2 + o] = diag_dot(n, Q, ((f0 + ff < DIM) ? B : Bl) + r, U + ff * ND + n * hi, 1);
-            }
-         }
-      }
-      __syncthreads();
+      zn.fields(a, z, a.map + (size_t)z * zn.ND);
       // ---- the points of this thread, in ascending order; maxima are kept as minima of the negated values
       double acc[kDiagZone];
 #pragma unroll
       for (int k = 0; k < kDiagZone; k++) { acc[k] = (diag_kind(k) == 0) ? 0.0 : inf; }
       const double gm1 = a.gamma[z] - 1.0;
-      const double *F = (DIM == 1) ? U : P;
+      const double x0[DIM] = {}; // (the positions are not read: offsets from the first node, dropped)
       for (int q = t; q < NQ; q += nt)
       {
-         const int qlow = q % Qlow, qhi = q / Qlow;
-         double v[DIM], v2 = 0.0;
-         bool finite_v = true;
-         for (int c = 0; c < DIM; c++)
-         {
-            v[c] = diag_dot(D, Q, B + qhi, F + c * S2 + qlow, Qlow);
-            v2 += v[c] * v[c];
-            finite_v = finite_v && isfinite(v[c]);
-         }
-         const double e = diag_dot(L, Q, Bl + qhi, F + DIM * S2 + qlow, Qlow);
-         const double det = dj[q], w = a.W[q], m = a.m[(size_t)z * NQ + q];
+         double v[DIM], x[DIM], v2;
+         bool finite_v;
+         const double e = zn.point(q, x0, v, x, v2, finite_v);
+         const double det = zn.dj[q], w = a.W[q], m = a.m[(size_t)z * NQ + q];
          const bool fin = isfinite(det) && isfinite(e) && finite_v, inv = det <= 0.0;
          acc[0] += m;
          acc[1] += w * det;
@@ -283,27 +157,11 @@ static int diag_ready(lgh_ctx *c, const char *who)
 
 static int diag_zones(lgh_ctx *c, const double *S, double *zone_out)
 {
-   const int dim = c->dim, D = c->D1D, Q = c->Q1D, L = c->L1D;
+   const int dim = c->dim;
    DiagArgs a;
-   a.S = S; a.B = c->B; a.G = c->G; a.Bl = c->Bl; a.W = c->W; a.gamma = c->gamma; a.m = c->rho0DetJ0w;
-   a.map = c->h1map;
-   const MeshOrder *o = mesh_order(c);
-   a.zorder = o ? o->zorder_d : nullptr;
-   a.out = zone_out;
-   a.NE = c->NE; a.N = c->N; a.D = D; a.Q = Q; a.L = L;
-   const size_t S1 = (dim == 3) ? (size_t)D * D * Q : 0, S2 = (dim == 1) ? 0 : (size_t)D * (c->NQ / Q);
-   const size_t fixed = (size_t)Q * (2 * D + L) + c->NQ + kDiagZone * 4 + (size_t)dim * dim * S2;
    size_t lds = 0;
-   for (a.TC = dim + 1; a.TC >= 1; a.TC--) // dof sets in the staging buffers at a time: as many as 64 KB allow
-   {
-      lds = (fixed + (size_t)a.TC * (c->ND + 2 * S1)) * sizeof(double);
-      if (lds <= 64 * 1024 || dim == 1) { break; }
-   }
-   if (a.TC < 1 || lds > 64 * 1024)
-   {
-      set_error("lgh_diagnostics: one zone of D1D = %d, Q1D = %d needs %zu bytes of LDS", D, Q, lds);
-      return LGH_ERR_UNSUPPORTED;
-   }
+   LGH_PASS(zone_eval_args(c, "lgh_diagnostics", S, kDiagZone * 4, a, lds));
+   a.out = zone_out;
    const unsigned threads = (unsigned)std::min(256, 64 * ceil_div(c->NQ, 64));
    const unsigned grid = (unsigned)std::min(c->NE, 1 << 16);
    KtScope kt(c, LGH_KERNEL_DIAG);

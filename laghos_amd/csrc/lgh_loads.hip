@@ -7,21 +7,18 @@
 // D1D^(dim-1) per H1 component, L1D^(dim-1) for e and rho - over the dim - 1 tangential axes, and the area vector needs
 // tangential derivatives only: N = sgn t_b (x) t_c in 3D (b < c the tangential axes; the sign flips for a = 1, whose pair
 // (0, 2) is an odd permutation), sgn (t_y, -t_x) turned with the axis in 2D - row a of adj(J), Nanson, with no branch on a
-// determinant.  The tangents are formed from the offsets x - x_first of the face's nodes, as ProfZone forms its Jacobian.
+// determinant.  The tangents are formed from the offsets x - x_first of the face's nodes, as ZoneEval forms its Jacobian.
 // A workgroup of 256 threads takes FPB faces (as many as fit 256 points and 48 KB of LDS) without gathering a whole zone;
 // the fields - dim components of x, dim of v, e, rho - go one per pass through the same LDS and a thread keeps the values
 // of its ONE point in registers, as in lgh_faces.hip.
 //
-// Reduction: that of lgh_map.hip, shared through lgh_profile.hpp with NS = 8 sum columns - pass 0 for the column maxima
-// and the windows (min-reduced over the ranks), pass 1 splits every addend into the limbs of two sets and scatters them
-// with non-returning 64-bit integer atomics, a NaN flag per (row, column) for an addend that is not finite, pack / sums
-// over the ranks / value.  With at most 64 rows nearly every wavefront holds one row: the lanes of a row are folded per
-// column and limb (wave_sum_i64) and the row's 64 words go out as one wave instruction; after kLoadsFold distinct rows the
-// lanes left send their own atomics.  Counts and extremes: integer atomics.  p may be negative or zero (a projected density
-// can undershoot), so the extremes go through a key that orders ALL doubles - the bits with the sign bit set for p >= 0,
-// their complement below - where the profiles take the bits of a positive density as they are.  No floating-point atomic:
-// the same bits for every face order, numbering, launch grid and rank count.
-#include "lgh_profile.hpp"
+// Reduction: the exact binned sums of lgh_binsum.hpp, which describes the scheme, with eight sum columns.  With at most 64
+// rows nearly every wavefront holds one row, so the wavefront scatters by row as lgh_map.hip does by cell
+// (prof_scatter_cells); after kLoadsFold distinct rows the lanes left send their own atomics.  p may be negative or zero (a
+// projected density can undershoot), so the extremes go through the key that orders ALL doubles (ProfKeyOrdered) where the
+// profiles take the bits of a positive density as they are.  No floating-point atomic: the same bits for every face order,
+// numbering, launch grid and rank count.
+#include "lgh_binsum.hpp"
 #include "lgh_sample.hpp"
 
 #include <cmath>
@@ -33,7 +30,6 @@ constexpr int kLoadsSums = 8; // area force_x force_y force_z pa power flux xn: 
 constexpr int kLoadsFold = 8; // distinct rows a wavefront folds before its remaining lanes send their own atomics
 constexpr int kLoadsThreads = 256;
 static_assert(kLoadsSums + 3 == LGH_LOADS_COLS, "a row: n, the sums, p_min, p_max");
-static_assert(kLoadsSums == kProfMaxSums && kLoadsSums * kProfWords == kWave, "one word of a row per lane");
 
 struct LoadsArgs
 {
@@ -45,17 +41,6 @@ struct LoadsArgs
 };
 
 struct LoadsTabs { const double *B, *G, *Bl; };
-
-// a key that grows with p over all doubles but NaN, never 0 for a number: the extremes as integer maxima
-__device__ __forceinline__ unsigned long long loads_key(const double p)
-{
-   const long long b = __double_as_longlong(p);
-   return (b < 0) ? ~(unsigned long long)b : ((unsigned long long)b | 0x8000000000000000ULL);
-}
-__device__ __forceinline__ double loads_unkey(const unsigned long long k)
-{
-   return __longlong_as_double((long long)((k & 0x8000000000000000ULL) ? (k ^ 0x8000000000000000ULL) : ~k));
-}
 
 // the zone-local dof (n per direction) of entry i = i_b + n i_c of the face layer on side s of axis ax
 template <int DIM>
@@ -150,8 +135,8 @@ __global__ void __launch_bounds__(kLoadsThreads) loads_faces_k(const LoadsArgs a
    const int D = a.D, Q = a.Q, L = a.L, t = threadIdx.x, lane = t & 63;
    const int NPF = (DIM == 3) ? Q * Q : Q;
    double *B = sm, *G = B + Q * D, *Bl = G + Q * D, *w1 = Bl + Q * L, *red = w1 + Q;
-   int *meta = reinterpret_cast<int *>(red + 32); // per face of the workgroup: zone, local face, row, -
-   double *buf = red + 32 + 2 * a.FPB;
+   int *meta = reinterpret_cast<int *>(red + kProfRed); // per face of the workgroup: zone, local face, row, -
+   double *buf = red + kProfRed + 2 * a.FPB;
    const long k0 = (long)blockIdx.x * a.FPB;
    const int nf = (int)min((long)a.FPB, (long)a.nfaces - k0); // >= 1: the grid covers the list and no more
    for (int i = t; i < Q * D; i += kLoadsThreads) { B[i] = a.B[i]; G[i] = a.G[i]; }
@@ -235,88 +220,17 @@ __global__ void __launch_bounds__(kLoadsThreads) loads_faces_k(const LoadsArgs a
 #pragma unroll
    for (int k = 0; k < kLoadsSums; k++) { E[k] = prof_window(a.s.neg[k]); }
    const bool ext = ok && pr == pr; // (a NaN pressure - an overflowed product times zero - has no place in an order)
-   const unsigned long long key = loads_key(pr);
-   unsigned long long rem = __ballot(ok);
-   for (int nfold = 0; rem != 0 && nfold < kLoadsFold; nfold++) // (wave-uniform)
-   {
-      const int r = __builtin_amdgcn_readlane(row, __ffsll((long long)rem) - 1);
-      const bool mine = ok && row == r;
-      const unsigned long long in_row = __ballot(mine); // (lanes of one row retire together: all of them still remain)
-      const unsigned long long lo_bits = wave_max_u64((mine && ext) ? ~key : 0ULL), hi_bits = wave_max_u64((mine && ext) ? key : 0ULL);
-      if (lane == 0)
-      {
-         prof_add((long long *)a.s.count + r, (long long)__popcll(in_row));
-         if (lo_bits != 0) { prof_max(a.s.rmin + r, lo_bits); }
-         if (hi_bits != 0) { prof_max(a.s.rmax + r, hi_bits); }
-      }
-      long long keep = 0; // word `lane` of the row, folded over the lanes of the row
-#pragma unroll
-      for (int k = 0; k < kLoadsSums; k++)
-      {
-         if (k >= 1 + DIM && k < 4) { continue; } // (a force component above the dimension: nothing but zeros)
-         long long l[kProfWords];
-         {
-            long long h4[kLimbs] = {0, 0, 0, 0}, l4[kLimbs] = {0, 0, 0, 0};
-            const bool added = !mine || prof_split(h4, l4, ad[k], E[k]);
-            if (__ballot(!added) != 0 && lane == 0) { prof_max(a.s.flags + (size_t)r * kLoadsSums + k, 1ULL); }
-#pragma unroll
-            for (int j = 0; j < kLimbs; j++) { l[j] = h4[j]; l[kLimbs + j] = l4[j]; }
-         }
-#pragma unroll
-         for (int j = 0; j < kProfWords; j++)
-         {
-            if (__ballot(l[j] != 0) == 0) { continue; }
-            const long long s = wave_sum_i64(l[j]);
-            if (lane == k * kProfWords + j) { keep = s; }
-         }
-      }
-      if (keep != 0) { prof_add(a.s.words + (size_t)r * (kLoadsSums * kProfWords) + lane, keep); }
-      rem &= ~in_row;
-   }
-   if ((rem >> lane) & 1ULL) // what is left after kLoadsFold rows: this lane's own atomics
-   {
-      prof_add((long long *)a.s.count + row, 1LL);
-      if (ext)
-      {
-         prof_max(a.s.rmin + row, ~key);
-         prof_max(a.s.rmax + row, key);
-      }
-#pragma unroll
-      for (int k = 0; k < kLoadsSums; k++)
-      {
-         if (k >= 1 + DIM && k < 4) { continue; }
-         long long h4[kLimbs] = {0, 0, 0, 0}, l4[kLimbs] = {0, 0, 0, 0};
-         long long *wp_ = a.s.words + ((size_t)row * kLoadsSums + k) * kProfWords;
-         if (!prof_split(h4, l4, ad[k], E[k])) { prof_max(a.s.flags + (size_t)row * kLoadsSums + k, 1ULL); continue; }
-#pragma unroll
-         for (int j = 0; j < kLimbs; j++)
-         {
-            if (h4[j] != 0) { prof_add(wp_ + j, h4[j]); }
-            if (l4[j] != 0) { prof_add(wp_ + kLimbs + j, l4[j]); }
-         }
-      }
-   }
+   const unsigned long long key = ProfKeyOrdered::key(pr);
+   // (columns 1 + DIM .. 3: a force component above the dimension, nothing but zeros)
+   prof_scatter_cells<kLoadsSums, 1 + DIM, 4>(a.s, ok, row, ext ? ~key : 0ULL, ext ? key : 0ULL, ad, E, kLoadsFold, lane);
    const long long n = wave_sum_i64((live && !ok) ? 1LL : 0LL);
    if (lane == 0 && n != 0) { prof_add((long long *)a.s.excl, n); }
 }
 
-// behind prof_pack_k: the extremes of this rank as doubles out of their keys (prof_pack_k reads the words as the bits of a
-// positive density), the maximum negated for the min-reduce over the ranks; an empty row, or one of NaN pressures only: +inf
-__global__ void loads_extremes_k(const ProfScratch s, const int R)
-{
-   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-   if (i >= R) { return; }
-   const size_t n_rc = (size_t)R * kLoadsSums;
-   double *rmin = s.pk + n_rc * kProfPack + n_rc + R + 1, *rmax = rmin + R;
-   const unsigned long long lo = s.rmin[i], hi = s.rmax[i];
-   rmin[i] = lo ? loads_unkey(~lo) : INFINITY;
-   rmax[i] = hi ? -loads_unkey(hi) : INFINITY;
-}
-
-// what the launch is sized with: the bytes of the tables (with the reduction's 32 doubles) and of one face in LDS
+// what the launch is sized with: the bytes of the tables (with the kProfRed doubles of the reduction) and of one face in LDS
 static void loads_lds(const int dim, const int D, const int Q, const int L, size_t *tab_bytes, size_t *face_bytes)
 {
-   *tab_bytes = ((size_t)Q * (2 * D + L) + Q + 32) * sizeof(double);
+   *tab_bytes = ((size_t)Q * (2 * D + L) + Q + kProfRed) * sizeof(double);
    *face_bytes = (size_t)(2 + ipow(D, dim - 1) + (dim == 3 ? 2 * Q * D : 0)) * sizeof(double); // (two words in front: zone, face, row)
 }
 // faces per workgroup: as many as fit 256 points and 48 KB of LDS, one where they do not
@@ -417,7 +331,8 @@ int lgh_loads(lgh_ctx *c, const double *S, const double *rho_l2, int nrows, int 
    size_t tab_bytes, face_bytes;
    LGH_PASS(loads_supported(c, "lgh_loads", &tab_bytes, &face_bytes));
    // scratch for the most rows a call may ask for, allocated at the first call; the list on the device, regrown for a longer one
-   if (!c->loads_dev) { LGH_PASS(c->loads_dev.alloc(prof_layout<kLoadsSums>(nullptr, LGH_LOADS_MAX_ROWS).bytes)); }
+   LoadsArgs a;
+   LGH_PASS(prof_scratch<kLoadsSums>(c->loads_dev, c->loads_rows, LGH_LOADS_MAX_ROWS, a.s));
    if (nfaces > c->loads_cap)
    {
       c->loads_cap = 0;
@@ -425,56 +340,17 @@ int lgh_loads(lgh_ctx *c, const double *S, const double *rho_l2, int nrows, int 
       c->loads_cap = nfaces;
    }
    if (nfaces > 0) { LGH_HIP_CHECK(hipMemcpyAsync(c->loads_faces.p, faces, 3 * (size_t)nfaces * sizeof(int), hipMemcpyHostToDevice, c->stream)); }
-   LoadsArgs a;
    a.S = S; a.rho = rho_l2; a.B = c->B; a.G = c->G; a.Bl = c->Bl; a.w1 = c->w1d; a.gamma = c->gamma;
    a.map = c->h1map; a.faces = c->loads_faces;
    a.N = c->N; a.nfaces = nfaces; a.D = c->D1D; a.Q = c->Q1D; a.L = c->L1D;
    a.FPB = std::max(1, std::min(loads_fpb(dim, c->Q1D, tab_bytes, face_bytes), nfaces));
    a.stride = (int)(face_bytes / sizeof(double)) - 2;
-   a.s = prof_layout<kLoadsSums>(c->loads_dev, LGH_LOADS_MAX_ROWS);
    const size_t lds = tab_bytes + (size_t)a.FPB * face_bytes;
    const unsigned grid = (unsigned)ceil_div(nfaces, a.FPB);
-   const bool multi = c->multi != 0 && c->comm;
-   const int R = nrows;
-   {
-      KtScope kt(c, LGH_KERNEL_LOADS);
-      LGH_HIP_CHECK(hipMemsetAsync(c->loads_dev, 0, a.s.int_bytes, c->stream));
-      if (nfaces > 0)
-      {
-         if (dim == 3) { hipLaunchKernelGGL((loads_faces_k<3, 0>), dim3(grid), dim3(kLoadsThreads), lds, c->stream, a); }
-         else { hipLaunchKernelGGL((loads_faces_k<2, 0>), dim3(grid), dim3(kLoadsThreads), lds, c->stream, a); }
-         LGH_HIP_CHECK(hipGetLastError());
-      }
-      hipLaunchKernelGGL(prof_window_k<kLoadsSums>, dim3(1), dim3(64), 0, c->stream, a.s);
-      LGH_HIP_CHECK(hipGetLastError());
-      if (multi) { LGH_PASS(allreduce_dev_n(c, a.s.neg, kLoadsSums, 1)); }
-      if (nfaces > 0)
-      {
-         if (dim == 3) { hipLaunchKernelGGL((loads_faces_k<3, 1>), dim3(grid), dim3(kLoadsThreads), lds, c->stream, a); }
-         else { hipLaunchKernelGGL((loads_faces_k<2, 1>), dim3(grid), dim3(kLoadsThreads), lds, c->stream, a); }
-         LGH_HIP_CHECK(hipGetLastError());
-      }
-      // prof_finish with the extremes of this file between its pack and its sums over the ranks
-      const long n_rc = (long)R * kLoadsSums;
-      hipLaunchKernelGGL(prof_pack_k<kLoadsSums>, dim3(ceil_div(n_rc, 256)), dim3(256), 0, c->stream, a.s, R);
-      LGH_HIP_CHECK(hipGetLastError());
-      hipLaunchKernelGGL(loads_extremes_k, dim3(ceil_div(R, 64)), dim3(64), 0, c->stream, a.s, R);
-      LGH_HIP_CHECK(hipGetLastError());
-      if (multi)
-      {
-         const long n_sum = n_rc * kProfPack + n_rc + R + 1;
-         LGH_PASS(allreduce_dev_n(c, a.s.pk, n_sum, 0));
-         LGH_PASS(allreduce_dev_n(c, a.s.pk + n_sum, 2L * R, 1));
-      }
-      hipLaunchKernelGGL(prof_value_k<kLoadsSums>, dim3(ceil_div(R, 64)), dim3(64), 0, c->stream, a.s, R);
-      LGH_HIP_CHECK(hipGetLastError());
-   }
-   LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
-   const size_t n_out = (size_t)R * LGH_LOADS_COLS;
-   LGH_HIP_CHECK(hipMemcpy(out, a.s.out, n_out * sizeof(double), hipMemcpyDeviceToHost));
-   double ex = 0.0;
-   LGH_HIP_CHECK(hipMemcpy(&ex, a.s.out + n_out, sizeof(double), hipMemcpyDeviceToHost));
-   *n_excluded = (long)ex;
-   return LGH_OK;
+   auto launch = [&](const int pass) {
+      if (dim == 3) { hipLaunchKernelGGL((pass ? loads_faces_k<3, 1> : loads_faces_k<3, 0>), dim3(grid), dim3(kLoadsThreads), lds, c->stream, a); }
+      else { hipLaunchKernelGGL((pass ? loads_faces_k<2, 1> : loads_faces_k<2, 0>), dim3(grid), dim3(kLoadsThreads), lds, c->stream, a); }
+   };
+   return prof_run<kLoadsSums, ProfKeyOrdered>(c, a.s, nrows, LGH_KERNEL_LOADS, nfaces > 0, launch, out, n_excluded);
 }
 }

@@ -3,36 +3,16 @@
 // distance from an origin).  The bin sums are exact and order-free: the same bits for every zone order, node numbering,
 // launch grid and rank count.
 //
-// Point evaluation: the sum factorisation of diag_zones_k (lgh_diag.hip), one workgroup per zone at a time, with one
-// difference - the arrays of phase A that hold B..B (x - x_first) in front of the last axis are kept (phase B puts v and e
-// into the arrays of the gradient, which are free by then), so the last axis gives the position x_q beside v_q and e_q.
-// The kernel of lgh_diagnostics is left as it is; the two share diag_dot / ipow_c (lgh_diag.hpp).  The evaluation (ProfZone),
-// the split into limbs and the kernels in front of and behind the scatter pass live in lgh_profile.hpp, which lgh_map.hip
-// (lgh_map: the cells of a Cartesian grid for the bins of one coordinate) uses too; this file keeps the scatter of a profile.
+// Point evaluation: ZoneEval (lgh_zone_eval.hpp), one workgroup per zone at a time; the last axis gives the position x_q
+// beside v_q and e_q.  Reduction: the exact binned sums of lgh_binsum.hpp, which describes the scheme, with seven sum columns
+// and the density's extremes as the bits of a positive double.
 //
-// Reduction, in two passes over the zones:
-//   pass 0   the maximum of |addend| of each of the seven sum columns over all points that enter a row and whose addend
-//            is finite: integer atomic max on the bit pattern of a non-negative double (one per workgroup and column, 16
-//            shards), folded by prof_window_k, max-reduced over the ranks (as a min of the negated values).  A maximum is
-//            order-free, so the windows below are the same for every numbering, grid and rank count.
-//   pass 1   M < 2^e (frexp) gives the window E = max(e + 2, kProfMinE): every addend is below 2^(E-2), half of what
-//            exact_add takes (x < 2^31) - the one bit of margin is there so that the two passes, two instantiations of one
-//            template, need not round an addend alike.  Capacity needs none: limb 0 of an accumulator holds 2^33 such
-//            addends in 64 bits, more points than a mesh has (exact_add's own limit is 2^31).  An addend v is split exactly into
-//            hi = trunc(v 2^-g) 2^g with g = E - 128 and lo = v - hi: hi goes into four limbs under E, lo into four more
-//            under E - 96 - together seven limbs, 224 bits below 2^E, so that a row of a quiet region beside one loud zone (addends
-//            2^-80 of the largest: e and v 10^-12 of it) keeps every bit of its addends; with the 128 bits of one set such
-//            a row would keep 46.  The limbs are added into the 64-bit words of (row, column) by non-returning integer
-//            atomics; so are the count and the extremes of rho (bit patterns of positive doubles; the minimum as a maximum
-//            of the complement, so that one memset clears everything).  An addend that is not finite sets the flag of its
-//            (row, column), which comes out NaN.  No floating-point atomic anywhere.
-// A zone's points fall into few rows and same-address atomics serialise, so a wavefront folds its lanes per row first:
-// the range of rows by wave_min, per row and limb the lanes of other rows zeroed, wave_sum_i64, one atomic per non-zero
-// limb.  A range above `fold` rows (one zone under thousands of bins) takes one atomic per lane and non-zero limb instead.
-// prof_pack_k then normalises the words of this rank to |limb| < 2^32 as doubles (exact), the sums over the ranks are
-// all-reduces of those (exact in any order for fewer than 2^20 ranks), and prof_value_k joins the two sets, resolves the
-// carries, takes the sign out and calls exact_value once for the upper and once for the lower limbs.
-#include "lgh_profile.hpp"
+// What is this file's own is how a wavefront walks its rows.  A zone's points fall into few rows that lie side by side, so
+// the wavefront takes the range of its rows by wave_min and folds row after row of it (prof_fold_head, prof_fold_column:
+// one atomic per non-zero limb, from lane 0).  A range of `fold` rows or more (LGH_PROFILE_FOLD; one zone under thousands of
+// bins) takes one atomic per lane and non-zero limb instead (prof_lane_tail).
+#include "lgh_binsum.hpp"
+#include "lgh_zone_eval.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -43,7 +23,7 @@ namespace lgh
 constexpr int kProfSums = 7;           // vol mass ie ke mom pv mxi: columns 1..7 of a row
 static_assert(kProfSums + 3 == LGH_PROFILE_COLS, "a row: n, the sums, rho_min, rho_max");
 
-struct ProfArgs : ProfZoneArgs
+struct ProfArgs : ZoneArgs
 {
    int axis, nbins, fold;
    double lo, inv_w, origin[3];
@@ -54,7 +34,7 @@ template <int DIM, int PASS>
 __global__ void __launch_bounds__(256) prof_zones_k(const ProfArgs a)
 {
    extern __shared__ double sm[];
-   ProfZone<DIM> zn(a, sm);
+   ZoneEval<DIM, kProfRed> zn(a, sm);
    const int NE = a.NE, N = a.N, NQ = zn.NQ, nt = zn.nt, t = zn.t, lane = t & 63;
    int E[kProfSums];
    double mx[kProfSums];
@@ -138,54 +118,18 @@ __global__ void __launch_bounds__(256) prof_zones_k(const ProfArgs a)
                const bool mine = row == r;
                const unsigned long long in_row = __ballot(mine);
                if (in_row == 0) { continue; }
-               const unsigned long long lo_bits = wave_max_u64(mine ? ~rb : 0ULL), hi_bits = wave_max_u64(mine ? rb : 0ULL);
-               if (lane == 0)
-               {
-                  prof_add((long long *)a.s.count + r, (long long)__popcll(in_row));
-                  prof_max(a.s.rmin + r, lo_bits);
-                  prof_max(a.s.rmax + r, hi_bits);
-               }
+               prof_fold_head(a.s, r, in_row, mine ? ~rb : 0ULL, mine ? rb : 0ULL, lane);
 #pragma unroll
                for (int k = 0; k < kProfSums; k++)
                {
-                  long long l[kProfWords];
-                  {
-                     long long h4[kLimbs] = {0, 0, 0, 0}, l4[kLimbs] = {0, 0, 0, 0};
-                     const bool added = !mine || prof_split(h4, l4, ad[k], E[k]);
-                     if (__ballot(!added) != 0 && lane == 0) { prof_max(a.s.flags + (size_t)r * kProfSums + k, 1ULL); }
-#pragma unroll
-                     for (int j = 0; j < kLimbs; j++) { l[j] = h4[j]; l[kLimbs + j] = l4[j]; }
-                  }
                   long long *wp = a.s.words + ((size_t)r * kProfSums + k) * kProfWords;
-#pragma unroll
-                  for (int j = 0; j < kProfWords; j++)
-                  {
-                     if (__ballot(l[j] != 0) == 0) { continue; }
-                     const long long s = wave_sum_i64(l[j]);
-                     if (lane == 0 && s != 0) { prof_add(wp + j, s); }
-                  }
+                  prof_fold_column(mine, ad[k], E[k], a.s.flags + (size_t)r * kProfSums + k, lane, [&](const int j, const long long sum) {
+                     if (lane == 0 && sum != 0) { prof_add(wp + j, sum); }
+                  });
                }
             }
          }
-         else if (ok)
-         {
-            prof_add((long long *)a.s.count + row, 1LL);
-            prof_max(a.s.rmin + row, ~rb);
-            prof_max(a.s.rmax + row, rb);
-#pragma unroll
-            for (int k = 0; k < kProfSums; k++)
-            {
-               long long h4[kLimbs] = {0, 0, 0, 0}, l4[kLimbs] = {0, 0, 0, 0};
-               long long *wp = a.s.words + ((size_t)row * kProfSums + k) * kProfWords;
-               if (!prof_split(h4, l4, ad[k], E[k])) { prof_max(a.s.flags + (size_t)row * kProfSums + k, 1ULL); continue; }
-#pragma unroll
-               for (int j = 0; j < kLimbs; j++)
-               {
-                  if (h4[j] != 0) { prof_add(wp + j, h4[j]); }
-                  if (l4[j] != 0) { prof_add(wp + kLimbs + j, l4[j]); }
-               }
-            }
-         }
+         else if (ok) { prof_lane_tail<kProfSums, 0, 0>(a.s, row, ~rb, rb, ad, E); }
       }
    }
    if (PASS == 0) { prof_store_maxima<kProfSums>(a.s, mx, zn.red); }
@@ -217,19 +161,10 @@ extern "C" int lgh_profile(lgh_ctx *c, const double *S, const lgh_profile_spec *
       for (int k = 0; k < dim; k++) { LGH_CHECK_ARG(std::isfinite(spec->origin[k])); }
    }
    const int R = spec->nbins + 2;
-   if (R > c->prof_rows)
-   {
-      c->prof_rows = 0;
-      LGH_PASS(c->prof_dev.alloc(prof_layout<kProfSums>(nullptr, R).bytes));
-      c->prof_rows = R;
-   }
    ProfArgs a;
-   a.s = prof_layout<kProfSums>(c->prof_dev, c->prof_rows);
+   LGH_PASS(prof_scratch<kProfSums>(c->prof_dev, c->prof_rows, R, a.s));
    size_t lds = 0;
-   {
-      const int rc = prof_zone_args(c, "lgh_profile", S, a, lds);
-      if (rc) { return rc; }
-   }
+   LGH_PASS(zone_eval_args(c, "lgh_profile", S, kProfRed, a, lds));
    a.axis = spec->axis; a.nbins = spec->nbins;
    a.lo = spec->lo;
    a.inv_w = (double)spec->nbins / (spec->hi - spec->lo);
@@ -237,34 +172,10 @@ extern "C" int lgh_profile(lgh_ctx *c, const double *S, const lgh_profile_spec *
    a.fold = c->sw.profile_fold;
    const unsigned threads = (unsigned)std::min(256, 64 * ceil_div(c->NQ, 64));
    const unsigned grid = (unsigned)std::min(c->NE, kProfMaxGrid);
-   const bool multi = c->multi != 0 && c->comm;
-   {
-      KtScope kt(c, LGH_KERNEL_PROFILE);
-      LGH_HIP_CHECK(hipMemsetAsync(c->prof_dev, 0, a.s.int_bytes, c->stream));
-      if (dim == 3) { hipLaunchKernelGGL((prof_zones_k<3, 0>), dim3(grid), dim3(threads), lds, c->stream, a); }
-      else if (dim == 2) { hipLaunchKernelGGL((prof_zones_k<2, 0>), dim3(grid), dim3(threads), lds, c->stream, a); }
-      else { hipLaunchKernelGGL((prof_zones_k<1, 0>), dim3(grid), dim3(threads), lds, c->stream, a); }
-      LGH_HIP_CHECK(hipGetLastError());
-      hipLaunchKernelGGL(prof_window_k<kProfSums>, dim3(1), dim3(64), 0, c->stream, a.s);
-      LGH_HIP_CHECK(hipGetLastError());
-      if (multi)
-      {
-         const int rc = allreduce_dev_n(c, a.s.neg, kProfSums, 1);
-         if (rc) { return rc; }
-      }
-      if (dim == 3) { hipLaunchKernelGGL((prof_zones_k<3, 1>), dim3(grid), dim3(threads), lds, c->stream, a); }
-      else if (dim == 2) { hipLaunchKernelGGL((prof_zones_k<2, 1>), dim3(grid), dim3(threads), lds, c->stream, a); }
-      else { hipLaunchKernelGGL((prof_zones_k<1, 1>), dim3(grid), dim3(threads), lds, c->stream, a); }
-      LGH_HIP_CHECK(hipGetLastError());
-      // (the kernels behind index by the rows of THIS call; the layout is that of the allocation)
-      const int rc = prof_finish<kProfSums>(c, a.s, R);
-      if (rc) { return rc; }
-   }
-   LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
-   const size_t n_out = (size_t)R * LGH_PROFILE_COLS;
-   LGH_HIP_CHECK(hipMemcpy(out, a.s.out, n_out * sizeof(double), hipMemcpyDeviceToHost));
-   double ex = 0.0;
-   LGH_HIP_CHECK(hipMemcpy(&ex, a.s.out + n_out, sizeof(double), hipMemcpyDeviceToHost));
-   *n_excluded = (long)ex;
-   return LGH_OK;
+   auto launch = [&](const int pass) {
+      if (dim == 3) { hipLaunchKernelGGL((pass ? prof_zones_k<3, 1> : prof_zones_k<3, 0>), dim3(grid), dim3(threads), lds, c->stream, a); }
+      else if (dim == 2) { hipLaunchKernelGGL((pass ? prof_zones_k<2, 1> : prof_zones_k<2, 0>), dim3(grid), dim3(threads), lds, c->stream, a); }
+      else { hipLaunchKernelGGL((pass ? prof_zones_k<1, 1> : prof_zones_k<1, 0>), dim3(grid), dim3(threads), lds, c->stream, a); }
+   };
+   return prof_run<kProfSums, ProfKeyPositive>(c, a.s, R, LGH_KERNEL_PROFILE, true, launch, out, n_excluded);
 }
