@@ -587,6 +587,50 @@ int lgh_records_update(lgh_ctx *ctx, long n, int dim, const double *p, const dou
  * the cap and out[0] * out[1] * out[2] the points of one trip. */
 int lgh_records_shape(lgh_ctx *ctx, long n, long out[4]);
 
+/* ---- gauges: time series at material points (the driver's `-gauges`).  A gauge is a point (zone, reference coordinates
+ * xi in [0, 1]^dim): the same particle in every cycle, so nothing is located after the caller has chosen it.  A set of n
+ * gauges is an object of the context (a handle; destroying the context frees it).  The caller hands over the 1-D basis
+ * values at xi, as with the lattice tables - the library holds no basis definition:
+ *   Bh[(g*dim + a)*D1D + d]  H1 basis function d at xi_a of gauge g      Gh: its derivative
+ *   Bl[(g*dim + a)*L1D + l]  L2 basis function l there
+ * zone[g] is the caller's zone id on this rank, -1 where another rank owns the gauge.  A sample is one row of LGH_GAUGE_COLS
+ * doubles per gauge,
+ *   0..2 x   3..5 v   6 rho   7 e   8 p   9 cs   10 det J   11 div v      (components >= dim are 0)
+ * contracted with the stages and in the order of lgh_sample_fields / lgh_sample_derived (x axis first, every sum over its dofs
+ * ascending in one thread): a gauge at a lattice point, given that lattice's table rows, has the bits those calls hold there.
+ * det J = det(dx/dxi), div v = tr((dv/dxi) adj(J) / det J), cs = sqrt(gamma_z (gamma_z - 1) max(e, 0)) as lgh_sample_derived;
+ * rho = m_g / det J, ONE division, with m_g = rho0(xi) * det J0(xi) formed once at create from x0_h1 and rho0_l2 (device; the
+ * arrays lgh_setup_rho0detj0 took): the scheme's own pointwise density - strong mass conservation, what the quadrature update
+ * uses at its points - and not the projected density of the dumps; p = (gamma_z - 1) rho max(e, 0).  No branch looks at the
+ * sign of det J and nothing is trapped: an inverted zone gives det J <= 0, a NaN dof NaN, in the rows of its gauges only.
+ * lgh_gauges_sample appends one sample of the state S to the set's buffer of `capacity` samples: one kernel on the context's
+ * stream, no host wait; it reads S and writes the buffer only (the quadrature data, its generation counter and the fused force
+ * products are untouched).  On a full buffer: LGH_ERR_ARG, nothing launched.  lgh_gauges_drain synchronises, copies the pending
+ * samples to host_out[(s*n + g)*LGH_GAUGE_COLS + col], oldest first, and empties the buffer; *samples = their number (0: nothing
+ * was pending); max_samples below it: LGH_ERR_ARG, nothing drained.  lgh_gauges_mass: m_g (n doubles, host).
+ * Several ranks: every rank creates the set with the same n and capacity and samples and drains in step.  A rank fills the rows
+ * of gauges it does not own with -0.0 (m_g likewise) and the drain is collective, a SUM all-reduce of the transport: x + (-0.0)
+ * has the bits of x for every x, signed zeros included, so the sum is an exact gather and every rank gets every row.  A gauge
+ * that no rank owns, or two (on one rank: a zone of -1), is refused at create, on every rank.
+ * LGH_ERR_ARG with the value in the message, nothing launched or kept: n < 1, capacity < 1, a NULL argument, a call before
+ * lgh_setup_rho0detj0, capacity * n above LGH_GAUGE_MAX_ROWS (these must be the same on every rank), a zone outside -1..NE-1, a
+ * table entry that is not finite (these are agreed on between the ranks: all refuse), an unknown handle.  LGH_ERR_UNSUPPORTED: a gauge that needs more than 48 KB
+ * of LDS (D1D = 9 in 3D).
+ * lgh_gauges_shape: out[0] = gauges per workgroup (one wavefront each), out[1] = workgroups of a sample, out[2] = bytes of LDS
+ * of a workgroup, out[3] = its threads. */
+#define LGH_GAUGE_COLS 12 /* x0 x1 x2 v0 v1 v2 rho e p cs detj div_v ; components >= dim are 0 */
+#define LGH_GAUGE_MAX_ROWS 16777216L /* capacity * n of a set: 1.5 GiB of rows */
+int lgh_gauges_create(lgh_ctx *ctx, int n, const int *zone /* caller's zone id on this rank, -1: not this rank's */,
+                      const double *Bh /* host, n*dim*D1D: H1 basis values at xi_g, [(g*dim + a)*D1D + d] */,
+                      const double *Gh /* their derivatives */, const double *Bl /* n*dim*L1D, L2 basis values */,
+                      const double *x0_h1 /* device */, const double *rho0_l2 /* device */, int capacity, int *handle);
+int lgh_gauges_sample(lgh_ctx *ctx, int handle, const double *S); /* asynchronous, appends one sample */
+int lgh_gauges_pending(lgh_ctx *ctx, int handle, int *samples);
+int lgh_gauges_drain(lgh_ctx *ctx, int handle, double *host_out /* [s][g][LGH_GAUGE_COLS] */, int max_samples, int *samples);
+int lgh_gauges_mass(lgh_ctx *ctx, int handle, double *host_m /* n */);
+int lgh_gauges_shape(lgh_ctx *ctx, int handle, long out[4]); /* gauges per workgroup, workgroups, LDS bytes, threads */
+int lgh_gauges_destroy(lgh_ctx *ctx, int handle);
+
 /* ---- timing data (TimingData, laghos_solver.hpp:39-56): seconds measured with
  * HIP events around the same regions as the reference stopwatches.
  * t[0..3] = cgH1, cgL2, force, qdata; c[0..2] = H1iter, L2iter, quad_tstep */
@@ -616,6 +660,7 @@ int lgh_enable_timers(lgh_ctx *ctx, int on);
 #define LGH_KERNEL_LOADS 15       /* lgh_loads: both passes over the faces and the kernels between and behind them */
 #define LGH_KERNEL_CONTOUR 16     /* lgh_contour: the count pass, the scan, the look at the totals and the emit pass of one call */
 #define LGH_KERNEL_RECORDS 17     /* lgh_records_update */
+#define LGH_KERNEL_GAUGES 18      /* lgh_gauges_sample */
 int lgh_ktime_begin(lgh_ctx *ctx, int which, int max_samples);
 int lgh_ktime_end(lgh_ctx *ctx, int *launches, double *mean_seconds);
 /* Whether lgh_create found the 1-D H1 / L2 tables mirror symmetric, B[q,d] = B[Q-1-q, D-1-d] (any nodal or

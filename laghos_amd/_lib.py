@@ -112,6 +112,13 @@ SYMBOLS = {
     "lgh_contour_zpb": (_I, [_P, _I, ctypes.POINTER(_I)]),
     "lgh_records_update": (_I, [_P, _L, _I, _P, _P, _P, _P, _D, _D, _D, _I, _P]),
     "lgh_records_shape": (_I, [_P, _L, ctypes.POINTER(ctypes.c_long)]),
+    "lgh_gauges_create": (_I, [_P, _I, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p, _P, _P, _I, c_int_p]),
+    "lgh_gauges_sample": (_I, [_P, _I, _P]),
+    "lgh_gauges_pending": (_I, [_P, _I, c_int_p]),
+    "lgh_gauges_drain": (_I, [_P, _I, c_dbl_p, _I, c_int_p]),
+    "lgh_gauges_mass": (_I, [_P, _I, c_dbl_p]),
+    "lgh_gauges_shape": (_I, [_P, _I, ctypes.POINTER(ctypes.c_long)]),
+    "lgh_gauges_destroy": (_I, [_P, _I]),
     "lgh_get_timers": (_I, [_P, c_dbl_p, ctypes.POINTER(ctypes.c_long)]),
     "lgh_reset_timers": (_I, [_P]),
     "lgh_enable_timers": (_I, [_P, _I]),

@@ -163,6 +163,7 @@ class Context:
         self.ND, self.NQ, self.NL = D1D ** dim, Q1D ** dim, L1D ** dim
         self.H1V, self.L2V = dim * N, NE * self.NL
         self.device = torch.device("cuda", device)
+        self._gauge_sets = {}   # handle -> (gauges, capacity) of the sets gauges_create made
         keep = dict(
             h1=_np_i32(np.asarray(h1_map).reshape(-1)),
             B=_np_f64(np.asarray(B_h1).T.reshape(-1)),   # -> [q + Q*d]
@@ -744,6 +745,58 @@ class Context:
         out = (ctypes.c_long * 4)()
         check(self.lib.lgh_records_shape(self.h, int(n), out))
         return tuple(out)
+
+    GAUGE_COLS = ("x", "y", "z", "vx", "vy", "vz", "rho", "e", "p", "cs", "detj", "div_v")   # LGH_GAUGE_COLS = 12
+
+    def gauges_create(self, zone, Bh, Gh, Bl, x0, rho0_l2, capacity=256):
+        """lgh_gauges_create: a set of n gauges - material points (zone, xi) - as a handle.  zone: n ints, the caller's zone id on
+        this rank or -1; Bh, Gh (n, dim, D1D) and Bl (n, dim, L1D): host arrays of the 1-D H1 values, H1 derivatives and L2
+        values at xi per gauge and axis; x0, rho0_l2: device tensors of the initial positions and density dofs (m_g = rho0 detJ0
+        is formed from them); capacity: samples the device buffer holds.  Collective on several ranks."""
+        z = _np_i32(np.asarray(zone).reshape(-1))
+        n = int(z.size)
+        tabs = [_np_f64(np.asarray(T, dtype=np.float64).reshape(-1)) for T in (Bh, Gh, Bl)]
+        assert tabs[0].size == n * self.dim * self.D1D and tabs[1].size == tabs[0].size and tabs[2].size == n * self.dim * self.L1D
+        h = ctypes.c_int(-1)
+        check(self.lib.lgh_gauges_create(self.h, n, z.ctypes.data_as(_lib.c_int_p) if n else None, _dbl(tabs[0]), _dbl(tabs[1]), _dbl(tabs[2]),
+                                         _ptr(x0), _ptr(rho0_l2), int(capacity), ctypes.byref(h)))
+        self._gauge_sets[h.value] = (n, int(capacity))
+        return h.value
+
+    def gauges_sample(self, handle, S):
+        """lgh_gauges_sample: appends one sample of the state S to the set's buffer.  Asynchronous; refused on a full buffer."""
+        check(self.lib.lgh_gauges_sample(self.h, int(handle), _ptr(S)))
+
+    def gauges_pending(self, handle):
+        n = ctypes.c_int(-1)
+        check(self.lib.lgh_gauges_pending(self.h, int(handle), ctypes.byref(n)))
+        return n.value
+
+    def gauges_drain(self, handle):
+        """lgh_gauges_drain: the pending samples, oldest first, as (samples, n, 12) by GAUGE_COLS; empties the buffer.
+        Synchronous; collective on several ranks (every rank gets every row)."""
+        n, cap = self._gauge_sets.get(int(handle), (1, 1))
+        out = np.full((cap, n, len(self.GAUGE_COLS)), np.nan)   # (an entry the library did not write would show)
+        k = ctypes.c_int(-1)
+        check(self.lib.lgh_gauges_drain(self.h, int(handle), _dbl(out), cap, ctypes.byref(k)))
+        return out[:k.value].copy()
+
+    def gauges_mass(self, handle):
+        """lgh_gauges_mass: m_g = rho0(xi_g) detJ0(xi_g) of this rank's gauges (-0.0 where another rank owns one)"""
+        n, _ = self._gauge_sets.get(int(handle), (1, 1))
+        out = np.full(n, np.nan)
+        check(self.lib.lgh_gauges_mass(self.h, int(handle), _dbl(out)))
+        return out
+
+    def gauges_shape(self, handle):
+        """(gauges per workgroup, workgroups, LDS bytes of a workgroup, threads) of the launch gauges_sample makes"""
+        out = (ctypes.c_long * 4)()
+        check(self.lib.lgh_gauges_shape(self.h, int(handle), out))
+        return tuple(out)
+
+    def gauges_destroy(self, handle):
+        check(self.lib.lgh_gauges_destroy(self.h, int(handle)))
+        self._gauge_sets.pop(int(handle), None)
 
     def internal_energy(self, e):
         v = ctypes.c_double()

@@ -228,6 +228,17 @@ struct CtxHandles
    ~CtxHandles();
 };
 
+// One set of gauges (lgh_gauges.hip): material points (zone, reference coordinates) with their 1-D basis values, the mass
+// m_g = rho0 det J0 of each and the rows of the samples taken since the last drain.
+struct GaugeSet
+{
+   int n = 0, capacity = 0, pending = 0; // gauges, samples the buffer holds, samples in it
+   DevPtr<int> zone;                     // n: the caller's zone id, -1: another rank's
+   DevPtr<double> Bh, Gh, Bl;            // n*dim*D1D, the same, n*dim*L1D
+   DevPtr<double> mass;                  // n
+   DevPtr<double> rows;                  // capacity * n * LGH_GAUGE_COLS
+};
+
 } // namespace lgh
 
 // One context.  Every device buffer is a DevPtr of its element type and every other resource has an owner of its own, so
@@ -347,6 +358,7 @@ struct lgh_ctx : lgh::CtxHandles
    lgh::DevPtr<long long> contour_dev; // lgh_contour (lgh_contour.hip): counts, skipped counts and offsets of contour_cap workgroups (3 n + 2 words); regrown only when the grid grows
    int contour_cap = 0;
    lgh::DevPtr<unsigned long long> fp_dev; // lgh_vec_fingerprint (lgh_fingerprint.hip): the two words of the result and the workgroups' partial words, allocated on first use
+   std::vector<std::unique_ptr<lgh::GaugeSet>> gauges; // lgh_gauges_create (lgh_gauges.hip): the handle is the index; a destroyed set leaves its slot empty
 };
 
 namespace lgh

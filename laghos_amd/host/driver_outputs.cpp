@@ -477,6 +477,7 @@ bool WriteCheckpointPiece(laghos_sim *s, const std::string &stem, int ti_now, st
 {
    const Options &o = s->opt;
    const Discretization &d = *s->disc;
+   if (!DrainGauges(s)) { return false; } // -gauges: the file holds every sample up to this cycle before the checkpoint exists
    Laps laps(s->ckpt_seconds);
    unsigned long long own[2], all[2];
    if (!StateFingerprint(s, own, all)) { return false; }
@@ -694,14 +695,68 @@ static bool LoadsOpen(laghos_sim *s, int resume_cycle)
    });
 }
 
-// The periodic outputs in the order a step writes them
+std::vector<double> GaugePositions(const Options &o)
+{
+   std::vector<double> pts;
+   for (const std::vector<Options::GaugePoint> *list : {&o.gauge_points, &o.gauge_file_points})
+   {
+      for (const Options::GaugePoint &p : *list) { pts.insert(pts.end(), p.x, p.x + 3); }
+   }
+   return pts;
+}
+
+bool DrainGauges(laghos_sim *s)
+{
+   if (s->gauges_handle < 0 || s->gauges_pending.empty()) { return true; } // (the ranks sample in step: all or none have samples)
+   const int n = s->gauges_n;
+   const int got = s->hydro->DrainGauges(s->gauges_handle, n, s->gauges_rows);
+   if (got != (int)s->gauges_pending.size()) { return SimFail(s, "-gauges: the device buffer held " + std::to_string(got) + " samples, " + std::to_string(s->gauges_pending.size()) + " were taken"); }
+   const bool ok = WriteAndAgree(s, false, "cannot write the -gauges file: ", "rank 0 could not write the -gauges file", [&](std::string &err) {
+      std::string text;
+      for (int k = 0; k < got; k++) { text += GaugesText(s->gauges_pending[k].first, s->gauges_pending[k].second, n, s->gauges_rows.data() + (size_t)k * n * LGH_GAUGE_COLS); }
+      return HistoryAppend(s->gauges_file, text, err);
+   });
+   s->gauges_pending.clear();
+   return ok;
+}
+
+// One sample of the `-gauges` series for the state as it stands, cycle `cycle`: one kernel on the stream and a note of (cycle, t) -
+// no host wait; the lines are written when the buffer is drained (here once it is full).
+static bool GaugesRecord(laghos_sim *s, int cycle)
+{
+   s->hydro->SampleGauges(s->gauges_handle, s->S);
+   s->gauges_pending.emplace_back(cycle, s->t);
+   s->gauges_when.Written(cycle);
+   return (int)s->gauges_pending.size() < s->opt.gauge_buffer || DrainGauges(s);
+}
+
+// Opens the `-gauges` file on rank 0 as HistoryOpen opens the `-hist` file
+static bool GaugesOpen(laghos_sim *s, int resume_cycle)
+{
+   return WriteAndAgree(s, false, "cannot write the -gauges file: ", "rank 0 could not open the -gauges file", [&](std::string &err) {
+      const std::string path = GaugesPath(s->opt.basename);
+      GaugesFileInit(s->gauges_file);
+      return (resume_cycle < 0) ? HistoryStart(s->gauges_file, path, err) : HistoryResume(s->gauges_file, path, resume_cycle, err);
+   });
+}
+
+// The periodic outputs in the order a step writes them (the gauges first: a checkpoint of the same cycle drains their sample too)
 static const struct { Periodic laghos_sim::*when; bool (*write)(laghos_sim *, int cycle); } kPeriodic[] = {
-   {&laghos_sim::ckpt, PeriodicCheckpoint}, {&laghos_sim::hist_when, HistoryRecord}, {&laghos_sim::prof_when, ProfileRecord}, {&laghos_sim::map_when, MapRecord},
+   {&laghos_sim::gauges_when, GaugesRecord}, {&laghos_sim::ckpt, PeriodicCheckpoint}, {&laghos_sim::hist_when, HistoryRecord}, {&laghos_sim::prof_when, ProfileRecord}, {&laghos_sim::map_when, MapRecord},
    {&laghos_sim::loads_when, LoadsRecord}};
 
-void SetUpOutputs(laghos_sim *s, const std::vector<double> &S0)
+void SetUpOutputs(laghos_sim *s, const std::vector<double> &S0, const std::vector<double> &rho0_l2)
 {
    const Options &o = s->opt;
+   s->gauges_when.every = o.gauge_steps;
+   if (o.gauge_steps > 0) // (the options have been held against the mesh: every point lies in it)
+   {
+      std::vector<int> zone;
+      std::vector<double> xi;
+      (void)ResolveGauges(*s->disc, GaugePositions(o), zone, xi, nullptr);
+      s->gauges_n = (int)zone.size();
+      s->gauges_handle = s->hydro->CreateGauges(zone, xi, S0, rho0_l2, o.gauge_buffer);
+   }
    s->ckpt.every = o.ckpt_steps;
    s->ckpt.at_start = false;
    s->ckpt.again_after_repeat = true;
@@ -753,7 +808,8 @@ void SetUpOutputs(laghos_sim *s, const std::vector<double> &S0)
 bool OpenPeriodicOutputs(laghos_sim *s, int resume_cycle)
 {
    for (const auto &out : kPeriodic) { (s->*out.when).last = resume_cycle; } // (a restart: the run that wrote the checkpoint has them)
-   return (s->hist_when.every <= 0 || HistoryOpen(s, resume_cycle)) && (s->loads_when.every <= 0 || LoadsOpen(s, resume_cycle));
+   return (s->hist_when.every <= 0 || HistoryOpen(s, resume_cycle)) && (s->loads_when.every <= 0 || LoadsOpen(s, resume_cycle)) &&
+          (s->gauges_when.every <= 0 || GaugesOpen(s, resume_cycle));
 }
 
 bool WritePeriodicOutputs(laghos_sim *s, Periodic::Moment m, int cycle)
@@ -762,7 +818,7 @@ bool WritePeriodicOutputs(laghos_sim *s, Periodic::Moment m, int cycle)
    {
       if ((s->*out.when).Due(m, cycle, s->last_step) && !out.write(s, cycle)) { return false; }
    }
-   return true;
+   return !s->last_step || DrainGauges(s); // (the end of the run)
 }
 
 } // namespace laghos

@@ -1,6 +1,6 @@
 // driver_outputs.hpp — the simulation object of the driver and everything it writes: the -paraview / -pv-surface / -pv-slice /
-// -pv-iso / -pv-plane dumps, -print, checkpoints, the -hist / -prof / -map / -loads recorders with the one cadence they and -ckpt share,
-// and the -peaks records that live across steps (in the material dumps, and beside every checkpoint piece).
+// -pv-iso / -pv-plane dumps, -print, checkpoints, the -hist / -prof / -map / -loads / -gauges recorders with the one cadence they and
+// -ckpt share, and the -peaks records that live across steps (in the material dumps, and beside every checkpoint piece).
 #pragma once
 
 #include <chrono>
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "checkpoint.hpp"
+#include "gauges_output.hpp"
 #include "history.hpp"
 #include "laghos_solver.hpp"
 #include "loads_output.hpp"
@@ -138,6 +139,13 @@ struct laghos_sim
    int rec_updates = 0;
    laghos::Vector rec_scratch;
    std::vector<double> rec_host;
+   // -gauges: the file (rank 0), the set on the device (the gauges of every rank, in the order of the file) and, per sample it holds,
+   // (cycle, t); scratch; the samples of this run
+   Periodic gauges_when;
+   laghos::HistoryFile gauges_file;
+   int gauges_handle = -1, gauges_n = 0;
+   std::vector<std::pair<int, double>> gauges_pending;
+   std::vector<double> gauges_rows;
    int steps_at_start = 0;             // RK steps the checkpoint of a restart had taken: timing / FOM cover the restarted segment
 };
 
@@ -150,11 +158,16 @@ std::string Hex32(const unsigned long long fp[2]);
 
 // What the options ask for, fixed at the start from the initial state S0: the cadences, the -prof axis and range, the -map grid,
 // the face lists (collective on several ranks)
-void SetUpOutputs(laghos_sim *s, const std::vector<double> &S0);
+void SetUpOutputs(laghos_sim *s, const std::vector<double> &S0, const std::vector<double> &rho0_l2);
 // The first thing the periodic outputs do: a restart resumes from cycle resume_cycle >= 0, which has its outputs; -1 starts anew
 bool OpenPeriodicOutputs(laghos_sim *s, int resume_cycle);
-// Writes the periodic outputs due at this moment for the state as it stands, cycle `cycle`: -ckpt, -hist, -prof, -map, -loads
+// Writes the periodic outputs due at this moment for the state as it stands, cycle `cycle`: -gauges, -ckpt, -hist, -prof, -map, -loads
 bool WritePeriodicOutputs(laghos_sim *s, Periodic::Moment m, int cycle);
+// -gauges: the samples the device buffer holds become lines of the file (collective; nothing to do without pending samples).  The
+// driver drains when the buffer is full, before every checkpoint piece is written and after the last step.
+bool DrainGauges(laghos_sim *s);
+// The gauges of this run as ResolveGauges takes them: 3 doubles per gauge, the command line's first, then the file's
+std::vector<double> GaugePositions(const Options &o);
 
 // `-print`: basename_<ti>_{mesh,rho,v,e} from host copies of the state and the density
 bool WriteFields(const std::string &basename, int ti, const Discretization &d, int nranks, int rank, const std::vector<double> &S,

@@ -154,6 +154,35 @@ void LatticeGradTable(int order_v, int R, std::vector<double> &G_h1_lat)
    LagrangeTables(gll, pts, B, G_h1_lat);
 }
 
+void BasisAt(int order_v, int order_e, double xi, double *Bh, double *Gh, double *Bl)
+{
+   std::vector<double> gll, B, G, L;
+   const std::vector<double> pts(1, xi);
+   GaussLobatto(order_v + 1, gll);
+   LagrangeTables(gll, pts, B, G); // (one point: [q + 1*d] = [d])
+   BernsteinTable(order_e, pts, L);
+   std::copy(B.begin(), B.end(), Bh);
+   std::copy(G.begin(), G.end(), Gh);
+   std::copy(L.begin(), L.end(), Bl);
+}
+
+bool LocateInitial(const CartMesh &mesh, const double X[3], int zone_ijk[3], double xi[3])
+{
+   for (int a = 0; a < 3; a++) { zone_ijk[a] = 0; xi[a] = 0.0; }
+   for (int a = 0; a < mesh.dim; a++)
+   {
+      const std::vector<double> &b = mesh.brk[a];
+      const int n = mesh.ne(a);
+      if (n < 1 || !std::isfinite(X[a]) || X[a] < b[0] || X[a] > b[n]) { return false; }
+      // [brk_i, brk_{i+1}), the last interval closed: the first break point above X, or the last one
+      int i = (int)(std::upper_bound(b.begin(), b.end(), X[a]) - b.begin()) - 1;
+      i = std::min(i, n - 1);
+      zone_ijk[a] = i;
+      xi[a] = (X[a] - b[i]) / (b[i + 1] - b[i]);
+   }
+   return true;
+}
+
 // ---- mesh ---------------------------------------------------------------------------
 CartMesh CartMesh::Named(const std::string &name_in)
 {

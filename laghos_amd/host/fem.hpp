@@ -43,6 +43,10 @@ void LatticeTables(int order_v, int order_e, int R, std::vector<double> &B_h1_la
 // The derivatives of the H1 basis there (lgh_sample_derived): G_h1_lat[r + R1*d] = l_d'(r/R) - Tables::G with Q1D -> R1.
 void LatticeGradTable(int order_v, int R, std::vector<double> &G_h1_lat);
 
+// The three bases at ONE arbitrary abscissa xi in [0, 1] (a gauge, lgh_gauges_create): Bh[d] = l_d(xi), Gh[d] = l_d'(xi), d <
+// order_v + 1, Bl[l], l < order_e + 1 - a one-point table by the routines above, so xi = r/R gives row r of the lattice tables.
+void BasisAt(int order_v, int order_e, double xi, double *Bh, double *Gh, double *Bl);
+
 // ---- mesh ---------------------------------------------------------------------------
 // Tensor-product mesh given by per-axis break points; element e = ex + nx*(ey + ny*ez).
 struct CartMesh
@@ -56,6 +60,12 @@ struct CartMesh
    int ne(int a) const { return (int)brk[a].size() - 1; }
    long NE() const;
 };
+
+// Where the point X lies in the INITIAL mesh (a gauge of `-gauges`): per axis a < dim the zone index zone_ijk[a] of
+// the interval [brk_i, brk_{i+1}) that holds X[a] - the last interval is closed - and xi[a] = (X[a] - brk_i) / (brk_{i+1} - brk_i);
+// the entries of axes >= dim are 0.  Arithmetic on the break points: x(xi) is affine in every zone of a tensor grid.  false for a
+// point outside the mesh or not finite.
+bool LocateInitial(const CartMesh &mesh, const double X[3], int zone_ijk[3], double xi[3]);
 
 // Block partition of the element grid over `nranks` processes (one per GPU).
 struct Partition

@@ -11,6 +11,7 @@
 #include "checkpoint.hpp"
 #include "fem.hpp"
 #include "history.hpp"
+#include "gauges_output.hpp"
 #include "loads_output.hpp"
 #include "map_output.hpp"
 #include "records_sidecar.hpp"
@@ -324,6 +325,39 @@ int laghos_host_loads_write(const char *path, long keep_upto, const char *lines,
    CkptMsg(err, msg, msg_len);
    if (rows_in_file) { *rows_in_file = h.rows; }
    return ok ? 0 : -1;
+}
+// host-only: the `-gauges` file (gauges_output.hpp) the same way - the header line and the lines of one sample of n gauges from n x
+// LGH_GAUGE_COLS doubles (returns the length, -1 when buf is too small) -, the three 1-D bases at one abscissa (BasisAt: D1D, D1D and
+// L1D doubles), and the location of a point in the initial mesh given by its break points (LocateInitial: brk holds nbrk[0] +
+// nbrk[1] + nbrk[2] break points, axis by axis; 0 = found, -1 = refused: outside the mesh, not finite, or no mesh).
+const char *laghos_host_gauges_header() { return kGaugesHeader; }
+int laghos_host_gauges_text(long cycle, double t, int n, const double *rows, char *buf, int len)
+{
+   const std::string r = GaugesText(cycle, t, n, rows);
+   if ((int)r.size() + 1 > len) { return -1; }
+   std::memcpy(buf, r.c_str(), r.size() + 1);
+   return (int)r.size();
+}
+int laghos_host_basis_at(int order_v, int order_e, double xi, double *Bh, double *Gh, double *Bl)
+{
+   if (order_v < 1 || order_e < 0 || !Bh || !Gh || !Bl) { return -1; }
+   BasisAt(order_v, order_e, xi, Bh, Gh, Bl);
+   return 0;
+}
+int laghos_host_locate_initial(int dim, const int *nbrk, const double *brk, const double *X, int *zone_ijk, double *xi)
+{
+   if (dim < 1 || dim > 3 || !nbrk || !brk || !X || !zone_ijk || !xi) { return -1; }
+   CartMesh m;
+   m.dim = dim;
+   for (int a = 0; a < dim; a++)
+   {
+      if (nbrk[a] < 2) { return -1; }
+      m.brk[a].assign(brk, brk + nbrk[a]);
+      brk += nbrk[a];
+   }
+   double x3[3] = {0, 0, 0};
+   std::copy(X, X + dim, x3);
+   return LocateInitial(m, x3, zone_ijk, xi) ? 0 : -1;
 }
 // Builds the discretisation of one rank and returns sizes; arrays are copied out
 // by laghos_host_disc_get.  kind: 0 h1map, 1 S0, 2 rho0_l2, 3 gamma, 4 rho0_q,

@@ -269,7 +269,7 @@ laghos_sim *laghos_sim_create(int argc, const char *const *argv, int nranks, int
       if (refusal.empty()) { refusal = OperatorAndSolver(*s, init); }
       if (refusal.empty())
       {
-         SetUpOutputs(s.get(), init.S0);
+         SetUpOutputs(s.get(), init.S0, init.rho0_l2);
          if (restarting)
          {
             refusal = StateFromCheckpoint(*s, ck, ck_piece);
@@ -634,6 +634,31 @@ long laghos_sim_records(laghos_sim *s, const char *tag, double *out, double *tim
    s->error = "laghos_sim_records: this run keeps no records at " + want + (s->opt.peaks_steps > 0 ? " (no such dump is on)" : " (no -peaks)");
    return -1;
 }
+// The rows of the `-gauges` file for the state as it stands at n gauges given by their positions in the initial mesh (3 doubles per
+// gauge; entries of axes >= dim ignored): one un-buffered evaluation - a set of its own is created, sampled once, drained and
+// destroyed, and the initial arrays it forms its masses from are built and uploaded anew: an accessor for a look at a state, not for
+// a loop (a series is what -gauges is for) -, rows = n x LGH_GAUGE_COLS doubles.  Collective on several ranks (every rank gets every row).  0 = ok; otherwise
+// laghos_sim_error() has the message and nothing was written.
+int laghos_sim_gauges(laghos_sim *s, int n, const double *points, double *rows)
+{
+   if (n < 1 || n > 4096 || !points || !rows) { s->error = "laghos_sim_gauges: 1 to 4096 gauges, no NULL argument"; return LGH_ERR_ARG; }
+   std::vector<int> zone;
+   std::vector<double> xi, out;
+   int bad = -1;
+   if (!ResolveGauges(*s->disc, std::vector<double>(points, points + 3 * (size_t)n), zone, xi, &bad))
+   {
+      s->error = "laghos_sim_gauges: gauge " + std::to_string(bad) + " lies outside the initial mesh";
+      return LGH_ERR_ARG;
+   }
+   const InitialArrays init(*s->disc);
+   const int h = s->hydro->CreateGauges(zone, xi, init.S0, init.rho0_l2, 1);
+   s->hydro->SampleGauges(h, s->S);
+   const int got = s->hydro->DrainGauges(h, n, out);
+   s->hydro->DestroyGauges(h);
+   if (got != 1) { s->error = "laghos_sim_gauges: no sample came back"; return LGH_ERR_HIP; }
+   std::memcpy(rows, out.data(), (size_t)n * LGH_GAUGE_COLS * sizeof(double));
+   return 0;
+}
 double laghos_sim_energy(laghos_sim *s) { return s->hydro->InternalEnergy(s->S) + s->hydro->KineticEnergy(s->S); }
 void laghos_sim_sync(laghos_sim *s) { s->hydro->Sync(); }
 void laghos_sim_enable_timers(laghos_sim *s, int on) { s->hydro->EnableTimers(on != 0); }
@@ -720,6 +745,7 @@ int laghos_main(int argc, const char *const *argv)
    if (o.hist_steps > 0 && !o.quiet) { std::cout << "History: " << s->hist.path << ", " << s->hist.rows << " rows" << std::endl; }
    if (o.prof_steps > 0 && !o.quiet) { std::cout << "Profiles: " << s->prof_when.count << " files, " << o.basename << "_profile_*.csv" << std::endl; }
    if (o.map_steps > 0 && !o.quiet) { std::cout << "Maps: " << s->map_when.count << " files, " << MapDir(o.basename) << "/cycle_*.vti" << std::endl; }
+   if (o.gauge_steps > 0 && !o.quiet) { std::cout << "Gauges: " << s->gauges_file.path << ", " << s->gauges_when.count << " cycles x " << s->gauges_n << " gauges" << std::endl; }
    if (o.loads_steps > 0 && !o.quiet) { std::cout << "Loads: " << s->loads_file.path << ", " << s->loads_when.count << " cycles x " << s->loads_names.size() << " rows" << std::endl; }
    int ret = 0;
    if (o.check_exact_sedov)

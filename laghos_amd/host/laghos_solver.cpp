@@ -321,6 +321,33 @@ void LagrangianHydroOperator::UpdateRecords(const Vector &S, const Vector &rho, 
    LGH_VERIFY(lgh_records_update(ctx, n, dim, p, r, e, v, t, dtr, threshold, first ? 1 : 0, rec.ReadWrite()));
 }
 
+int LagrangianHydroOperator::CreateGauges(const std::vector<int> &zone, const std::vector<double> &xi, const std::vector<double> &S0,
+                                          const std::vector<double> &rho0_l2, int capacity) const
+{
+   const int n = (int)zone.size(), D = disc.tab.D1D, L = disc.tab.L1D;
+   std::vector<double> Bh((size_t)n * dim * D), Gh(Bh.size()), Bl((size_t)n * dim * L);
+   for (size_t k = 0; k < (size_t)n * dim; k++) { BasisAt(disc.tab.order_v, disc.tab.order_e, xi[k], &Bh[k * D], &Gh[k * D], &Bl[k * L]); }
+   Vector x0, r0;
+   x0.FromHost(std::vector<double>(S0.begin(), S0.begin() + H1Vsize));
+   r0.FromHost(rho0_l2);
+   int handle = -1;
+   LGH_VERIFY(lgh_gauges_create(ctx, n, zone.data(), Bh.data(), Gh.data(), Bl.data(), x0.Read(), r0.Read(), capacity, &handle));
+   return handle;
+}
+
+void LagrangianHydroOperator::SampleGauges(int handle, const Vector &S) const { LGH_VERIFY(lgh_gauges_sample(ctx, handle, S.Read())); }
+
+int LagrangianHydroOperator::DrainGauges(int handle, int n, std::vector<double> &rows) const
+{
+   int pending = 0, got = 0;
+   LGH_VERIFY(lgh_gauges_pending(ctx, handle, &pending));
+   rows.resize((size_t)std::max(pending, 1) * n * LGH_GAUGE_COLS);
+   LGH_VERIFY(lgh_gauges_drain(ctx, handle, rows.data(), pending, &got));
+   return got;
+}
+
+void LagrangianHydroOperator::DestroyGauges(int handle) const { LGH_VERIFY(lgh_gauges_destroy(ctx, handle)); }
+
 static const char *const kContourFields[] = {"density", "energy", "pressure", "speed", "x", "y", "z", "div_v", "detj", "sound_speed"};
 
 int LagrangianHydroOperator::ContourField(const std::string &name)

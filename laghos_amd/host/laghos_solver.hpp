@@ -129,6 +129,18 @@ public:
    void UpdateRecords(const Vector &S, const Vector &rho, int R, const std::vector<int> *faces, double t, double dtr, double threshold, bool first,
                       Vector &scratch, Vector &rec) const;
    long RecordPoints(int R, const std::vector<int> *faces) const { return faces ? FacePoints(R, (long)faces->size() / 2) : SamplePoints(R); }
+   // Gauges: time series at material points (lgh_gauges_*; the driver's `-gauges`).  CreateGauges makes a set of n =
+   // zone.size() gauges - zone[g] this rank's zone id or -1 where another rank owns the gauge, xi[g*dim + a] its reference
+   // coordinates - from the host copies of the initial state and density dofs (the gauge's mass rho0 detJ0 is formed from them), with
+   // a device buffer of `capacity` samples; returns the handle.  SampleGauges appends one sample of S: one kernel on the context's
+   // stream, no host wait.  DrainGauges takes the pending samples of the set of n gauges, oldest first, into rows (samples x n x
+   // LGH_GAUGE_COLS; sized anew) and returns their number.  Create and drain are collective on several ranks; the quadrature data is
+   // not touched.
+   int CreateGauges(const std::vector<int> &zone, const std::vector<double> &xi, const std::vector<double> &S0, const std::vector<double> &rho0_l2,
+                    int capacity) const;
+   void SampleGauges(int handle, const Vector &S) const;
+   int DrainGauges(int handle, int n, std::vector<double> &rows) const;
+   void DestroyGauges(int handle) const;
    // A contour of the state S, formed on the lattice of R + 1 points per direction (lgh_contour; the driver's `-pv-iso` / `-pv-plane`):
    // the iso-surface field = value of one of the fields below, or - field CONTOUR_PLANE - the cut plane coef . x = value.  Runs, in
    // this order, SampleFields (and SampleDerived where the field or the mask needs it) into `lattice`, the scalar, the counting and

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <iostream>
 
 #include "laghos_solver.hpp"
@@ -58,7 +59,10 @@ const CountOpt kCounts[] = {
    {"-ckpt", "--checkpoint-steps", &Options::ckpt_steps, 1}, {"-ckpt-keep", "--checkpoint-keep", &Options::ckpt_keep, 0},
    {"-hist", "--history-steps", &Options::hist_steps, 1}, {"-prof", "--profile-steps", &Options::prof_steps, 1},
    {"-map", "--map-steps", &Options::map_steps, 1}, {"-loads", "--loads-steps", &Options::loads_steps, 1},
-   {"-peaks", "--peaks-steps", &Options::peaks_steps, 1}};
+   {"-peaks", "--peaks-steps", &Options::peaks_steps, 1}, {"-gauges", "--gauge-steps", &Options::gauge_steps, 1}};
+
+constexpr size_t kGaugesOnCommandLine = 64, kGaugesInAll = 4096;
+constexpr double kGaugeBufferBytes = 256.0 * 1024 * 1024;
 
 template <class Opt, size_t N> const Opt *Find(const Opt (&table)[N], const std::string &a)
 {
@@ -120,6 +124,39 @@ bool ParsePlane(const std::string &opt, const char *noun, const std::string &ax,
    if (std::find(planes.begin(), planes.end(), sl) != planes.end()) { return Refuse(err, which + " is given twice"); }
    if (planes.size() == 8) { return Refuse(err, which + ": at most 8 " + noun + ", this is the ninth"); }
    planes.push_back(sl);
+   return true;
+}
+
+// -gauge-file PATH: one point per line - one to three numbers separated by blanks or tabs -, `#` starts a comment, empty lines are skipped
+bool ReadGaugeFile(const std::string &path, std::vector<Options::GaugePoint> &points, std::string &err)
+{
+   points.clear();
+   std::ifstream f(path.c_str());
+   if (!f) { return Refuse(err, "-gauge-file " + path + ": cannot read the file"); }
+   std::string line;
+   for (int no = 1; std::getline(f, line); no++)
+   {
+      const std::string where = "-gauge-file " + path + " line " + std::to_string(no);
+      line = line.substr(0, line.find('#'));
+      Options::GaugePoint p;
+      p.from = where;
+      const char *c = line.c_str();
+      while (true)
+      {
+         while (*c == ' ' || *c == '\t' || *c == '\r') { c++; }
+         if (!*c) { break; }
+         char *end = nullptr;
+         const double x = std::strtod(c, &end);
+         if (end == c || (*end && *end != ' ' && *end != '\t' && *end != '\r')) { return Refuse(err, where + ": malformed, a point is one to three numbers, got " + line); }
+         if (p.n == 3) { return Refuse(err, where + ": malformed, a point has at most three coordinates"); }
+         if (!std::isfinite(x)) { return Refuse(err, where + ": the coordinates must be finite numbers"); }
+         p.x[p.n++] = x;
+         c = end;
+      }
+      if (p.n > 0) { points.push_back(p); }
+   }
+   if (f.bad()) { return Refuse(err, "-gauge-file " + path + ": cannot read the file"); }
+   if (points.empty()) { return Refuse(err, "-gauge-file " + path + ": the file holds no point"); }
    return true;
 }
 
@@ -217,6 +254,35 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
          if (end == v || *end || !std::isfinite(o.peaks_arrival)) { return Refuse(err, "-peaks-arrival P: the pressure threshold must be a finite number, got " + std::string(v)); }
          continue;
       }
+      if (a == "-gauge" || a == "--gauge")
+      {
+         Options::GaugePoint p;
+         p.n = TakeNumbers(argc, argv, i, 3, false, p.x);
+         if (p.n == 0) { return Refuse(err, "-gauge X [Y [Z]] needs one to three numbers"); }
+         p.from = "-gauge";
+         for (int k = 0; k < p.n; k++) { p.from += std::string(" ") + argv[i - p.n + 1 + k]; }
+         for (int k = 0; k < p.n; k++) { if (!std::isfinite(p.x[k])) { return Refuse(err, p.from + ": the coordinates must be finite numbers"); } }
+         if (o.gauge_points.size() == kGaugesOnCommandLine) { return Refuse(err, p.from + ": at most 64 gauges on the command line (-gauge-file takes more), this is the 65th"); }
+         o.gauge_points.push_back(p);
+         continue;
+      }
+      if (a == "-gauge-file" || a == "--gauge-file")
+      {
+         if (!(v = need(i))) { return false; }
+         o.gauge_file = v;
+         if (!ReadGaugeFile(o.gauge_file, o.gauge_file_points, err)) { return false; }
+         continue;
+      }
+      if (a == "-gauge-buffer" || a == "--gauge-buffer")
+      {
+         if (!(v = need(i))) { return false; }
+         char *end = nullptr;
+         const long M = std::strtol(v, &end, 10);
+         o.gauge_buffer_set = true;
+         if (end == v || *end || M < 1 || M > 1000000000L) { return Refuse(err, "-gauge-buffer M: the buffer holds at least 1 sample, got " + std::string(v)); }
+         o.gauge_buffer = (int)M;
+         continue;
+      }
       if (a == "-restart" || a == "--restart")
       {
          if (!(v = need(i))) { return false; }
@@ -306,6 +372,19 @@ bool ParseArgs(int argc, const char *const *argv, Options &o, std::string &err)
    {
       return Refuse(err, "-peaks keeps its records at the points of the material dumps: it needs -paraview, -pv-surface or -pv-slice");
    }
+   const char *gauge_detail = !o.gauge_points.empty() ? "-gauge" : (!o.gauge_file.empty() ? "-gauge-file" : (o.gauge_buffer_set ? "-gauge-buffer" : nullptr));
+   if (gauge_detail && o.gauge_steps == 0) { return Refuse(err, std::string(gauge_detail) + " describes the gauges of the -gauges file: it needs -gauges"); }
+   if (o.gauge_steps > 0)
+   {
+      const size_t n = o.Gauges();
+      if (n == 0) { return Refuse(err, "-gauges records time series at gauges: it needs a point, -gauge X [Y [Z]] or -gauge-file PATH"); }
+      if (n > kGaugesInAll) { return Refuse(err, "-gauges: at most 4096 gauges in all, got " + std::to_string(n)); }
+      if ((double)o.gauge_buffer * (double)n * (LGH_GAUGE_COLS * sizeof(double)) > kGaugeBufferBytes)
+      {
+         return Refuse(err, "-gauge-buffer " + std::to_string(o.gauge_buffer) + ": " + std::to_string(o.gauge_buffer) + " samples of " + std::to_string(n) +
+                               " gauges need more than 256 MiB on the device");
+      }
+   }
    if (o.check_exact_sedov) // laghos.cpp:303-309, in the reference's words
    {
       if (o.problem != 1) { err = "Can only compare problem 1 (Sedov) against the exact solution"; return false; }
@@ -358,6 +437,16 @@ bool CheckAgainstMesh(Options &o, const CartMesh &mesh, std::string &err)
       const std::string ax(1, (char)('x' + pl.first)), which = "-loads-plane " + ax + " " + std::to_string(pl.second);
       if (pl.first >= o.dim) { return Refuse(err, which + ": the mesh has " + dims + " dimensions, there is no " + ax + " axis"); }
       if (pl.second > mesh.ne(pl.first)) { return Refuse(err, which + ": K is out of range, the zone grid has node planes 0.." + std::to_string(mesh.ne(pl.first)) + " along " + ax); }
+   }
+   for (const std::vector<Options::GaugePoint> *list : {&o.gauge_points, &o.gauge_file_points})
+   {
+      for (const Options::GaugePoint &p : *list)
+      {
+         if (p.n != o.dim) { return Refuse(err, p.from + ": the point has " + std::to_string(p.n) + " coordinates, the mesh has " + dims + " dimensions"); }
+         int ijk[3];
+         double xi[3];
+         if (!LocateInitial(mesh, p.x, ijk, xi)) { return Refuse(err, p.from + ": the point lies outside the initial mesh"); }
+      }
    }
    if (o.prof_axis.empty()) { o.prof_axis = (o.problem == 1) ? "r" : "x"; }
    const int prof_dims = (o.prof_axis == "r") ? 1 : o.prof_axis[0] - 'x' + 1; // the dimensions the axis needs

@@ -108,6 +108,22 @@ struct Options
    int peaks_steps = 0;
    bool peaks_arrival_set = false;
    double peaks_arrival = 0;       // (meaningful with peaks_arrival_set)
+   // -gauges N: time series at material points (lgh_gauges_*) in <basename>_gauges.csv - x, v, rho, e, p, cs, detJ and
+   // div v at every gauge at cycle 0, every N accepted steps and after the last one.  A gauge is given by its position in the INITIAL
+   // mesh: -gauge X [Y [Z]] (repeatable, at most 64) and -gauge-file PATH (one point per line, # comments), 4096 in all, in the order
+   // of the command line, then of the file.  -gauge-buffer M: samples held on the device between two drains (default 256).
+   int gauge_steps = 0;
+   struct GaugePoint
+   {
+      int n = 0;                   // the numbers given (the mesh's dimension decides whether they fit)
+      double x[3] = {0, 0, 0};
+      std::string from;            // "-gauge 0.5 0.25", "-gauge-file pts.txt line 3": what the messages call it
+   };
+   std::vector<GaugePoint> gauge_points, gauge_file_points;
+   std::string gauge_file;
+   bool gauge_buffer_set = false;
+   int gauge_buffer = 256;
+   size_t Gauges() const { return gauge_points.size() + gauge_file_points.size(); }
    bool fingerprint = false;       // -fp: rank 0 prints the state fingerprint after the last step and per checkpoint
 };
 

@@ -127,6 +127,16 @@ def load():
         L.laghos_host_loads_text.argtypes = [Lg, D, ctypes.c_char_p, P, ctypes.c_char_p, I]
         L.laghos_host_loads_write.restype = I
         L.laghos_host_loads_write.argtypes = [ctypes.c_char_p, Lg, ctypes.c_char_p, ctypes.POINTER(Lg), ctypes.c_char_p, I]
+        L.laghos_sim_gauges.restype = I
+        L.laghos_sim_gauges.argtypes = [P, I, P, P]
+        L.laghos_host_gauges_header.restype = ctypes.c_char_p
+        L.laghos_host_gauges_header.argtypes = []
+        L.laghos_host_gauges_text.restype = I
+        L.laghos_host_gauges_text.argtypes = [Lg, D, I, P, ctypes.c_char_p, I]
+        L.laghos_host_basis_at.restype = I
+        L.laghos_host_basis_at.argtypes = [I, I, D, P, P, P]
+        L.laghos_host_locate_initial.restype = I
+        L.laghos_host_locate_initial.argtypes = [I, P, P, P, P, P]
         L.laghos_host_write_vti.restype = I
         L.laghos_host_write_vti.argtypes = [ctypes.c_char_p, I, P, P, P, P, Lg, I, D]
         L.laghos_host_history_header.restype = ctypes.c_char_p
@@ -248,6 +258,20 @@ class Sim:
         if rc != 0:
             raise RuntimeError(f"laghos_sim_loads: error {rc}: {self.L.laghos_sim_error(self.h).decode()}")
         return loads_dict(names, rows, n_excl.value, dim)
+
+    def gauges(self, points):
+        """The rows of a `-gauges` file for the state as it stands at gauges given by their positions in the initial mesh (one
+        sequence of dim numbers each): (n, 12) by GAUGES_FILE_COLUMNS[3:] - one un-buffered evaluation, as `loads`; every rank calls it."""
+        dim = self.sizes()["dim"]
+        pts = np.zeros((len(points), 3))
+        for g, X in enumerate(points):
+            assert len(X) == dim, (X, dim)
+            pts[g, :dim] = X
+        rows = np.full((len(points), len(GAUGES_FILE_COLUMNS) - 3), np.nan)
+        rc = self.L.laghos_sim_gauges(self.h, len(points), pts.ctypes.data, rows.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"laghos_sim_gauges: error {rc}: {self.L.laghos_sim_error(self.h).decode()}")
+        return rows
 
     def derived_fields(self, R):
         """The derived fields of the state as it stands on the lattice of R cells per zone and direction (lgh_sample_derived;
@@ -703,6 +727,55 @@ def host_loads_text(cycle, t, names, rows):
     if n < 0:
         raise RuntimeError("host_loads_text: the lines do not fit")
     return buf.value.decode()
+
+
+GAUGES_FILE_COLUMNS = ("cycle", "t", "gauge", "x", "y", "z", "vx", "vy", "vz", "rho", "e", "p", "cs", "detj", "div_v")
+
+
+def host_gauges_header():
+    """The first line of a `-gauges` file (gauges_output.hpp), without its newline."""
+    return load().laghos_host_gauges_header().decode()
+
+
+def host_gauges_text(cycle, t, rows):
+    """The lines of one sample of a `-gauges` file, each with its newline, from the (n, 12) rows of lgh_gauges_drain."""
+    r = _f64(rows).reshape(-1, 12)
+    buf = ctypes.create_string_buffer(512 * max(1, len(r)))
+    n = load().laghos_host_gauges_text(int(cycle), float(t), len(r), r.ctypes.data, buf, len(buf))
+    if n < 0:
+        raise RuntimeError("host_gauges_text: the lines do not fit")
+    return buf.value.decode()
+
+
+def host_basis_at(order_v, order_e, xi):
+    """(Bh, Gh, Bl): the 1-D H1 basis, its derivative and the L2 basis at the abscissa xi (fem.hpp BasisAt; the tables of a gauge)."""
+    Bh, Gh, Bl = np.empty(order_v + 1), np.empty(order_v + 1), np.empty(order_e + 1)
+    if load().laghos_host_basis_at(int(order_v), int(order_e), float(xi), Bh.ctypes.data, Gh.ctypes.data, Bl.ctypes.data) != 0:
+        raise ValueError(f"host_basis_at({order_v}, {order_e}, {xi})")
+    return Bh, Gh, Bl
+
+
+def host_gauge_tables(order_v, order_e, xi):
+    """The tables Context.gauges_create takes for gauges at the reference coordinates xi (n, dim): Bh, Gh (n, dim, D1D), Bl (n, dim, L1D)."""
+    xi = np.asarray(xi, dtype=np.float64)
+    n, dim = xi.shape
+    Bh, Gh, Bl = np.empty((n, dim, order_v + 1)), np.empty((n, dim, order_v + 1)), np.empty((n, dim, order_e + 1))
+    for g in range(n):
+        for a in range(dim):
+            Bh[g, a], Gh[g, a], Bl[g, a] = host_basis_at(order_v, order_e, xi[g, a])
+    return Bh, Gh, Bl
+
+
+def host_locate_initial(breaks, X):
+    """fem.hpp LocateInitial: where the point X lies in the tensor grid with the break points `breaks` (one array per axis) -
+    (zone index per axis, xi per axis), or None where the driver refuses the point (outside the mesh, not finite)."""
+    dim = len(breaks)
+    nbrk = np.array([len(b) for b in breaks], dtype=np.int32)
+    brk = np.concatenate([_f64(b) for b in breaks])
+    x = _f64(np.asarray(X, dtype=np.float64).reshape(dim))
+    ijk, xi = np.zeros(3, dtype=np.int32), np.zeros(3)
+    rc = load().laghos_host_locate_initial(dim, nbrk.ctypes.data, brk.ctypes.data, x.ctypes.data, ijk.ctypes.data, xi.ctypes.data)
+    return None if rc != 0 else ([int(i) for i in ijk[:dim]], [float(v) for v in xi[:dim]])
 
 
 def host_loads_write(path, lines="", keep_upto=None):

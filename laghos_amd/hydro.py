@@ -34,7 +34,8 @@ class HydroOperator:
             ctx.comm_set_neighbors(comm["nbr_rank"], comm["nbr_nodes"])
         self.S0 = ctx.to_dev(S)
         x0 = ctx.clone(self.S0[:prob.H1V])
-        vol = ctx.setup_rho0detj0(x0, ctx.to_dev(rho_l2), ctx.to_dev(rho0_q))
+        self.rho0_l2 = ctx.to_dev(rho_l2)
+        vol = ctx.setup_rho0detj0(x0, self.rho0_l2, ctx.to_dev(rho0_q))
         ne = float(prob.NE)
         if multi:
             vol = ctx.allreduce(vol, 0)
@@ -162,6 +163,17 @@ class HydroOperator:
         ctx.records_update(dim, f["p"], f["rho"], f["e"], f["v"], t, dtr, rec, threshold=threshold, first=first)
         ctx.sync()   # (the scratch tensors go out of scope here)
         return n
+
+    def gauges(self, zone, xi, capacity=256):
+        """A set of gauges (Context.gauges_create; the driver's `-gauges`): material points given as zone[g] - this rank's zone id, -1
+        where another rank owns the gauge - and reference coordinates xi (n, dim).  Returns the handle for Context.gauges_sample /
+        gauges_pending / gauges_drain; the gauge's mass rho0 detJ0 comes from the initial state this operator was set up with.
+        Collective on several ranks."""
+        from . import host_lib
+        p, ctx = self.p, self.ctx
+        xi = np.asarray(xi, dtype=np.float64).reshape(-1, p.dim)
+        Bh, Gh, Bl = host_lib.host_gauge_tables(p.order_v, p.order_e, xi)
+        return ctx.gauges_create(zone, Bh, Gh, Bl, ctx.clone(self.S0[:p.H1V]), self.rho0_l2, capacity)
 
     CONTOUR_FIELDS = ("density", "energy", "pressure", "speed", "x", "y", "z", "div_v", "detj", "sound_speed")
     CONTOUR_EXTRA = ("detj", "grad_v", "div_v", "vorticity", "sound_speed")
