@@ -1,6 +1,7 @@
-"""2D runs on several ranks: the rank grids and the element grids that go with them, shared by tests/test_rank_cases.py
-(CPU: the conditions the GPU tests rely on), tests/test_gpu_ranks_2d.py (the kernels on ranks), tests/test_host_setup.py
-and the 2D entries of tests/test_gpu_pipeline.py::MULTI_RANK_CASES.
+"""Runs on several ranks: the rank grids and the element grids that go with them, shared by tests/test_rank_cases.py
+(CPU: the conditions the GPU tests rely on), tests/test_gpu_ranks_2d.py and tests/test_gpu_ranks_3d.py (the kernels on
+ranks), tests/test_host_setup.py and the 2D entries of tests/test_gpu_pipeline.py::MULTI_RANK_CASES.  2D first, the 3D table
+at the end.
 
 In 3D every velocity solve goes through the lockstep solver (lgh_vcg.hip); in 2D vcg_available() is false and
 lgh_solve_velocity runs the scalar cg_solve(LGH_SPACE_H1) of lgh_scg.hip once per component - whose several-rank branch
@@ -29,8 +30,24 @@ Two meshes per grid:
           each axis differ by more than 2e-3 (a kernel that reads a face or corner neighbour's factor is wrong by that
           much).  hx != hy in every zone as in shape_cases.
 
-The 3D block of the one 3D case (the several-rank branch of mass_apply_3d in MODE 2 is reachable through lgh_cg_solve only):
-2 x 1 x 1 ranks of 5 x 3 x 2 zones at Q2Q1."""
+The 3D block of the one 3D case of the 2D module (the several-rank branch of mass_apply_3d in MODE 2 is reachable through
+lgh_cg_solve only): 2 x 1 x 1 ranks of 5 x 3 x 2 zones at Q2Q1.
+
+The 3D table (tests/test_gpu_ranks_3d.py: the lockstep velocity solve of lgh_vcg.hip in its several-rank mode).  A block has 30
+zones (5 x 3 x 2: six full slab sets of 5, 1120 nodes at Q3Q2) or 20 zones (5 x 2 x 2, 784 nodes), both ragged against the plane
+batch of 13, the column batch of 7 and the Kronecker batch of 16:
+
+  rank grid  block      global      the smallest case of
+  2 x 1 x 1  5 x 3 x 2  10 x 3 x 2  one shared x-face: every slab set is an x-chain and the chains end at the rank boundary
+  1 x 1 x 2  5 x 3 x 2  5 x 3 x 4   the shared face is a z-plane: contiguous node lists
+  2 x 2 x 2  5 x 3 x 2  10 x 6 x 4  a corner node held by eight ranks, edge nodes by four, 7 peers each; all-pairs like the
+                                    two above, so (d, A d) rides on the halo messages and (r, z) goes as accumulator words
+  3 x 1 x 1  5 x 2 x 2  15 x 2 x 2  not all-pairs: the all-reduce fallback and ticketed (r, z), decided collectively
+  3 x 3 x 1  5 x 2 x 2  15 x 6 x 2  a middle rank with eight neighbours; nine ranks, not all-pairs
+
+laghos::Partition picks the table's rank grid for each of the five global shapes and rank counts, and 2 x 2 x 1 for the
+10 x 6 x 2 zones of the problem-7 case (tests/test_rank_cases.py asserts it); the kernel-level tests build their partition
+with the oracle and do not depend on it."""
 import zlib
 
 import numpy as np
@@ -50,6 +67,18 @@ RANK_GRIDS = {
 PEERS = {(2, 1): [1, 1], (1, 2): [1, 1], (2, 2): [3, 3, 3, 3], (3, 1): [1, 2, 1], (3, 2): [3, 5, 3, 3, 5, 3],
          (3, 3): [3, 5, 3, 5, 8, 5, 3, 5, 3]}
 BLOCK_3D, GRID_3D, ORDER_3D = (5, 3, 2), (2, 1, 1), (2, 1)
+# rank grid: (block, what it is the smallest case of)
+RANK_GRIDS_3D = {
+    (2, 1, 1): ((5, 3, 2), "one shared x-face: the x-chains end at the rank boundary; all-pairs"),
+    (1, 1, 2): ((5, 3, 2), "the shared face is a z-plane: contiguous node lists; all-pairs"),
+    (2, 2, 2): ((5, 3, 2), "a corner node held by eight ranks, edge nodes by four, 7 peers each; all-pairs"),
+    (3, 1, 1): ((5, 2, 2), "not all-pairs: the all-reduce fallback and ticketed (r, z)"),
+    (3, 3, 1): ((5, 2, 2), "a middle rank with eight neighbours; nine ranks, not all-pairs"),
+}
+# peers per rank (x fastest), counted by hand; the most ranks that hold one node; every rank sees every other
+PEERS_3D = {(2, 1, 1): [1, 1], (1, 1, 2): [1, 1], (2, 2, 2): [7] * 8, (3, 1, 1): [1, 2, 1], (3, 3, 1): [3, 5, 3, 5, 8, 5, 3, 5, 3]}
+HELD_MAX_3D = {(2, 1, 1): 2, (1, 1, 2): 2, (2, 2, 2): 8, (3, 1, 1): 2, (3, 3, 1): 4}
+ALL_PAIRS_3D = {(2, 1, 1): True, (1, 1, 2): True, (2, 2, 2): True, (3, 1, 1): False, (3, 3, 1): False}
 MESHES = sc.MESHES
 
 
@@ -61,8 +90,14 @@ def n_ranks(pgrid):
     return int(np.prod(pgrid))
 
 
+def block_of(pgrid):
+    """the block of zones every rank of the grid holds: the 2D block, or the 3D table's (a 3D grid outside it: BLOCK_3D)"""
+    pgrid = tuple(pgrid)
+    return BLOCK if len(pgrid) == 2 else RANK_GRIDS_3D.get(pgrid, (BLOCK_3D,))[0]
+
+
 def global_shape(pgrid, block=None):
-    block = block or (BLOCK if len(pgrid) == 2 else BLOCK_3D)
+    block = block or block_of(pgrid)
     return tuple(int(b * p) for b, p in zip(block, pgrid))
 
 
@@ -131,6 +166,31 @@ def problems(pgrid, mesh, order, problem=1):
             check_graded(glob)
         _problems[key] = (glob, ranks)
     return _problems[key]
+
+
+def permuted_rank(prob_r, seed):
+    """A rank problem under a random renumbering of its nodes and zones (helpers.PermutedProblem), with the neighbour lists
+    translated by node_perm - PermutedProblem.__getattr__ would hand through the lists of the base numbering, which name
+    other nodes there.  The order within a list stays the base problem's, so both sides still list the same global nodes
+    in the same order.  unpermute_nodes / unpermute_zones take a result back to the generator's numbering."""
+    from helpers import PermutedProblem
+
+    class PermutedRank(PermutedProblem):
+        def neighbors(self):
+            nr, lists = self.base.neighbors()
+            return nr, [self.node_perm[np.asarray(l, dtype=np.int64)].astype(np.int32) for l in lists]
+
+    return PermutedRank(prob_r, seed=seed)
+
+
+def unpermute_nodes(perm, v, ncomp=1):
+    return np.ascontiguousarray(np.asarray(v).reshape(ncomp, perm.base.N)[:, perm.node_perm]).reshape(-1)
+
+
+def unpermute_zones(perm, a, per_zone):
+    out = np.empty((perm.base.NE, per_zone))
+    out[perm.elem_perm] = np.asarray(a).reshape(perm.base.NE, per_zone)
+    return out.reshape(-1)
 
 
 # ---- a rank's zones and nodes in the global numbering, from the integer block offsets ---------------------------------------

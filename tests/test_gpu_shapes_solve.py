@@ -11,7 +11,8 @@ tests/test_gpu_shapes_operators.py).
   * the same right-hand side under a random renumbering of nodes and zones (helpers.PermutedProblem), in the library's
     own order and in the caller's;
   * the C++ driver's own set-up of such grids (-nx -ny -nz -Sx -Sy -Sz) against the oracle on the same break points.
-The several-rank runs on such grids are cases of tests/test_gpu_pipeline.py::test_multi_rank_run_on_one_gpu.
+Several ranks on such grids: tests/test_gpu_ranks_3d.py holds every entry of the right-hand side to the oracle (3D; 2D:
+tests/test_gpu_ranks_2d.py); whole runs are cases of tests/test_gpu_pipeline.py::test_multi_rank_run_on_one_gpu.
 
 Measured on an MI355X, worst over the shapes and forms (two runs): dx/dt exact; dv/dt 1.8e-15 (Q1Q0), 9.4e-15 (Q2Q1),
 4.7e-14 (Q3Q2), 8.3e-14 (Q4Q3), 5.7e-14 (Q5Q4) against 1e-10; de/dt 1.3e-15, 1.4e-14, 1.1e-13, 1.0e-13 against 1e-10 and
