@@ -226,28 +226,17 @@ int lgh_sample_derived(lgh_ctx *c, const double *S, int R1, const double *B_h1_l
       set_error("lgh_sample_derived: %s is NULL", !B_h1_lat ? "B_h1_lat" : (!G_h1_lat ? "G_h1_lat" : "B_l2_lat"));
       return LGH_ERR_ARG;
    }
-   if (R1 < 2 || R1 > 9)
-   {
-      set_error("lgh_sample_derived: R1 = %d lattice points per direction is out of range (2 <= R1 <= 9)", R1);
-      return LGH_ERR_ARG;
-   }
+   LGH_PASS(lattice_r1("lgh_sample_derived", R1));
    const int dim = c->dim, D = c->D1D, L = c->L1D;
    if (dim == 1 && vort_out)
    {
       set_error("lgh_sample_derived: vort_out: there is no vorticity in 1D");
       return LGH_ERR_ARG;
    }
-   if (R1 * D > kSampleMaxTab || R1 * L > kSampleMaxTab)
-   {
-      set_error("lgh_sample_derived: lattice tables of R1 * D1D = %d entries (at most %d)", R1 * D, kSampleMaxTab);
-      return LGH_ERR_UNSUPPORTED;
-   }
-   if (!detj_out && !gradv_out && !div_out && !vort_out && !cs_out) { return LGH_OK; }
    DerivedArgs a;
    memset(&a, 0, sizeof(a));
-   std::copy(B_h1_lat, B_h1_lat + (size_t)R1 * D, a.Th);
-   std::copy(G_h1_lat, G_h1_lat + (size_t)R1 * D, a.Gh);
-   std::copy(B_l2_lat, B_l2_lat + (size_t)R1 * L, a.Tl);
+   LGH_PASS(lattice_tables("lgh_sample_derived", c, R1, B_h1_lat, G_h1_lat, B_l2_lat, a.Th, a.Gh, a.Tl));
+   if (!detj_out && !gradv_out && !div_out && !vort_out && !cs_out) { return LGH_OK; }
    const int NPZ = ipow(R1, dim);
    a.x = S; a.v = S + (size_t)c->H1V; a.e = S + 2 * (size_t)c->H1V;
    a.detj = detj_out; a.gradv = gradv_out; a.div = div_out; a.vort = vort_out; a.cs = cs_out;
@@ -263,15 +252,10 @@ int lgh_sample_derived(lgh_ctx *c, const double *S, int R1, const double *B_h1_l
    const int h1 = ipow(D, dim) + (dim >= 2 ? 2 * R1 * ipow(D, dim - 1) : 0) + (dim == 3 ? 3 * R1 * R1 * D : 0);
    const int l2 = std::max(ipow(L, dim), dim == 3 ? L * R1 * R1 : 0) + (dim >= 2 ? ipow(L, dim - 1) * R1 : 0);
    a.stride = std::max(h1, l2);
-   const size_t zone_bytes = (size_t)a.stride * sizeof(double);
-   const size_t tab_bytes = (size_t)R1 * (2 * D + L) * sizeof(double), budget = 48 * 1024;
-   if (zone_bytes + tab_bytes > 64 * 1024)
-   {
-      set_error("lgh_sample_derived: one zone of D1D = %d on R1 = %d points needs %zu bytes of LDS", D, R1, zone_bytes + tab_bytes);
-      return LGH_ERR_UNSUPPORTED;
-   }
+   const size_t zone_bytes = (size_t)a.stride * sizeof(double), tab_bytes = (size_t)R1 * (2 * D + L) * sizeof(double);
+   LGH_PASS(lattice_lds_fits("lgh_sample_derived", "zone", c, R1, zone_bytes + tab_bytes));
    // several zones per workgroup where a zone's lattice is smaller than the workgroup, as far as 48 KB of LDS go
-   a.ZPB = std::max(1, std::min(std::min(kSampleThreads / NPZ, (int)((budget - tab_bytes) / zone_bytes)), c->NE));
+   a.ZPB = std::min(patches_per_group(kSampleThreads, NPZ, tab_bytes, zone_bytes), c->NE);
    const size_t lds = tab_bytes + (size_t)a.ZPB * zone_bytes;
    const unsigned grid = (unsigned)ceil_div(c->NE, a.ZPB);
    KtScope kt(c, LGH_KERNEL_DERIVED);

@@ -294,13 +294,6 @@ static void faces_lds(const int dim, const int D, const int L, const int R1, siz
    *face_bytes = (size_t)(1 + std::max(h1, l2)) * sizeof(double); // (one word in front: the face's zone and local face)
    *tab_bytes = (size_t)(R1 + 2) * (2 * D + L) * sizeof(double);
 }
-// faces per workgroup: as many as fit 256 lattice points and 48 KB of LDS, one where they do not
-static int faces_fpb(const int dim, const int R1, const size_t tab_bytes, const size_t face_bytes)
-{
-   const size_t budget = 48 * 1024;
-   const int by_lds = tab_bytes + face_bytes <= budget ? (int)((budget - tab_bytes) / face_bytes) : 1;
-   return std::max(1, std::min(kSampleThreads / ipow(R1, dim - 1), by_lds));
-}
 
 } // namespace lgh
 
@@ -312,14 +305,14 @@ extern "C"
 int lgh_sample_faces_fpb(lgh_ctx *c, int R1, int *fpb)
 {
    LGH_CHECK_ARG(c && fpb);
-   if (c->dim == 1 || R1 < 2 || R1 > 9 || R1 * c->D1D > kSampleMaxTab || R1 * c->L1D > kSampleMaxTab)
+   if (c->dim == 1 || lattice_refusal(c, R1) != LGH_OK)
    {
       set_error("lgh_sample_faces_fpb: dim = %d, R1 = %d: lgh_sample_faces refuses these", c->dim, R1);
       return LGH_ERR_ARG;
    }
    size_t tab_bytes, face_bytes;
    faces_lds(c->dim, c->D1D, c->L1D, R1, &tab_bytes, &face_bytes);
-   *fpb = faces_fpb(c->dim, R1, tab_bytes, face_bytes);
+   *fpb = patches_per_group(kSampleThreads, ipow(R1, c->dim - 1), tab_bytes, face_bytes);
    return LGH_OK;
 }
 
@@ -334,11 +327,7 @@ int lgh_sample_faces(lgh_ctx *c, const double *S, const double *rho_l2, int R1, 
       set_error("lgh_sample_faces: dim = 1: faces are sampled in 2D and 3D");
       return LGH_ERR_ARG;
    }
-   if (R1 < 2 || R1 > 9)
-   {
-      set_error("lgh_sample_faces: R1 = %d lattice points per direction is out of range (2 <= R1 <= 9)", R1);
-      return LGH_ERR_ARG;
-   }
+   LGH_PASS(lattice_r1("lgh_sample_faces", R1));
    if (nfaces < 0)
    {
       set_error("lgh_sample_faces: nfaces = %d", nfaces);
@@ -375,19 +364,12 @@ int lgh_sample_faces(lgh_ctx *c, const double *S, const double *rho_l2, int R1, 
          return LGH_ERR_ARG;
       }
    }
-   if (R1 * D > kSampleMaxTab || R1 * L > kSampleMaxTab)
-   {
-      set_error("lgh_sample_faces: lattice tables of R1 * D1D = %d entries, %zu bytes (at most %d entries)", R1 * D, (size_t)R1 * D * sizeof(double),
-                kSampleMaxTab);
-      return LGH_ERR_UNSUPPORTED;
-   }
+   FacesArgs a;
+   memset(&a, 0, sizeof(a));
+   LGH_PASS(lattice_tables("lgh_sample_faces", c, R1, h1 ? B_h1_lat : nullptr, der ? G_h1_lat : nullptr, l2 ? B_l2_lat : nullptr, a.Th, a.Gh, a.Tl, true));
    size_t tab_bytes, face_bytes;
    faces_lds(dim, D, L, R1, &tab_bytes, &face_bytes);
-   if (tab_bytes + face_bytes > 64 * 1024)
-   {
-      set_error("lgh_sample_faces: one face of a zone of D1D = %d on R1 = %d points needs %zu bytes of LDS", D, R1, tab_bytes + face_bytes);
-      return LGH_ERR_UNSUPPORTED;
-   }
+   LGH_PASS(lattice_lds_fits("lgh_sample_faces", "face of a zone", c, R1, tab_bytes + face_bytes));
    if (nfaces == 0 || !(h1 || l2)) { return LGH_OK; }
    // the list on the device: a buffer of the context, regrown when a longer list comes.  The copy is ordered on the
    // context's stream behind the kernel of an earlier call, which may still read the buffer (a copy from pageable host
@@ -398,11 +380,6 @@ int lgh_sample_faces(lgh_ctx *c, const double *S, const double *rho_l2, int R1, 
       c->faces_cap = nfaces;
    }
    LGH_HIP_CHECK(hipMemcpyAsync(c->faces_dev.p, faces, 2 * (size_t)nfaces * sizeof(int), hipMemcpyHostToDevice, c->stream));
-   FacesArgs a;
-   memset(&a, 0, sizeof(a));
-   if (h1) { std::copy(B_h1_lat, B_h1_lat + (size_t)R1 * D, a.Th); }
-   if (der) { std::copy(G_h1_lat, G_h1_lat + (size_t)R1 * D, a.Gh); }
-   if (l2) { std::copy(B_l2_lat, B_l2_lat + (size_t)R1 * L, a.Tl); }
    a.x = S; a.v = S + (size_t)c->H1V; a.e = S + 2 * (size_t)c->H1V; a.rho = rho_l2;
    a.xo = x_out; a.vo = v_out; a.eo = e_out; a.rhoo = rho_out; a.po = p_out;
    a.detj = detj_out; a.gradv = gradv_out; a.div = div_out; a.vort = vort_out; a.cs = cs_out; a.an = an_out;
@@ -419,7 +396,7 @@ int lgh_sample_faces(lgh_ctx *c, const double *S, const double *rho_l2, int R1, 
    a.N = c->N; a.NPt = (long)nfaces * NPF;
    a.nfaces = nfaces; a.D = D; a.L = L; a.R1 = R1;
    a.stride = (int)(face_bytes / sizeof(double));
-   a.FPB = std::min(faces_fpb(dim, R1, tab_bytes, face_bytes), nfaces);
+   a.FPB = std::min(patches_per_group(kSampleThreads, NPF, tab_bytes, face_bytes), nfaces);
    const size_t lds = tab_bytes + (size_t)a.FPB * face_bytes;
    const unsigned grid = (unsigned)ceil_div(nfaces, a.FPB);
    KtScope kt(c, LGH_KERNEL_FACES);

@@ -210,13 +210,14 @@ __global__ void __launch_bounds__(kGaugesPerGroup *kWave) gauges_k(const GaugeAr
    if (lane < LGH_GAUGE_COLS) { a.out[(size_t)g * LGH_GAUGE_COLS + lane] = mine; }
 }
 
-// gauges per workgroup and the LDS of one gauge for this context; 0 gauges: one gauge does not fit
+// gauges per workgroup - one wavefront each - and the LDS of one gauge for this context (one that does not fit kGaugeLdsBudget
+// is refused at create)
 static void gauge_shape(const lgh_ctx *c, int *per_group, size_t *gauge_bytes)
 {
    const int D = c->D1D, L = c->L1D;
    const int doubles = c->dim == 3 ? GaugeLayout<3>(D, L).total() : (c->dim == 2 ? GaugeLayout<2>(D, L).total() : GaugeLayout<1>(D, L).total());
    *gauge_bytes = (size_t)doubles * sizeof(double);
-   *per_group = (int)std::min<size_t>(kGaugesPerGroup, kGaugeLdsBudget / *gauge_bytes);
+   *per_group = patches_per_group(kGaugesPerGroup * kWave, kWave, 0, *gauge_bytes);
 }
 
 static int gauge_launch(lgh_ctx *c, const GaugeSet &s, const double *x, const double *v, const double *e, double *out, const bool mass_mode)
@@ -293,7 +294,7 @@ int lgh_gauges_create(lgh_ctx *c, int n, const int *zone, const double *Bh, cons
    int G;
    size_t bytes;
    gauge_shape(c, &G, &bytes);
-   if (G < 1)
+   if (bytes > kGaugeLdsBudget)
    {
       set_error("lgh_gauges_create: one gauge of D1D = %d needs %zu bytes of LDS (at most %zu)", D, bytes, kGaugeLdsBudget);
       return LGH_ERR_UNSUPPORTED;

@@ -236,9 +236,7 @@ static void loads_lds(const int dim, const int D, const int Q, const int L, size
 // faces per workgroup: as many as fit 256 points and 48 KB of LDS, one where they do not
 static int loads_fpb(const int dim, const int Q, const size_t tab_bytes, const size_t face_bytes)
 {
-   const size_t budget = 48 * 1024;
-   const int by_lds = tab_bytes + face_bytes <= budget ? (int)((budget - tab_bytes) / face_bytes) : 1;
-   return std::max(1, std::min(kLoadsThreads / ipow(Q, dim - 1), by_lds));
+   return patches_per_group(kLoadsThreads, ipow(Q, dim - 1), tab_bytes, face_bytes);
 }
 
 // why a context cannot take the call at all, or LGH_OK

@@ -125,27 +125,17 @@ int lgh_sample_fields(lgh_ctx *c, const double *S, const double *rho_l2, int R1,
                       double *x_out, double *v_out, double *e_out, double *rho_out, double *p_out)
 {
    LGH_CHECK_ARG(c && S && B_h1_lat && B_l2_lat);
-   if (R1 < 2 || R1 > 9)
-   {
-      set_error("lgh_sample_fields: R1 = %d lattice points per direction is out of range (2 <= R1 <= 9)", R1);
-      return LGH_ERR_ARG;
-   }
+   LGH_PASS(lattice_r1("lgh_sample_fields", R1));
    if (!rho_l2 && (rho_out || p_out))
    {
       set_error("lgh_sample_fields: %s needs the density dofs, but rho_l2 is NULL", rho_out ? "rho_out" : "p_out");
       return LGH_ERR_ARG;
    }
    const int dim = c->dim, D = c->D1D, L = c->L1D;
-   if (R1 * D > kSampleMaxTab || R1 * L > kSampleMaxTab)
-   {
-      set_error("lgh_sample_fields: lattice tables of R1 * D1D = %d entries (at most %d)", R1 * D, kSampleMaxTab);
-      return LGH_ERR_UNSUPPORTED;
-   }
-   if (!x_out && !v_out && !e_out && !rho_out && !p_out) { return LGH_OK; }
    SampleArgs a;
    memset(&a, 0, sizeof(a));
-   std::copy(B_h1_lat, B_h1_lat + (size_t)R1 * D, a.Th);
-   std::copy(B_l2_lat, B_l2_lat + (size_t)R1 * L, a.Tl);
+   LGH_PASS(lattice_tables("lgh_sample_fields", c, R1, B_h1_lat, nullptr, B_l2_lat, a.Th, nullptr, a.Tl));
+   if (!x_out && !v_out && !e_out && !rho_out && !p_out) { return LGH_OK; }
    const int NPZ = ipow(R1, dim);
    const size_t NP = (size_t)c->NE * NPZ;
    for (int k = 0; k < dim; k++)
@@ -171,14 +161,10 @@ int lgh_sample_fields(lgh_ctx *c, const double *S, const double *rho_l2, int R1,
    a.strideB = (dim >= 2) ? ipow(nmax, dim - 1) * R1 : 0;
    const int NF = a.nh + a.nl;
    const size_t zone_bytes = (size_t)NF * (a.strideA + a.strideB) * sizeof(double);
-   const size_t tab_bytes = (size_t)R1 * (D + L) * sizeof(double), budget = 48 * 1024;
-   if (zone_bytes + tab_bytes > 64 * 1024)
-   {
-      set_error("lgh_sample_fields: one zone of D1D = %d on R1 = %d points needs %zu bytes of LDS", D, R1, zone_bytes + tab_bytes);
-      return LGH_ERR_UNSUPPORTED;
-   }
+   const size_t tab_bytes = (size_t)R1 * (D + L) * sizeof(double);
+   LGH_PASS(lattice_lds_fits("lgh_sample_fields", "zone", c, R1, zone_bytes + tab_bytes));
    // several zones per workgroup where a zone's lattice is smaller than the workgroup, as far as 48 KB of LDS go
-   a.ZPB = std::max(1, std::min(std::min(kSampleThreads / NPZ, (int)((budget - tab_bytes) / zone_bytes)), c->NE));
+   a.ZPB = std::min(patches_per_group(kSampleThreads, NPZ, tab_bytes, zone_bytes), c->NE);
    const size_t lds = tab_bytes + (size_t)a.ZPB * zone_bytes;
    const unsigned grid = (unsigned)ceil_div(c->NE, a.ZPB);
    KtScope kt(c, LGH_KERNEL_SAMPLE);

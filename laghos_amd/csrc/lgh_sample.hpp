@@ -1,9 +1,12 @@
 // lgh_sample.hpp — what the lattice kernels share (lgh_sample.hip: the fields; lgh_derived.hip: their derivatives;
-// lgh_faces.hip: both on zone faces): the sizes, the sum-factorisation stages and the point expressions.  Every sum runs
+// lgh_faces.hip: both on zone faces): the sizes, the sum-factorisation stages, the point expressions and the host side of a
+// launch (the checks of R1 and of the tables, their copy, patches per workgroup, the LDS refusal).  Every sum runs
 // over its dofs in ascending order in one thread; one text for each expression is what makes the face values the bits of
 // the volume values.
 #pragma once
 #include "lgh_common.hpp"
+
+#include <algorithm>
 
 namespace lgh
 {
@@ -123,6 +126,52 @@ __device__ __forceinline__ void derived_grad(const double (&V)[DIM][DIM], const 
          vort[2 * NP + pt] = Lm[1][0] - Lm[0][1];
       }
    }
+}
+
+// ---- the host side of a lattice launch, shared by the entries; each keeps its own refusals, its name in the messages, its timer id -----
+// what refuses a lattice of R1 points per direction on this context, or LGH_OK
+inline int lattice_refusal(const lgh_ctx *c, const int R1)
+{
+   if (R1 < 2 || R1 > 9) { return LGH_ERR_ARG; }
+   return (R1 * c->D1D > kSampleMaxTab || R1 * c->L1D > kSampleMaxTab) ? LGH_ERR_UNSUPPORTED : LGH_OK;
+}
+// the range of R1, with the entry's message: among an entry's first refusals
+inline int lattice_r1(const char *who, const int R1)
+{
+   if (R1 >= 2 && R1 <= 9) { return LGH_OK; }
+   set_error("%s: R1 = %d lattice points per direction is out of range (2 <= R1 <= 9)", who, R1);
+   return LGH_ERR_ARG;
+}
+// The size of the tables, with the entry's message (`bytes`: the form that names the bytes too), behind the entry's own argument
+// checks; then the caller's tables - those that are given - copied into the kernel's argument, where they travel by value
+inline int lattice_tables(const char *who, const lgh_ctx *c, const int R1, const double *Bh, const double *Gh, const double *Bl, double *Th_arg,
+                          double *Gh_arg, double *Tl_arg, const bool bytes = false)
+{
+   const int D = c->D1D, L = c->L1D;
+   if (R1 * D > kSampleMaxTab || R1 * L > kSampleMaxTab)
+   {
+      if (!bytes) { set_error("%s: lattice tables of R1 * D1D = %d entries (at most %d)", who, R1 * D, kSampleMaxTab); }
+      else { set_error("%s: lattice tables of R1 * D1D = %d entries, %zu bytes (at most %d entries)", who, R1 * D, (size_t)R1 * D * sizeof(double), kSampleMaxTab); }
+      return LGH_ERR_UNSUPPORTED;
+   }
+   if (Bh) { std::copy(Bh, Bh + (size_t)R1 * D, Th_arg); }
+   if (Gh) { std::copy(Gh, Gh + (size_t)R1 * D, Gh_arg); }
+   if (Bl) { std::copy(Bl, Bl + (size_t)R1 * L, Tl_arg); }
+   return LGH_OK;
+}
+// patches (zones, faces, gauges) per workgroup: as many as fit `threads` threads at `pts` each and 48 KB of LDS, at least one
+inline int patches_per_group(const int threads, const int pts, const size_t tab_bytes, const size_t patch_bytes)
+{
+   const size_t budget = 48 * 1024;
+   const int by_lds = tab_bytes + patch_bytes <= budget ? (int)((budget - tab_bytes) / patch_bytes) : 1;
+   return std::max(1, std::min(threads / pts, by_lds));
+}
+// one patch (`what`: "zone", "face of a zone") with the tables has to fit the 64 KB of a workgroup
+inline int lattice_lds_fits(const char *who, const char *what, const lgh_ctx *c, const int R1, const size_t bytes)
+{
+   if (bytes <= 64 * 1024) { return LGH_OK; }
+   set_error("%s: one %s of D1D = %d on R1 = %d points needs %zu bytes of LDS", who, what, c->D1D, R1, bytes);
+   return LGH_ERR_UNSUPPORTED;
 }
 
 } // namespace lgh
