@@ -25,32 +25,7 @@
 namespace lgh
 {
 
-// ---- kernel ids: (1<<8)|(D1D<<4)|Q1D, the (order_v, order_e) pairs of the reference's 2D/3D tables -----------------
-bool kernel_id_supported_1d(int kid)
-{
-   switch (kid)
-   {
-      case 0x122: case 0x134: case 0x146: case 0x158: case 0x16A: return true;
-   }
-   return false;
-}
-
-template <int V> using IC = std::integral_constant<int, V>;
-
-// f(IC<D>, IC<Q>) for the context's kernel id
-template <class F> static int dispatch_1d(const lgh_ctx *c, F &&f)
-{
-   switch (c->kid)
-   {
-      case 0x122: return f(IC<2>(), IC<2>());
-      case 0x134: return f(IC<3>(), IC<4>());
-      case 0x146: return f(IC<4>(), IC<6>());
-      case 0x158: return f(IC<5>(), IC<8>());
-      case 0x16A: return f(IC<6>(), IC<10>());
-   }
-   set_error("Unknown kernel 0x%x", c->kid);
-   return LGH_ERR_UNSUPPORTED;
-}
+// (kernel ids: (1<<8)|(D1D<<4)|Q1D, the orders of the 2D/3D tables - visit_order, lgh_common.hpp)
 
 static int zone_grid(const lgh_ctx *c) { return ceil_div(c->NE, 256); }
 
@@ -752,7 +727,7 @@ int create_1d(const lgh_config *cfg, lgh_ctx *c)
 // the Jacobi diagonal of the H1 mass and the factors of the zone mass matrices, from the current mass data
 int mass_changed_1d(lgh_ctx *c)
 {
-   return dispatch_1d(c, [&](auto Dc, auto Qc) {
+   return visit_order(c->kid, [&](auto Dc, auto Qc, auto) {
       constexpr int D = decltype(Dc)::value, Q = decltype(Qc)::value;
       hipLaunchKernelGGL((h1_diag_e_1d_k<D, Q>), dim3(zone_grid(c)), dim3(256), 0, c->stream, c->NE, c->B, c->massD, c->YE);
       hipLaunchKernelGGL(gather_1d_k, dim3(ceil_div(c->N, 256)), dim3(256), 0, c->stream, c->N, c->t_off, c->t_idx, c->YE,
@@ -768,7 +743,7 @@ int mass_changed_1d(lgh_ctx *c)
 
 int setup_1d(lgh_ctx *c, const double *x0, const double *rho0_l2, const double *rho0_q, double *volume)
 {
-   const int rc = dispatch_1d(c, [&](auto Dc, auto Qc) {
+   const int rc = visit_order(c->kid, [&](auto Dc, auto Qc, auto) {
       constexpr int D = decltype(Dc)::value, Q = decltype(Qc)::value;
       hipLaunchKernelGGL((setup_1d_k<D, Q>), dim3(zone_grid(c)), dim3(256), 0, c->stream, c->NE, c->h1map, c->G, c->Bl, c->W,
                          x0, rho0_l2, rho0_q, c->Jac0inv, c->rho0DetJ0w, c->massD, c->partials, c->tickets, c->scal);
@@ -787,7 +762,7 @@ int setup_1d(lgh_ctx *c, const double *x0, const double *rho0_l2, const double *
 
 int force_mult_1d(lgh_ctx *c, const double *x_l2, double *y_h1)
 {
-   return dispatch_1d(c, [&](auto Dc, auto Qc) {
+   return visit_order(c->kid, [&](auto Dc, auto Qc, auto) {
       constexpr int D = decltype(Dc)::value, Q = decltype(Qc)::value;
       hipLaunchKernelGGL((force_e_1d_k<D, Q>), dim3(zone_grid(c)), dim3(256), 0, c->stream, c->NE, c->G, c->Bl, c->stressJinvT,
                          x_l2, c->YE);
@@ -800,7 +775,7 @@ int force_mult_1d(lgh_ctx *c, const double *x_l2, double *y_h1)
 
 int force_mult_t_1d(lgh_ctx *c, const double *v_h1, double *y_l2)
 {
-   return dispatch_1d(c, [&](auto Dc, auto Qc) {
+   return visit_order(c->kid, [&](auto Dc, auto Qc, auto) {
       constexpr int D = decltype(Dc)::value, Q = decltype(Qc)::value;
       hipLaunchKernelGGL((force_t_1d_k<D, Q>), dim3(zone_grid(c)), dim3(256), 0, c->stream, c->NE, c->h1map, c->G, c->Bl,
                          c->stressJinvT, v_h1, y_l2);
@@ -811,7 +786,7 @@ int force_mult_t_1d(lgh_ctx *c, const double *v_h1, double *y_l2)
 
 int mass_apply_1d(lgh_ctx *c, int space, const double *x, double *y, bool eliminate)
 {
-   return dispatch_1d(c, [&](auto Dc, auto Qc) {
+   return visit_order(c->kid, [&](auto Dc, auto Qc, auto) {
       constexpr int D = decltype(Dc)::value, Q = decltype(Qc)::value;
       if (space == LGH_SPACE_H1)
       {
@@ -831,7 +806,7 @@ int mass_apply_1d(lgh_ctx *c, int space, const double *x, double *y, bool elimin
 
 int l2_solve_local_1d(lgh_ctx *c, const double *b, double *x)
 {
-   return dispatch_1d(c, [&](auto Dc, auto Qc) {
+   return visit_order(c->kid, [&](auto Dc, auto Qc, auto) {
       constexpr int D = decltype(Dc)::value, Q = decltype(Qc)::value;
       hipLaunchKernelGGL((energy_solve_1d_k<D, Q, false>), dim3(zone_grid(c)), dim3(256), 0, c->stream, c->NE, c->h1map, c->G,
                          c->Bl, c->stressJinvT, (const double *)nullptr, (const double *)nullptr, b, (double *)nullptr, c->me_fac, x);
@@ -865,7 +840,7 @@ int cg_1d(lgh_ctx *c, int space, const double *b, double *x, double rel_tol, int
    a.max_iter = max_iter;
    a.x_zero = (x_is_zero || !h1) ? 1 : 0; // (the L2 solve starts from x = 0: CG_EMass.iterative_mode = false)
    a.cgs = c->cgs;
-   const int rc = dispatch_1d(c, [&](auto Dc, auto Qc) {
+   const int rc = visit_order(c->kid, [&](auto Dc, auto Qc, auto) {
       constexpr int D = decltype(Dc)::value, Q = decltype(Qc)::value;
       if (h1) { hipLaunchKernelGGL((cg1d_k<D, Q, true>), dim3(1), dim3(256), 0, c->stream, a); }
       else { hipLaunchKernelGGL((cg1d_k<D - 1, Q, false>), dim3(1), dim3(256), 0, c->stream, a); }
@@ -888,7 +863,7 @@ int qupdate_1d(lgh_ctx *c, const double *S)
    a.G = c->G; a.Bl = c->Bl; a.W = c->W; a.gamma = c->gamma; a.rdw = c->rho0DetJ0w; a.Jac0inv = c->Jac0inv; a.S = S;
    a.h0 = c->h0; a.cfl = c->cfl; a.h1order = c->h1order;
    a.sJ = c->stressJinvT; a.partials = c->partials; a.ticket = c->tickets; a.dt_est = c->dt_est_dev;
-   const int rc = dispatch_1d(c, [&](auto Dc, auto Qc) {
+   const int rc = visit_order(c->kid, [&](auto Dc, auto Qc, auto) {
       constexpr int D = decltype(Dc)::value, Q = decltype(Qc)::value;
       hipLaunchKernelGGL((qupdate_1d_k<D, Q>), dim3(zone_grid(c)), dim3(256), 0, c->stream, a);
       LGH_HIP_CHECK(hipGetLastError());
@@ -931,7 +906,7 @@ int solve_energy_1d(lgh_ctx *c, const double *v_h1, double *de, double *e_rhs, c
 {
    RoctxRange range("SolveEnergy-MeInv"); // :508
    timer_start(c);
-   const int rc = dispatch_1d(c, [&](auto Dc, auto Qc) {
+   const int rc = visit_order(c->kid, [&](auto Dc, auto Qc, auto) {
       constexpr int D = decltype(Dc)::value, Q = decltype(Qc)::value;
       hipLaunchKernelGGL((energy_solve_1d_k<D, Q, true>), dim3(zone_grid(c)), dim3(256), 0, c->stream, c->NE, c->h1map, c->G, c->Bl,
                          c->stressJinvT, v_h1, e_source, (const double *)nullptr, e_rhs, c->me_fac, de);
@@ -947,7 +922,7 @@ int solve_energy_1d(lgh_ctx *c, const double *v_h1, double *de, double *e_rhs, c
 
 int density_1d(lgh_ctx *c, const double *x_h1, double *rho_l2)
 {
-   const int rc = dispatch_1d(c, [&](auto Dc, auto Qc) {
+   const int rc = visit_order(c->kid, [&](auto Dc, auto Qc, auto) {
       constexpr int D = decltype(Dc)::value, Q = decltype(Qc)::value;
       hipLaunchKernelGGL((density_1d_k<D, Q>), dim3(zone_grid(c)), dim3(256), 0, c->stream, c->NE, c->h1map, c->G, c->Bl, c->W,
                          x_h1, c->rho0DetJ0w, rho_l2);
@@ -961,7 +936,7 @@ int density_1d(lgh_ctx *c, const double *x_h1, double *rho_l2)
 
 int energy_1d(lgh_ctx *c, int which, const double *vec, double *result)
 {
-   const int rc = dispatch_1d(c, [&](auto Dc, auto Qc) {
+   const int rc = visit_order(c->kid, [&](auto Dc, auto Qc, auto) {
       constexpr int D = decltype(Dc)::value, Q = decltype(Qc)::value;
       if (which == 0)
       {
@@ -999,7 +974,7 @@ int sedov_density_error_1d(lgh_ctx *c, const double *x_h1, const double *rho_l2,
    LGH_HIP_CHECK(hipMemcpy(buf, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
    const double *dw = buf, *dB = dw + n1d, *dG = dB + (size_t)n1d * D, *dBl = dG + (size_t)n1d * D;
    double *r = buf + tab.size(), *rh = r + np, *wd = rh + np, *rx = wd + np, *vx = rx + np, *px = vx + np;
-   int rc = dispatch_1d(c, [&](auto Dc, auto) {
+   int rc = visit_order(c->kid, [&](auto Dc, auto, auto) {
       constexpr int Dt = decltype(Dc)::value;
       hipLaunchKernelGGL((sedov_points_1d_k<Dt>), dim3(ceil_div((long)np, 256)), dim3(256), 0, c->stream, c->NE, n1d, c->h1map,
                          dB, dG, dBl, dw, x_h1, rho_l2, origin[0], r, rh, wd);

@@ -118,7 +118,7 @@ int halo_sum(lgh_ctx *c, double *v, int ncomp, double *extra, int nextra, bool p
                          extra);
       LGH_HIP_CHECK(hipGetLastError());
    }
-   LGH_COMM_TRY(cm->transport->exchange_blocks(c, ch, ncomp, nx));
+   LGH_PASS(cm->transport->exchange_blocks(c, ch, ncomp, nx));
    const long ncomb = std::max((long)t.n_shared * ncomp, (long)nx);
    hipLaunchKernelGGL(halo_combine_k, dim3(ceil_div(ncomb, 256)), dim3(256), 0,
                       c->stream, t.n_shared, ncomp, c->N, l_sh_node, t.sh_off.p, t.sh_src.p, t.pos.p,
@@ -183,7 +183,7 @@ int comm_word_peers(lgh_ctx *c, int nwords, const long long **peers, int *n_peer
    if (cm->wordcap != nwords || cm->wordnbr != n_nbr) // (sized by BOTH factors)
    {
       cm->wordcap = 0;
-      LGH_COMM_TRY(cm->wordbuf.alloc((size_t)n_nbr * nwords, true));
+      LGH_PASS(cm->wordbuf.alloc((size_t)n_nbr * nwords, true));
       cm->wordcap = nwords;
       cm->wordnbr = n_nbr;
    }
@@ -234,7 +234,7 @@ int allreduce_dev_n(lgh_ctx *c, double *dev, long count, int op)
 // at least one element is allocated: an empty list still has an address the kernels may be handed
 template <typename T> static int upload_list(DevPtr<T> &d, const std::vector<T> &h)
 {
-   LGH_COMM_TRY(d.alloc(std::max<size_t>(h.size(), 1)));
+   LGH_PASS(d.alloc(std::max<size_t>(h.size(), 1)));
    if (!h.empty()) { LGH_HIP_CHECK(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice)); }
    return LGH_OK;
 }
@@ -304,12 +304,12 @@ static int build_tables(const lgh_ctx *c, const bool channel2, const int n_nbr, 
          off[u + 1] = (int)src.size();
       }
       t.n_shared = (int)uniq.size();
-      LGH_COMM_TRY(upload_list(t.sh_node, uniq));
-      LGH_COMM_TRY(upload_list(t.sh_off, off));
-      LGH_COMM_TRY(upload_list(t.sh_src, src));
+      LGH_PASS(upload_list(t.sh_node, uniq));
+      LGH_PASS(upload_list(t.sh_off, off));
+      LGH_PASS(upload_list(t.sh_src, src));
       std::vector<uint8_t> hm((size_t)c->N, 0);
       for (int n : uniq) { hm[n] = 1; }
-      LGH_COMM_TRY(upload_list(t.hmask, hm));
+      LGH_PASS(upload_list(t.hmask, hm));
    }
    {
       std::vector<int> pos(std::max(tot, 1)), cnt(std::max(tot, 1));
@@ -321,15 +321,15 @@ static int build_tables(const lgh_ctx *c, const bool channel2, const int n_nbr, 
             cnt[t.nbr_off[k] + i] = nbr_count[k];
          }
       }
-      LGH_COMM_TRY(upload_list(t.pos, pos));
-      LGH_COMM_TRY(upload_list(t.cnt, cnt));
+      LGH_PASS(upload_list(t.pos, pos));
+      LGH_PASS(upload_list(t.cnt, cnt));
    }
-   LGH_COMM_TRY(upload_list(t.nodes, all));
+   LGH_PASS(upload_list(t.nodes, all));
    t.bufsize = 3 * std::max(tot, 1) + kHaloSlack * n_nbr;
    for (int ch = 0; ch < (channel2 ? 2 : 1); ch++)
    {
-      LGH_COMM_TRY(t.sendbuf[ch].alloc((size_t)t.bufsize, true));
-      LGH_COMM_TRY(t.recvbuf[ch].alloc((size_t)t.bufsize, true));
+      LGH_PASS(t.sendbuf[ch].alloc((size_t)t.bufsize, true));
+      LGH_PASS(t.recvbuf[ch].alloc((size_t)t.bufsize, true));
    }
    LGH_HIP_CHECK(hipStreamSynchronize(nullptr)); // the fills run asynchronously on the null stream
    // the rank -> neighbour map of the piggy-backed scalars; all-pairs: every other rank is a neighbour
@@ -376,9 +376,9 @@ int lgh_comm_init(lgh_ctx *c, int nranks, int rank, const char unique_id[128])
    }
    if (!c->comm) { c->comm.reset(new Comm()); }
    OpenedTransport o;
-   if (memcmp(unique_id, "LGHSHM", 6) == 0) { LGH_COMM_TRY(open_shm(c, nranks, rank, unique_id, o)); } // cross-process loopback (bench.py --transport shm, tests)
-   else if (memcmp(unique_id, "LGHLOCAL", 8) == 0) { LGH_COMM_TRY(open_local(c, nranks, rank, unique_id, o)); } // in-process loopback (tests)
-   else { LGH_COMM_TRY(open_rccl(c, nranks, rank, unique_id, o)); }
+   if (memcmp(unique_id, "LGHSHM", 6) == 0) { LGH_PASS(open_shm(c, nranks, rank, unique_id, o)); } // cross-process loopback (bench.py --transport shm, tests)
+   else if (memcmp(unique_id, "LGHLOCAL", 8) == 0) { LGH_PASS(open_local(c, nranks, rank, unique_id, o)); } // in-process loopback (tests)
+   else { LGH_PASS(open_rccl(c, nranks, rank, unique_id, o)); }
    c->comm->transport = std::move(o.transport);
    c->comm->channel2 = o.channel2;
    c->nranks = nranks;
@@ -413,13 +413,13 @@ int lgh_comm_set_neighbors(lgh_ctx *c, int n_nbr, const int *nbr_rank, const int
    HaloTables t;
    std::vector<int> rank_src;
    const int rc_local = build_tables(c, cm->channel2, n_nbr, nbr_rank, nbr_count, nbr_nodes, t, rank_src);
-   if (cm->transport) { LGH_COMM_TRY(cm->transport->publish_tables(c->rank, rc_local ? nullptr : &t)); }
+   if (cm->transport) { LGH_PASS(cm->transport->publish_tables(c->rank, rc_local ? nullptr : &t)); }
    // the message sizes depend on it: every rank must come to the same decision (in a 3x1x1 partition
    // only the middle rank sees all others); a local failure travels in the same MIN-reduction
    if (c->multi != 0 && cm->transport)
    {
       double flag = rc_local ? -1.0 : (t.allpairs ? 1.0 : 0.0);
-      LGH_COMM_TRY(lgh_allreduce(c, &flag, 1));
+      LGH_PASS(lgh_allreduce(c, &flag, 1));
       if (flag < 0.0)
       {
          if (!rc_local) { set_error("lgh_comm_set_neighbors failed on another rank"); }
@@ -428,9 +428,9 @@ int lgh_comm_set_neighbors(lgh_ctx *c, int n_nbr, const int *nbr_rank, const int
       t.allpairs = (flag > 0.5);
    }
    else if (rc_local) { return rc_local; }
-   LGH_COMM_TRY(upload_list(t.d_base, t.nbr_base));
-   LGH_COMM_TRY(upload_list(t.d_cnt, t.nbr_count));
-   LGH_COMM_TRY(upload_list(t.rank_src, rank_src));
+   LGH_PASS(upload_list(t.d_base, t.nbr_base));
+   LGH_PASS(upload_list(t.d_cnt, t.nbr_count));
+   LGH_PASS(upload_list(t.rank_src, rank_src));
    // Publication: the tables change hands whole (the previous ones leave with t), and what was built for them goes -
    // the peer buffer of exchange_words, sized by the neighbour count, and the flag bytes of the node kernel K2
    cm->tab = std::move(t);
@@ -493,8 +493,8 @@ int lgh_test_rccl_self_sendrecv(lgh_ctx *c, int n, double *max_abs_diff)
    std::vector<double> h(2 * (size_t)n, 0.0);
    for (int i = 0; i < n; i++) { h[i] = 1.0 + 0.5 * i; }
    DevPtr<double> buf;
-   LGH_COMM_TRY(buf.upload(h.data(), h.size()));
-   LGH_COMM_TRY(rccl_self_sendrecv(c, buf, n));
+   LGH_PASS(buf.upload(h.data(), h.size()));
+   LGH_PASS(rccl_self_sendrecv(c, buf, n));
    LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
    LGH_HIP_CHECK(hipMemcpy(h.data(), buf, h.size() * sizeof(double), hipMemcpyDeviceToHost));
    double d = 0.0;

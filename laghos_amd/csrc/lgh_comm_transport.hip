@@ -148,7 +148,7 @@ struct RcclTransport : Transport
 static int negotiate_second_channel(lgh_ctx *c, int nranks, int rank, RcclTransport &t, bool *channel2)
 {
    DevPtr<char> dbuf;
-   LGH_COMM_TRY(dbuf.alloc(128 + 2 * sizeof(double)));
+   LGH_PASS(dbuf.alloc(128 + 2 * sizeof(double)));
    char hbuf[128 + sizeof(double)];
    ncclUniqueId id2;
    memset(&id2, 0, sizeof(id2));
@@ -175,7 +175,7 @@ static int negotiate_second_channel(lgh_ctx *c, int nranks, int rank, RcclTransp
 
 int open_rccl(lgh_ctx *c, int nranks, int rank, const char unique_id[128], OpenedTransport &out)
 {
-   LGH_COMM_TRY(load_nccl());
+   LGH_PASS(load_nccl());
    LGH_HIP_CHECK(hipSetDevice(c->device));
    auto t = std::make_unique<RcclTransport>();
    ncclUniqueId id;
@@ -183,14 +183,14 @@ int open_rccl(lgh_ctx *c, int nranks, int rank, const char unique_id[128], Opene
    LGH_NCCL_CHECK(g_nccl.CommInitRank(&t->comm[0], nranks, id, rank));
    out.multi = (nranks > 1 || c->sw.force_multi) ? 1 : 0;
    const bool want2 = c->sw.comm2 >= 0 ? c->sw.comm2 == 1 : (nranks == 1);
-   if (out.multi && g_nccl.Broadcast && want2) { LGH_COMM_TRY(negotiate_second_channel(c, nranks, rank, *t, &out.channel2)); }
+   if (out.multi && g_nccl.Broadcast && want2) { LGH_PASS(negotiate_second_channel(c, nranks, rank, *t, &out.channel2)); }
    out.transport = std::move(t);
    return LGH_OK;
 }
 
 int rccl_unique_id(char id_out[128])
 {
-   LGH_COMM_TRY(load_nccl());
+   LGH_PASS(load_nccl());
    ncclUniqueId id;
    LGH_NCCL_CHECK(g_nccl.GetUniqueId(&id));
    memcpy(id_out, id.internal, 128);
@@ -230,9 +230,9 @@ struct Loopback : Transport
    template <class Post, class Fetch> int bracket(lgh_ctx *c, const char *what, const char *hint, Post post, Fetch fetch)
    {
       LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
-      LGH_COMM_TRY(post());
-      LGH_COMM_TRY(meet(what, hint));
-      LGH_COMM_TRY(fetch());
+      LGH_PASS(post());
+      LGH_PASS(meet(what, hint));
+      LGH_PASS(fetch());
       return meet(what);
    }
    // where a peer keeps the block of rank `me` (index into the peer's neighbour list); -1: it has none, or of another size
@@ -260,7 +260,7 @@ struct Loopback : Transport
       // ordered with the kernels of the stream (observed: stale sums, run-to-run different
       // results), so drain the stream first and copy synchronously
       double mine[8], res[8];
-      LGH_COMM_TRY(bracket(c, "all-reduce", "",
+      LGH_PASS(bracket(c, "all-reduce", "",
          [&]() -> int {
             LGH_HIP_CHECK(hipMemcpy(mine, dev, count * sizeof(double), hipMemcpyDeviceToHost));
             for (int i = 0; i < count; i++) { slots()[(size_t)rank * 8 + i] = mine[i]; }
@@ -585,7 +585,7 @@ struct ShmTransport : Loopback
 int open_shm(lgh_ctx *c, int nranks, int rank, const char unique_id[128], OpenedTransport &out)
 {
    auto t = std::make_unique<ShmTransport>();
-   LGH_COMM_TRY(t->g.open(unique_id, nranks, rank));
+   LGH_PASS(t->g.open(unique_id, nranks, rank));
    t->n = nranks;
    t->rank = rank;
    out.transport = std::move(t);

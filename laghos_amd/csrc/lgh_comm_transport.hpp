@@ -8,8 +8,6 @@
 namespace lgh
 {
 
-#define LGH_COMM_TRY(call) do { const int rc_ = (call); if (rc_) { return rc_; } } while (0) // (an LGH_* status: passed on)
-
 constexpr int kHaloSlack = 4; // doubles of room behind every neighbour's block (<= 4 scalars: (d, A d) of the three velocity components and, in lockstep, of the energy CG)
 
 // The neighbour tables of one lgh_comm_set_neighbors call: built into a local object (build_tables, lgh_comm.hip) and

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/laghos_hip.h"
@@ -363,6 +364,42 @@ struct lgh_ctx : lgh::CtxHandles
 
 namespace lgh
 {
+
+// ---- the orders: THE table of the kernel ids, (dim << 8) | (D1D << 4) | Q1D with dim 1, 2, 3 and the five rows below -----------
+// The (order_v, order_e) pairs of the reference's 2D / 3D tables (assembly.cpp:534-548, :944-956; laghos_solver.cpp:1387-1396);
+// Q5Q4 is an extension the reference does not instantiate.  D, Q, L: the 1-D sizes of the H1 basis, the quadrature rule and the
+// L2 basis (L = D - 1: lgh_create).  Every order-templated kernel family picks its instantiation through visit_order; the
+// dimension stays a runtime branch inside the callable.
+template <int V> using IC = std::integral_constant<int, V>;
+template <class F, class G> auto order_row(const int kid, F &&f, G &&none)
+{
+   switch (kid & 0xFF)
+   {
+      case 0x22: return f(IC<2>(), IC<2>(), IC<1>());  // Q1Q0
+      case 0x34: return f(IC<3>(), IC<4>(), IC<2>());  // Q2Q1
+      case 0x46: return f(IC<4>(), IC<6>(), IC<3>());  // Q3Q2
+      case 0x58: return f(IC<5>(), IC<8>(), IC<4>());  // Q4Q3
+      case 0x6A: return f(IC<6>(), IC<10>(), IC<5>()); // Q5Q4
+   }
+   return none();
+}
+inline int unknown_kernel(const int kid)
+{
+   set_error("Unknown kernel 0x%x", kid);
+   return LGH_ERR_UNSUPPORTED;
+}
+// f(IC<D>, IC<Q>, IC<L>) for the order of kernel id `kid`: what f returns, an LGH_* status; any other id is the one failure
+template <class F> int visit_order(const int kid, F &&f) { return order_row(kid, f, [kid] { return unknown_kernel(kid); }); }
+// ... of a 2D / 3D context: a 1D context has kernels of its own (lgh_1d.hip), to the families here its id is unknown as well
+template <class F> int visit_order_2d3d(const lgh_ctx *c, F &&f) { return c->dim == 1 ? unknown_kernel(c->kid) : visit_order(c->kid, f); }
+// one of the fifteen ids (launches nothing, sets no error)
+inline bool order_supported(const int kid)
+{
+   return kid >= 0x100 && kid < 0x400 && order_row(kid, [](auto, auto, auto) { return true; }, [] { return false; });
+}
+// zones per workgroup of the kernels whose threads are the (qx, qy) columns of their zones: the force kernels, the column
+// forms of the mass operators and of K1, the 2-D point form of the quadrature update
+constexpr int zones_per_wg(const int Q) { return (256 / (Q * Q)) > 0 ? (256 / (Q * Q)) : 1; }
 
 // ---- wave / block reductions (wave64, DPP) ----------------------------------
 // Workgroups here are Q*Q*NEB threads, not always a multiple of 64, so the last wave may be partial (`nact` live
@@ -743,7 +780,6 @@ int no_1d(const lgh_ctx *c, const char *who);   // LGH_OK: not a 1D context (ent
 int create_common(const lgh_config *cfg, lgh_ctx *c, std::vector<int> &t_off, std::vector<int> &t_idx); // what create_1d and the 2D/3D create share
 
 // ---- lgh_1d.hip: the 1D path (the entry points send a context with dim == 1 there; the 2D/3D kernels never see one)
-bool kernel_id_supported_1d(int kid);
 int create_1d(const lgh_config *cfg, lgh_ctx *c);
 int setup_1d(lgh_ctx *c, const double *x0, const double *rho0_l2, const double *rho0_q, double *volume);
 int mass_changed_1d(lgh_ctx *c); // Jacobi diagonal and zone mass factors from the current mass data

@@ -83,17 +83,6 @@ int create_common(const lgh_config *cfg, lgh_ctx *c, std::vector<int> &t_off, st
    return ctx_buffer(c->dt_est_dev, infs.size(), infs.data());
 }
 
-static bool kernel_id_supported(int id)
-{
-   switch (id)
-   {
-      case 0x222: case 0x234: case 0x246: case 0x258: case 0x26A:
-      case 0x322: case 0x334: case 0x346: case 0x358: case 0x36A:
-         return true;
-   }
-   return false;
-}
-
 // C_F = 3 cG cB^2, cB = max_d sum_q |B[q, d]|, cG likewise from G.  An output of F.1 is the sum over the three reference
 // directions gd and the points q of stressJinvT w detJ (q, gd, c) * T_z[qz, dz] T_y[qy, dy] T_x[qx, dx], T = G in direction gd
 // and B in the other two: its absolute value is at most max_q|stressJinvT w detJ| times the sum of the three products of
@@ -253,7 +242,8 @@ int lgh_create(const lgh_config *cfg, lgh_ctx **out)
    // MFEM_VERIFY(L1D==D1D-1) (laghos_assembly.cpp:533, :943)
    if (cfg->L1D != cfg->D1D - 1) { set_error("L1D!=D1D-1"); return LGH_ERR_UNSUPPORTED; }
    const int kid = (cfg->dim << 8) | (cfg->D1D << 4) | cfg->Q1D;
-   if (!(cfg->dim == 1 ? kernel_id_supported_1d(kid) : kernel_id_supported(kid))) { set_error("Unknown kernel 0x%x", kid); return LGH_ERR_UNSUPPORTED; }
+   const bool packed = (cfg->D1D & ~0xF) == 0 && (cfg->Q1D & ~0xF) == 0; // (four bits each: no other sizes alias one of the fifteen ids)
+   if (!packed || !order_supported(kid)) { return unknown_kernel(kid); }
    int ndev = 0;
    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
    {

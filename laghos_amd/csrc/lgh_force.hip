@@ -554,60 +554,29 @@ int h1_transpose_gather(lgh_ctx *c, int ncomp, const double *YE, double *yL)
 }
 
 // ---- dispatch: same ids as the reference tables (assembly.cpp:534-548, :944-956)
-static int unknown_kernel(int id)
-{
-   set_error("Unknown kernel 0x%x", id);
-   return LGH_ERR_UNSUPPORTED;
-}
-
-template <int D, int Q, int L> constexpr int neb3() { return (256 / (Q * Q)) > 0 ? (256 / (Q * Q)) : 1; }
-
-#define LGH_LAUNCH_3D(K, D_, Q_, L_, ...)                                                     \
-   {                                                                                          \
-      constexpr int NEB_ = neb3<D_, Q_, L_>();                                                \
-      hipLaunchKernelGGL((K<D_, Q_, L_, NEB_>), dim3(ceil_div(c->NE, NEB_)),                  \
-                         dim3(Q_ * Q_ * NEB_), 0, c->stream, __VA_ARGS__);                    \
-   }
-
+// (0x36A is not instantiated by the reference (assembly.cpp:544-547); extension.)
 int force_mult_E(lgh_ctx *c, const double *sJit, const double *xE, double *yE)
 {
-   switch (c->kid)
-   {
-      case 0x222: LGH_LAUNCH_3D(force_mult_2d, 2, 2, 1, c->NE, c->Bl, c->B, c->G, sJit, xE, yE); break;
-      case 0x234: LGH_LAUNCH_3D(force_mult_2d, 3, 4, 2, c->NE, c->Bl, c->B, c->G, sJit, xE, yE); break;
-      case 0x246: LGH_LAUNCH_3D(force_mult_2d, 4, 6, 3, c->NE, c->Bl, c->B, c->G, sJit, xE, yE); break;
-      case 0x258: LGH_LAUNCH_3D(force_mult_2d, 5, 8, 4, c->NE, c->Bl, c->B, c->G, sJit, xE, yE); break;
-      case 0x26A: LGH_LAUNCH_3D(force_mult_2d, 6, 10, 5, c->NE, c->Bl, c->B, c->G, sJit, xE, yE); break;
-      case 0x322: LGH_LAUNCH_3D(force_mult_3d, 2, 2, 1, c->NE, c->Bl, c->B, c->G, sJit, xE, yE); break;
-      case 0x334: LGH_LAUNCH_3D(force_mult_3d, 3, 4, 2, c->NE, c->Bl, c->B, c->G, sJit, xE, yE); break;
-      case 0x346: LGH_LAUNCH_3D(force_mult_3d, 4, 6, 3, c->NE, c->Bl, c->B, c->G, sJit, xE, yE); break;
-      case 0x358: LGH_LAUNCH_3D(force_mult_3d, 5, 8, 4, c->NE, c->Bl, c->B, c->G, sJit, xE, yE); break;
-      // 0x36A is not instantiated by the reference (assembly.cpp:544-547); extension.
-      case 0x36A: LGH_LAUNCH_3D(force_mult_3d, 6, 10, 5, c->NE, c->Bl, c->B, c->G, sJit, xE, yE); break;
-      default: return unknown_kernel(c->kid);
-   }
-   LGH_HIP_CHECK(hipGetLastError());
-   return LGH_OK;
+   return visit_order_2d3d(c, [&](auto Dc, auto Qc, auto Lc) {
+      constexpr int D = Dc, Q = Qc, L = Lc, NEB = zones_per_wg(Q);
+      const dim3 grid(ceil_div(c->NE, NEB)), block(Q * Q * NEB);
+      if (c->dim == 2) { hipLaunchKernelGGL((force_mult_2d<D, Q, L, NEB>), grid, block, 0, c->stream, c->NE, c->Bl, c->B, c->G, sJit, xE, yE); }
+      else { hipLaunchKernelGGL((force_mult_3d<D, Q, L, NEB>), grid, block, 0, c->stream, c->NE, c->Bl, c->B, c->G, sJit, xE, yE); }
+      LGH_HIP_CHECK(hipGetLastError());
+      return LGH_OK;
+   });
 }
 
 static int force_mult_t_any(lgh_ctx *c, const double *sJit, const double *v, const int *map, double *y, const int *guard)
 {
-   switch (c->kid)
-   {
-      case 0x222: LGH_LAUNCH_3D(force_mult_t_2d, 2, 2, 1, c->NE, c->N, c->Bl, c->B, c->G, sJit, v, map, y, guard); break;
-      case 0x234: LGH_LAUNCH_3D(force_mult_t_2d, 3, 4, 2, c->NE, c->N, c->Bl, c->B, c->G, sJit, v, map, y, guard); break;
-      case 0x246: LGH_LAUNCH_3D(force_mult_t_2d, 4, 6, 3, c->NE, c->N, c->Bl, c->B, c->G, sJit, v, map, y, guard); break;
-      case 0x258: LGH_LAUNCH_3D(force_mult_t_2d, 5, 8, 4, c->NE, c->N, c->Bl, c->B, c->G, sJit, v, map, y, guard); break;
-      case 0x26A: LGH_LAUNCH_3D(force_mult_t_2d, 6, 10, 5, c->NE, c->N, c->Bl, c->B, c->G, sJit, v, map, y, guard); break;
-      case 0x322: LGH_LAUNCH_3D(force_mult_t_3d, 2, 2, 1, c->NE, c->N, c->Bl, c->B, c->G, sJit, v, map, y, guard); break;
-      case 0x334: LGH_LAUNCH_3D(force_mult_t_3d, 3, 4, 2, c->NE, c->N, c->Bl, c->B, c->G, sJit, v, map, y, guard); break;
-      case 0x346: LGH_LAUNCH_3D(force_mult_t_3d, 4, 6, 3, c->NE, c->N, c->Bl, c->B, c->G, sJit, v, map, y, guard); break;
-      case 0x358: LGH_LAUNCH_3D(force_mult_t_3d, 5, 8, 4, c->NE, c->N, c->Bl, c->B, c->G, sJit, v, map, y, guard); break;
-      case 0x36A: LGH_LAUNCH_3D(force_mult_t_3d, 6, 10, 5, c->NE, c->N, c->Bl, c->B, c->G, sJit, v, map, y, guard); break;
-      default: return unknown_kernel(c->kid);
-   }
-   LGH_HIP_CHECK(hipGetLastError());
-   return LGH_OK;
+   return visit_order_2d3d(c, [&](auto Dc, auto Qc, auto Lc) {
+      constexpr int D = Dc, Q = Qc, L = Lc, NEB = zones_per_wg(Q);
+      const dim3 grid(ceil_div(c->NE, NEB)), block(Q * Q * NEB);
+      if (c->dim == 2) { hipLaunchKernelGGL((force_mult_t_2d<D, Q, L, NEB>), grid, block, 0, c->stream, c->NE, c->N, c->Bl, c->B, c->G, sJit, v, map, y, guard); }
+      else { hipLaunchKernelGGL((force_mult_t_3d<D, Q, L, NEB>), grid, block, 0, c->stream, c->NE, c->N, c->Bl, c->B, c->G, sJit, v, map, y, guard); }
+      LGH_HIP_CHECK(hipGetLastError());
+      return LGH_OK;
+   });
 }
 // guard: device flag; the kernel does nothing when it is 0 (lgh_solve_energy: the fused F^T v is current)
 int force_mult_t_L(lgh_ctx *c, const double *sJit, const double *v_h1, double *y_l2, const int *guard)

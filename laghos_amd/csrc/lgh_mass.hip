@@ -529,12 +529,6 @@ mass_apply_2d(const MassArgs a)
    }
 }
 
-static int unknown_kernel(int id)
-{
-   set_error("Unknown kernel 0x%x", id);
-   return LGH_ERR_UNSUPPORTED;
-}
-
 // ---- L2 mass apply, Kronecker form (3D; compact mass data on a tensor-product rule: lgh_create's 1-D mass tile M1l)
 // B^T diag(s_e w (x) w (x) w) B = s_e M1 (x) M1 (x) M1 with M1 = B^T diag(w) B (L x L): three contractions of L on the
 // element's L^3 dofs - 3 L^4 FMAs instead of ~2 (L^3 Q + L^2 Q^2 + L Q^3) + Q^3 through the quadrature points (L = 5,
@@ -738,7 +732,6 @@ mass_apply_l2_kron(const MassArgs a)
    }
 }
 
-template <int Q> constexpr int neb_for() { return (256 / (Q * Q)) > 0 ? (256 / (Q * Q)) : 1; }
 static bool l2_one_round(const lgh_ctx *c)
 {
    return c->L1D >= 5 && c->sw.l2_neb;
@@ -749,13 +742,12 @@ static bool l2_one_round(const lgh_ctx *c)
 // 0 = the column form.  `compact`: whether the kernel reads one factor per element instead of the NQ-entry table.
 static int l2_mass_kernel(lgh_ctx *c, int *form, int *compact)
 {
-   const int id = (c->dim << 8) | (c->L1D << 4) | c->Q1D;
    const double *Dq, *Se;
    int dqs = 1;
    *form = 0;
    *compact = 0;
    const bool kron_ok = c->dim == 3 && c->M1l && c->w1d && c->L1D <= 5;
-   const bool plane_ok = c->b_l2_sym && (id == 0x336 || id == 0x348 || id == 0x35A) && c->sw.l2_plane; // (LGH_L2_PLANE=0: column form)
+   const bool plane_ok = c->b_l2_sym && c->dim == 3 && c->L1D >= 3 && c->sw.l2_plane; // (LGH_L2_PLANE=0: column form)
    if (kron_ok || plane_ok)
    {
       const int rc = mass_data(c, &Dq, &dqs, &Se);
@@ -772,98 +764,58 @@ int l2_mass_form(lgh_ctx *c, int *form, int *compact) { return l2_mass_kernel(c,
 // instead of sixteen (400 rows: a second round with 144 of 256 threads, three workgroups per CU): 53 -> 46 us per apply at
 // config 5, the leg 501 -> 534 (profiles/r6_l2_neb.txt); at L = 3 the same choice (28 zones instead of 64) changes nothing.
 // LGH_L2_NEB=0: sixteen.
-template <int M> static void launch_l2_kron(lgh_ctx *c, const MassArgs &a)
+template <int M> static int launch_l2_kron(lgh_ctx *c, const MassArgs &a)
 {
-#define LGH_L2K(L_, NEB_) hipLaunchKernelGGL((mass_apply_l2_kron<L_, NEB_, M>), dim3(ceil_div(c->NE, NEB_)), dim3(256), 0, c->stream, a)
-   if (l2_one_round(c)) { LGH_L2K(5, 10); }
-   else
-   {
-      switch (c->L1D)
-      {
-         case 1: LGH_L2K(1, 256); break;
-         case 2: LGH_L2K(2, 128); break;
-         case 3: LGH_L2K(3, 64); break;
-         case 4: LGH_L2K(4, 32); break;
-         default: LGH_L2K(5, 16); break;
-      }
-   }
-#undef LGH_L2K
+   return visit_order_2d3d(c, [&](auto, auto, auto Lc) {
+      constexpr int L = Lc, NEB = 512 >> L; // 256, 128, 64, 32, 16
+      if (L == 5 && l2_one_round(c)) { hipLaunchKernelGGL((mass_apply_l2_kron<5, 10, M>), dim3(ceil_div(c->NE, 10)), dim3(256), 0, c->stream, a); }
+      else { hipLaunchKernelGGL((mass_apply_l2_kron<L, NEB, M>), dim3(ceil_div(c->NE, NEB)), dim3(256), 0, c->stream, a); }
+      LGH_HIP_CHECK(hipGetLastError());
+      return LGH_OK;
+   });
 }
 
 template <int MODE> static int launch_mass(lgh_ctx *c, int space, const MassArgs &a0)
 {
-   const MassArgs &a = a0;
-   const int n1d = (space == LGH_SPACE_H1) ? c->D1D : c->L1D;
-   const int id = (c->dim << 8) | (n1d << 4) | c->Q1D;
    int l2form = 0, l2compact = 0;
-   if ((MODE == 0 || MODE == 3) && space == LGH_SPACE_L2)
-   {
-      const int rc_f = l2_mass_kernel(c, &l2form, &l2compact);
-      if (rc_f) { return rc_f; }
-   }
-#define LGH_MASS_CASE(DIMK, D_, Q_)                                                           \
-   {                                                                                          \
-      constexpr int NEB_ = neb_for<Q_>();                                                     \
-      hipLaunchKernelGGL((DIMK<D_, Q_, NEB_, MODE>), dim3(ceil_div(c->NE, NEB_)),             \
-                         dim3(Q_ * Q_ * NEB_), 0, c->stream, a);                              \
-   }                                                                                          \
-   break
+   if ((MODE == 0 || MODE == 3) && space == LGH_SPACE_L2) { LGH_PASS(l2_mass_kernel(c, &l2form, &l2compact)); }
+   constexpr int M = (MODE == 3 ? 3 : 0); // (the mode of the L2 forms)
+   MassArgs a = a0;
+   if (l2form) { LGH_PASS(mass_data(c, &a.Dq, &a.dqs, &a.Se)); } // (the Kronecker and plane forms take the mass data in its compact form where it has one)
    if (l2form == 2)
    {
       // compact mass data on a tensor-product rule: the Kronecker form (LGH_MASS_KRON=0: no tiles, see lgh_create)
-      MassArgs a = a0;
-      const int rc_md = mass_data(c, &a.Dq, &a.dqs, &a.Se);
-      if (rc_md) { return rc_md; }
       a.M1 = c->M1l;
-      launch_l2_kron<(MODE == 3 ? 3 : 0)>(c, a);
+      return launch_l2_kron<M>(c, a);
+   }
+   return visit_order_2d3d(c, [&](auto Dc, auto Qc, auto Lc) {
+      constexpr int Q = Qc, L = Lc;
+      // the column form on the n1d = D (H1) or L (L2) basis functions of the space
+      auto column = [&](auto Nc) {
+         constexpr int N1 = Nc, NEB = zones_per_wg(Q);
+         const dim3 grid(ceil_div(c->NE, NEB)), block(Q * Q * NEB);
+         if (c->dim == 2) { hipLaunchKernelGGL((mass_apply_2d<N1, Q, NEB, MODE>), grid, block, 0, c->stream, a); }
+         else { hipLaunchKernelGGL((mass_apply_3d<N1, Q, NEB, MODE>), grid, block, 0, c->stream, a); }
+      };
+      if constexpr (L >= 3)
+      {
+         if (l2form == 1)
+         {
+            // the plane form (L = 3, 4, 5 in 3-D: l2_mass_kernel): lanes per plane and zones per workgroup (1, 42), (1, 32), (2, 12)
+            constexpr int HY = (L == 5) ? 2 : 1, NEB = (L == 3) ? 42 : (L == 4) ? 32 : 12;
+            const dim3 grid(ceil_div(c->NE, NEB)), block(Q * HY * NEB);
+            a.w1 = (a.dqs == 0) ? c->w1d : nullptr;
+            if (a.w1) { hipLaunchKernelGGL((mass_apply_l2_plane<L, Q, HY, NEB, M, true>), grid, block, 0, c->stream, a); }
+            else { hipLaunchKernelGGL((mass_apply_l2_plane<L, Q, HY, NEB, M, false>), grid, block, 0, c->stream, a); }
+            LGH_HIP_CHECK(hipGetLastError());
+            return LGH_OK;
+         }
+      }
+      if (space == LGH_SPACE_H1) { column(Dc); }
+      else { column(Lc); }
       LGH_HIP_CHECK(hipGetLastError());
       return LGH_OK;
-   }
-   if (l2form == 1)
-   {
-      constexpr int M = (MODE == 3 ? 3 : 0);
-      {
-         MassArgs a = a0; // (the plane form takes the mass data in its compact form where it has one)
-         const int rc_md = mass_data(c, &a.Dq, &a.dqs, &a.Se);
-         if (rc_md) { return rc_md; }
-         a.w1 = (a.dqs == 0) ? c->w1d : nullptr;
-#define LGH_L2P(L_, Q_, HY_, NEB_) do { if (a.w1) { hipLaunchKernelGGL((mass_apply_l2_plane<L_, Q_, HY_, NEB_, M, true>), dim3(ceil_div(c->NE, NEB_)), dim3(Q_ * HY_ * NEB_), 0, c->stream, a); } \
-                                        else { hipLaunchKernelGGL((mass_apply_l2_plane<L_, Q_, HY_, NEB_, M, false>), dim3(ceil_div(c->NE, NEB_)), dim3(Q_ * HY_ * NEB_), 0, c->stream, a); } } while (0)
-         if (id == 0x336) { LGH_L2P(3, 6, 1, 42); }
-         else if (id == 0x348) { LGH_L2P(4, 8, 1, 32); }
-         else { LGH_L2P(5, 10, 2, 12); }
-#undef LGH_L2P
-         LGH_HIP_CHECK(hipGetLastError());
-         return LGH_OK;
-      }
-   }
-   switch (id)
-   {
-      case 0x212: LGH_MASS_CASE(mass_apply_2d, 1, 2);
-      case 0x222: LGH_MASS_CASE(mass_apply_2d, 2, 2);
-      case 0x224: LGH_MASS_CASE(mass_apply_2d, 2, 4);
-      case 0x234: LGH_MASS_CASE(mass_apply_2d, 3, 4);
-      case 0x236: LGH_MASS_CASE(mass_apply_2d, 3, 6);
-      case 0x246: LGH_MASS_CASE(mass_apply_2d, 4, 6);
-      case 0x248: LGH_MASS_CASE(mass_apply_2d, 4, 8);
-      case 0x258: LGH_MASS_CASE(mass_apply_2d, 5, 8);
-      case 0x25A: LGH_MASS_CASE(mass_apply_2d, 5, 10);
-      case 0x26A: LGH_MASS_CASE(mass_apply_2d, 6, 10);
-      case 0x312: LGH_MASS_CASE(mass_apply_3d, 1, 2);
-      case 0x322: LGH_MASS_CASE(mass_apply_3d, 2, 2);
-      case 0x324: LGH_MASS_CASE(mass_apply_3d, 2, 4);
-      case 0x334: LGH_MASS_CASE(mass_apply_3d, 3, 4);
-      case 0x336: LGH_MASS_CASE(mass_apply_3d, 3, 6);
-      case 0x346: LGH_MASS_CASE(mass_apply_3d, 4, 6);
-      case 0x348: LGH_MASS_CASE(mass_apply_3d, 4, 8);
-      case 0x358: LGH_MASS_CASE(mass_apply_3d, 5, 8);
-      case 0x35A: LGH_MASS_CASE(mass_apply_3d, 5, 10);
-      case 0x36A: LGH_MASS_CASE(mass_apply_3d, 6, 10);
-      default: return unknown_kernel(id);
-   }
-#undef LGH_MASS_CASE
-   LGH_HIP_CHECK(hipGetLastError());
-   return LGH_OK;
+   });
 }
 // D[q, e] = W[q] s_e ?  In exact arithmetic the data of laghos_assembly.cpp:92-95, w_q detJ0(x_q) rho0(x_q), has this
 // form whenever the initial element is affine and rho0 constant in it; the stored entries carry the rounding of the
@@ -936,9 +888,7 @@ int mass_l2_fused_update(lgh_ctx *c, const MassArgs &m, double *ux, double *ur, 
    a.ur = ur;
    a.partials = partials;
    a.ticket = ticket;
-   launch_l2_kron<4>(c, a);
-   LGH_HIP_CHECK(hipGetLastError());
-   return LGH_OK;
+   return launch_l2_kron<4>(c, a);
 }
 
 int mass_apply_E(lgh_ctx *c, int space, const double *xE, double *yE)

@@ -858,58 +858,37 @@ qpoint_kernel(const QArgs a)
    }
 }
 
-static int unknown_kernel(int id)
-{
-   set_error("Unknown kernel 0x%x", id);
-   return LGH_ERR_UNSUPPORTED;
-}
-
+// ids follow the reference table (laghos_solver.cpp:1387-1396) joined with D1D; Q5Q4 is an extension, not in that table
 template <int MODE> static int launch_q(lgh_ctx *c, const QArgs &a)
 {
-#define LGH_Q3(D_, Q_, L_, NF_)                                                                      \
-   hipLaunchKernelGGL((qpoint_kernel<3, D_, Q_, L_, 1, NF_, MODE>), dim3(c->NE), dim3(Q_ * Q_ * Q_), \
-                      0, c->stream, a);                                                              \
-   break
-#define LGH_Q2(D_, Q_, L_)                                                                           \
-   {                                                                                                 \
-      constexpr int NEB_ = (256 / (Q_ * Q_)) > 0 ? (256 / (Q_ * Q_)) : 1;                            \
-      hipLaunchKernelGGL((qpoint_kernel<2, D_, Q_, L_, NEB_, 4, MODE>), dim3(ceil_div(c->NE, NEB_)), \
-                         dim3(Q_ * Q_ * NEB_), 0, c->stream, a);                                     \
-   }                                                                                                 \
-   break
-   switch (c->kid)
-   {
-      // ids follow the reference table (laghos_solver.cpp:1387-1396) joined with D1D
-      case 0x222: LGH_Q2(2, 2, 1);
-      case 0x234: LGH_Q2(3, 4, 2);
-      case 0x246: LGH_Q2(4, 6, 3);
-      case 0x258: LGH_Q2(5, 8, 4);
-      case 0x26A: LGH_Q2(6, 10, 5);
-      case 0x322: LGH_Q3(2, 2, 1, 6);
-      case 0x334: LGH_Q3(3, 4, 2, 6);
-      case 0x346: LGH_Q3(4, 6, 3, 6);
-      // all six H1 fields in one LDS pass at every order: only one workgroup of 512 / 1000 threads fits a CU at Q4Q3 /
-      // Q5Q4 anyway, so its 76 / 140 KB of LDS cost nothing, and one pass needs fewer registers than several (the
-      // gradients do not have to survive across passes): 234 -> 158 VGPRs at Q4Q3, 70 -> 41 spilled registers under
-      // the 128-register cap of the 1000-thread workgroup at Q5Q4, where the update takes 10.4 instead of 17 ms
-      case 0x358: LGH_Q3(5, 8, 4, 6);
-      case 0x36A: // extension: not in the reference table
-         if constexpr (MODE == QMODE_UPDATE)
+   return visit_order_2d3d(c, [&](auto Dc, auto Qc, auto Lc) {
+      constexpr int D = Dc, Q = Qc, L = Lc;
+      if (c->dim == 2)
+      {
+         constexpr int NEB = zones_per_wg(Q);
+         hipLaunchKernelGGL((qpoint_kernel<2, D, Q, L, NEB, 4, MODE>), dim3(ceil_div(c->NE, NEB)), dim3(Q * Q * NEB), 0, c->stream, a);
+      }
+      else
+      {
+         // all six H1 fields in one LDS pass at every order: only one workgroup of 512 / 1000 threads fits a CU at Q4Q3 /
+         // Q5Q4 anyway, so its 76 / 140 KB of LDS cost nothing, and one pass needs fewer registers than several (the
+         // gradients do not have to survive across passes): 234 -> 158 VGPRs at Q4Q3, 70 -> 41 spilled registers under
+         // the 128-register cap of the 1000-thread workgroup at Q5Q4, where the update takes 10.4 instead of 17 ms
+         if constexpr (Q == 10 && MODE == QMODE_UPDATE)
          {
             // two points per thread: 500-thread workgroups under a cap of 256 registers instead of 1000 under 128 (41 spilled)
             if (!c->sw.q_ppt) // (LGH_Q_PPT=1, A/B: one point per thread)
             {
-               hipLaunchKernelGGL((qpoint_kernel<3, 6, 10, 5, 1, 6, MODE, 2>), dim3(c->NE), dim3(500), 0, c->stream, a);
-               break;
+               hipLaunchKernelGGL((qpoint_kernel<3, D, Q, L, 1, 6, MODE, 2>), dim3(c->NE), dim3(Q * Q * Q / 2), 0, c->stream, a);
+               LGH_HIP_CHECK(hipGetLastError());
+               return LGH_OK;
             }
          }
-         LGH_Q3(6, 10, 5, 6);
-      default: return unknown_kernel(c->kid);
-   }
-#undef LGH_Q3
-#undef LGH_Q2
-   LGH_HIP_CHECK(hipGetLastError());
-   return LGH_OK;
+         hipLaunchKernelGGL((qpoint_kernel<3, D, Q, L, 1, 6, MODE>), dim3(c->NE), dim3(Q * Q * Q), 0, c->stream, a);
+      }
+      LGH_HIP_CHECK(hipGetLastError());
+      return LGH_OK;
+   });
 }
 
 static QArgs q_base(lgh_ctx *c)

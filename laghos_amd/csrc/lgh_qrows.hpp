@@ -477,15 +477,7 @@ qrows_kernel(const QArgs a, unsigned long long *trace = nullptr)
 
 // kernel ids the row form is instantiated for (3D; Q5Q4 keeps the point form with two points per thread: the slices of
 // a 1000-point element do not fit the LDS of a CU twice over)
-static bool qrows_available(const lgh_ctx *c)
-{
-   if (c->dim != 3) { return false; }
-   switch (c->kid)
-   {
-      case 0x322: case 0x334: case 0x346: case 0x358: return true;
-   }
-   return false;
-}
+static bool qrows_available(const lgh_ctx *c) { return c->dim == 3 && c->Q1D < 10 && order_supported(c->kid); }
 // debug: LGH_Q_TRACE=<file>: the Q3Q2 update through the traced instantiation; the stamps of call number LGH_Q_TRACE_CALL
 // (default 40: inside the timed window of a bench run) are written to the file (qrows_trace_dump)
 // (the buffer and the call counter live in the context - round-5 advisor: file-scope statics were shared by every context)
@@ -522,19 +514,19 @@ template <int MINW6> static int launch_qrows_w(lgh_ctx *c, const QArgs &a)
       if (++c->q_trace_calls == c->sw.q_trace_call) { qrows_trace_dump(c); } // (LGH_Q_TRACE_CALL: which call to dump)
       return LGH_OK;
    }
-#define LGH_QROWS(D_, Q_, L_, W_, NT_) do { if (a.Jac0inv_e) { hipLaunchKernelGGL((qrows_kernel<D_, Q_, L_, W_, false, true>), dim3(c->NE), dim3(NT_), 0, c->stream, a, (unsigned long long *)nullptr); } \
-                                           else { hipLaunchKernelGGL((qrows_kernel<D_, Q_, L_, W_, false, false>), dim3(c->NE), dim3(NT_), 0, c->stream, a, (unsigned long long *)nullptr); } } while (0)
-   switch (c->kid)
-   {
-      case 0x322: LGH_QROWS(2, 2, 1, 1, 8); break;
-      case 0x334: LGH_QROWS(3, 4, 2, 1, 64); break;
-      case 0x346: LGH_QROWS(4, 6, 3, MINW6, 216); break;
-      case 0x358: LGH_QROWS(5, 8, 4, 1, 512); break;
-      default: return unknown_kernel(c->kid);
-   }
-#undef LGH_QROWS
-   LGH_HIP_CHECK(hipGetLastError());
-   return LGH_OK;
+   if (c->dim != 3) { return unknown_kernel(c->kid); }
+   return visit_order_2d3d(c, [&](auto Dc, auto Qc, auto Lc) {
+      constexpr int D = Dc, Q = Qc, L = Lc;
+      if constexpr (Q < 10)
+      {
+         constexpr int W = (Q == 6) ? MINW6 : 1; // one thread per point: 8, 64, 216, 512
+         if (a.Jac0inv_e) { hipLaunchKernelGGL((qrows_kernel<D, Q, L, W, false, true>), dim3(c->NE), dim3(Q * Q * Q), 0, c->stream, a, (unsigned long long *)nullptr); }
+         else { hipLaunchKernelGGL((qrows_kernel<D, Q, L, W, false, false>), dim3(c->NE), dim3(Q * Q * Q), 0, c->stream, a, (unsigned long long *)nullptr); }
+         LGH_HIP_CHECK(hipGetLastError());
+         return LGH_OK;
+      }
+      else { return unknown_kernel(c->kid); } // (Q5Q4 has no row form: qrows_available)
+   });
 }
 static int launch_qrows(lgh_ctx *c, const QArgs &a)
 {

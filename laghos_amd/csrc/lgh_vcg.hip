@@ -814,12 +814,12 @@ static int vcg_work_buffers(lgh_ctx *c)
 {
    if (c->vcg_tickets) { return LGH_OK; } // (the last one built: a failure on the way leaves the rest to the next call)
    const size_t N = (size_t)c->N;
-   LGH_VCG_TRY(c->vcg_s.alloc(1, true));
-   LGH_VCG_TRY(c->vcg_vec.alloc(3 * kVC * N, true)); // r, d, yL (z = r/diag is never stored)
+   LGH_PASS(c->vcg_s.alloc(1, true));
+   LGH_PASS(c->vcg_vec.alloc(3 * kVC * N, true)); // r, d, yL (z = r/diag is never stored)
    // block partials of the largest reducing launch: K1 (<= NE batches), vcg_update_k (N/256 blocks), vcg_update_p_k (2 per CU)
    c->vcg_stride = (unsigned)(std::max<size_t>(std::max<size_t>((size_t)c->NE, (N + 255) / 256), 4096) + kShards);
-   LGH_VCG_TRY(c->vcg_partials.alloc(2 * kVC * (size_t)c->vcg_stride, true));
-   LGH_VCG_TRY(c->vcg_tickets.alloc(2 * kTicketSlot, true));
+   LGH_PASS(c->vcg_partials.alloc(2 * kVC * (size_t)c->vcg_stride, true));
+   LGH_PASS(c->vcg_tickets.alloc(2 * kTicketSlot, true));
    return LGH_OK;
 }
 
@@ -839,7 +839,7 @@ static int vcg_mode_collective(lgh_ctx *c, VcgAux *aux, const VcgK1 &k1, const b
       const double mine[2] = {m.rz_words ? 1.0 : 0.0, m.ls_mine ? 1.0 : 0.0};
       LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
       LGH_HIP_CHECK(hipMemcpy(c->scal + 12, mine, sizeof(mine), hipMemcpyHostToDevice)); // (pageable host memory: synchronous copies)
-      LGH_VCG_TRY(allreduce_dev(c, c->scal + 12, 2, 1));
+      LGH_PASS(allreduce_dev(c, c->scal + 12, 2, 1));
       double all[2] = {0.0, 0.0};
       LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
       LGH_HIP_CHECK(hipMemcpy(all, c->scal + 12, sizeof(all), hipMemcpyDeviceToHost));
@@ -873,7 +873,7 @@ static int vcg_mode(lgh_ctx *c, VcgAux *aux, const VcgK1 &k1, const bool in_solv
                   (m.n_shared == 0 || (c->sw.halo_fused_pack && halo_can_piggyback(c) && comm_pack_tables(c, &hp)));
    }
    if (m.multi && c->nranks == 1) { aux->ls_all = m.ls_mine ? 1 : 0; }
-   if (m.multi && c->nranks > 1) { LGH_VCG_TRY(vcg_mode_collective(c, aux, k1, in_solve, m)); }
+   if (m.multi && c->nranks > 1) { LGH_PASS(vcg_mode_collective(c, aux, k1, in_solve, m)); }
    m.rzl = m.rz_words && c->sw.slab_defer && aux->rzl != nullptr; // (needs the deferred fold of (d, A d) as well)
    // (LGH_SLAB_DEFER=0, A/B: the last workgroup of K1 folds the accumulators (ticket), K2 reads the result)
    m.den_limbs = (m.limbs && c->sw.slab_defer) ? (m.multi ? 2 : 1) : 0; // (several ranks: folded before the exchange, vcg_fold_den)
@@ -903,12 +903,12 @@ static int vcg_fill_internal_order(lgh_ctx *c, VcgAux *aux, const VcgK1 &k1, con
    const bool need_table = a.dqs != 0 || k1.form == kK1Column; // (the column form of K1 reads the stored table whatever the compact form says)
    if (aux->o_mass_gen != c->mass_gen)
    {
-      LGH_VCG_TRY(order_gather_nodes(c, c->dinvV, aux->o_dinv, 1));
-      if (a.dqs == 0) { LGH_VCG_TRY(order_zone_blocks(c, a.Se, aux->o_Se, 1, false)); }
+      LGH_PASS(order_gather_nodes(c, c->dinvV, aux->o_dinv, 1));
+      if (a.dqs == 0) { LGH_PASS(order_zone_blocks(c, a.Se, aux->o_Se, 1, false)); }
       if (need_table)
       {
-         if (!aux->o_massD) { LGH_VCG_TRY(aux->o_massD.alloc((size_t)c->NE * c->NQ + 2048, true)); }
-         LGH_VCG_TRY(order_zone_blocks(c, c->massD, aux->o_massD, c->NQ, false));
+         if (!aux->o_massD) { LGH_PASS(aux->o_massD.alloc((size_t)c->NE * c->NQ + 2048, true)); }
+         LGH_PASS(order_zone_blocks(c, c->massD, aux->o_massD, c->NQ, false));
       }
       aux->o_mass_gen = c->mass_gen;
    }
@@ -934,7 +934,7 @@ static int vcg_fill_args(lgh_ctx *c, VcgAux *aux, const VcgK1 &k1, const VcgMode
    a.N = c->N;
    a.B = c->B;
    a.DqFull = c->massD;
-   LGH_VCG_TRY(mass_data(c, &a.Dq, &a.dqs, &a.Se));
+   LGH_PASS(mass_data(c, &a.Dq, &a.dqs, &a.Se));
    a.w1 = (a.dqs == 0) ? c->w1d : nullptr;
    a.M1 = (a.dqs == 0 && c->w1d) ? c->M1h : nullptr; // (nullptr with LGH_MASS_KRON=0)
    a.map = c->h1map;
@@ -945,7 +945,7 @@ static int vcg_fill_args(lgh_ctx *c, VcgAux *aux, const VcgK1 &k1, const VcgMode
    a.owner = m.multi ? c->owner : nullptr;
    a.b = B;
    a.x = X;
-   if (aux->ord) { LGH_VCG_TRY(vcg_fill_internal_order(c, aux, k1, m, a)); }
+   if (aux->ord) { LGH_PASS(vcg_fill_internal_order(c, aux, k1, m, a)); }
    a.r = c->vcg_vec;
    a.d = c->vcg_vec + kVC * N;
    a.yL = c->vcg_vec + 2 * kVC * N;
@@ -972,7 +972,7 @@ static int vcg_fill_args(lgh_ctx *c, VcgAux *aux, const VcgK1 &k1, const VcgMode
    //  single kernels on state of their own, had vcg_set_tol_k do it: vcg_prepare)
    a.reset = in_solve ? 1 : 0;
    a.reset_tol2 = rel_tol * rel_tol;
-   if (m.rzl && m.multi) { LGH_VCG_TRY(comm_word_peers(c, kLimbWords, &a.rzl_peers, &a.n_rz_peers)); }
+   if (m.rzl && m.multi) { LGH_PASS(comm_word_peers(c, kLimbWords, &a.rzl_peers, &a.n_rz_peers)); }
    a.queue = a.limbs ? (unsigned *)(a.limbs + 2 * kLimbWords) : nullptr;
    a.den_limbs = m.den_limbs;
    a.k2_skip = c->sw.k2_skip;
@@ -1006,12 +1006,12 @@ static int vcg_fill_args(lgh_ctx *c, VcgAux *aux, const VcgK1 &k1, const VcgMode
 // stream (a solve does that in its first kernel, VcgArgs::reset).
 int vcg_prepare(lgh_ctx *c, double *B, double *X, double rel_tol, VcgPlan &plan, const bool in_solve)
 {
-   LGH_VCG_TRY(vcg_work_buffers(c));
-   if (!c->vcg_aux) { LGH_VCG_TRY(vcg_build_aux(c)); } // (first solve, or the communicator has changed since)
+   LGH_PASS(vcg_work_buffers(c));
+   if (!c->vcg_aux) { LGH_PASS(vcg_build_aux(c)); } // (first solve, or the communicator has changed since)
    VcgAux *aux = c->vcg_aux.get();
    plan.aux = aux;
    plan.k1 = vcg_resolve_k1(c);
-   LGH_VCG_TRY(vcg_mode(c, aux, plan.k1, in_solve, plan.mode));
+   LGH_PASS(vcg_mode(c, aux, plan.k1, in_solve, plan.mode));
    const VcgMode &m = plan.mode;
    if (!in_solve)
    {
@@ -1057,7 +1057,7 @@ static int vcg_start(lgh_ctx *c, VcgPlan &plan, double *B, const double *force_E
    LGH_HIP_CHECK(hipGetLastError());
    if (plan.mode.multi)
    {
-      LGH_VCG_TRY(allreduce_dev(c, a.s->rz, kVC, 0));
+      LGH_PASS(allreduce_dev(c, a.s->rz, kVC, 0));
       hipLaunchKernelGGL(vcg_init_finish_k, dim3(1), dim3(1), 0, c->stream, a.s);
    }
    return LGH_OK;
@@ -1077,14 +1077,14 @@ static int vcg_look(lgh_ctx *c, const VcgPlan &plan, VcgRun &r, bool &stop)
    bool copied = false;
    // the first look of a solve comes after a whole chunk of iterations: the energy solve on the second stream is
    // brought to its end meanwhile (its looks used to wait behind the velocity solve, with the GPU idle)
-   if (!r.energy_polled) { r.energy_polled = true; LGH_VCG_TRY(energy_overlap_poll(c)); }
+   if (!r.energy_polled) { r.energy_polled = true; LGH_PASS(energy_overlap_poll(c)); }
    if (plan.mode.multi && !a.rzl && r.it > 0) { hipLaunchKernelGGL(vcg_update_finish_k, dim3(1), dim3(1), 0, c->stream, r.ds, r.it, hs_dev, tok_dev, token); copied = true; }
    if (a.rzl && r.it > 0) { vcg_launch_rz_finish(c, a, r.it, hs_dev, tok_dev, token); copied = true; }
    if (copied)
    {
       // (on several ranks the exchanges that follow are host-synchronous on the loopback transports and enqueue-only over
       //  RCCL: either way nothing of this rank is in flight behind the finishing kernel)
-      LGH_VCG_TRY(host_wait_token(c, tok, token));
+      LGH_PASS(host_wait_token(c, tok, token));
    }
    else
    {
@@ -1113,7 +1113,7 @@ static int vcg_step_k1(lgh_ctx *c, const VcgPlan &plan, VcgArgs &a)
 // one iteration on one rank (valence <= 8): K1, then K2 gathers A d itself
 static int vcg_iterate_direct(lgh_ctx *c, const VcgPlan &plan, VcgArgs &a)
 {
-   LGH_VCG_TRY(vcg_step_k1(c, plan, a));
+   LGH_PASS(vcg_step_k1(c, plan, a));
    if (plan.mode.k2p) { vcg_launch_k2p(c, plan, a, a.iter); }
    else { kt_begin(c, LGH_KERNEL_CG_UPDATE_H1); vcg_launch_update(c, a, true); kt_end(c, LGH_KERNEL_CG_UPDATE_H1); }
    LGH_HIP_CHECK(hipGetLastError());
@@ -1132,8 +1132,8 @@ static int vcg_iterate_exchange(lgh_ctx *c, const VcgPlan &plan, VcgArgs &a, con
    const int it = a.iter, nb = ceil_div(a.N, 256);
    const bool ls_it = m.ls && it <= r.ls_limit;
    auto ls_words = [&](const int set_it) { return LockstepWords{a.rzl + (set_it % 3) * kLimbWords, a.rzl_peers, a.n_rz_peers, r.ls_before}; };
-   LGH_VCG_TRY(vcg_step_k1(c, plan, a));
-   if (ls_it) { LGH_VCG_TRY(l2_lockstep_apply(c, it, ls_words(it - 1), &r.ds->den_e)); } // (the messages are packed after this)
+   LGH_PASS(vcg_step_k1(c, plan, a));
+   if (ls_it) { LGH_PASS(l2_lockstep_apply(c, it, ls_words(it - 1), &r.ds->den_e)); } // (the messages are packed after this)
    if (m.mixed)
    {
       if (a.n_shared > 0) { hipLaunchKernelGGL(vcg_gather_list_k, dim3(ceil_div(a.n_shared, 256)), dim3(256), 0, c->stream, a); }
@@ -1150,26 +1150,26 @@ static int vcg_iterate_exchange(lgh_ctx *c, const VcgPlan &plan, VcgArgs &a, con
       // (d, A d): summed over the ranks by the halo messages themselves when every
       // rank is a neighbour of every other, by an all-reduce otherwise
       const bool ride = halo_can_piggyback(c);
-      LGH_VCG_TRY(halo_sum(c, a.yL, kVC, ride ? r.ds->den : nullptr, ride ? std::max(a.nx_den, kVC) : 0, a.pack_halo != 0, r.alias));
-      if (!ride) { LGH_VCG_TRY(allreduce_dev(c, r.ds->den, kVC, 0)); }
+      LGH_PASS(halo_sum(c, a.yL, kVC, ride ? r.ds->den : nullptr, ride ? std::max(a.nx_den, kVC) : 0, a.pack_halo != 0, r.alias));
+      if (!ride) { LGH_PASS(allreduce_dev(c, r.ds->den, kVC, 0)); }
    }
    // (the bounded-grid K2 knows the shared nodes and the owner weights from its flag bytes)
    if (m.mixed && m.k2p) { vcg_launch_k2p(c, plan, a, it); }
    else { vcg_launch_update(c, a, m.mixed); }
-   if (ls_it) { LGH_VCG_TRY(l2_lockstep_update(c, it, &r.ds->den_e, a.rzl + (it % 3) * kLimbWords)); } // (reads the summed (d, M d); the word exchange carries its (r, r))
+   if (ls_it) { LGH_PASS(l2_lockstep_update(c, it, &r.ds->den_e, a.rzl + (it % 3) * kLimbWords)); } // (reads the summed (d, M d); the word exchange carries its (r, r))
    if (m.multi && a.rzl)
    {
       // exact all-reduce of (r, z): the accumulator words K2 just added into go to every peer as they are - no fold,
       // no pack, no combine kernel; the next K1 (or vcg_rz_finish_k) adds own and peers' words before it folds
-      LGH_VCG_TRY(exchange_words(c, a.rzl + (it % 3) * kLimbWords, kLimbWords));
+      LGH_PASS(exchange_words(c, a.rzl + (it % 3) * kLimbWords, kLimbWords));
       if (ls_it && (it == r.ls_limit || it == upto))
       {
          // the energy CG's last interleaved iteration of this chunk: its outcome is committed now, while the peers'
          // words of THIS exchange are still in the buffer (the next apply, if there is one, finds the same sum)
-         LGH_VCG_TRY(l2_lockstep_fold(c, it, ls_words(it)));
+         LGH_PASS(l2_lockstep_fold(c, it, ls_words(it)));
       }
    }
-   else if (m.multi) { LGH_VCG_TRY(allreduce_dev(c, r.ds->rz, kVC, 0, a.pack_rz != 0 && m.mixed && m.k2p)); } // convergence is looked at by the next K1 (vcg_pending_update)
+   else if (m.multi) { LGH_PASS(allreduce_dev(c, r.ds->rz, kVC, 0, a.pack_rz != 0 && m.mixed && m.k2p)); } // convergence is looked at by the next K1 (vcg_pending_update)
    LGH_HIP_CHECK(hipGetLastError());
    return LGH_OK;
 }
@@ -1224,7 +1224,7 @@ int vcg_solve(lgh_ctx *c, double *B, double *X, double rel_tol, int max_iter, in
 {
    if (!vcg_available(c)) { return LGH_ERR_UNSUPPORTED; }
    VcgPlan plan;
-   LGH_VCG_TRY(vcg_prepare(c, B, X, rel_tol, plan, true));
+   LGH_PASS(vcg_prepare(c, B, X, rel_tol, plan, true));
    VcgArgs &a = plan.a;
    const VcgMode &m = plan.mode;
    VcgRun r;
@@ -1235,7 +1235,7 @@ int vcg_solve(lgh_ctx *c, double *B, double *X, double rel_tol, int max_iter, in
    r.chunk = c->vcg_last > 0 ? c->vcg_last : 8; // first chunk = iteration count of the previous velocity solve (see cg_solve, lgh_scg.hip)
    r.ls_limit = m.ls ? std::min(l2_lockstep_limit(c), max_iter) : 0;
    r.ls_before = m.ls ? comm_ranks_before(c) : 0;
-   LGH_VCG_TRY(vcg_start(c, plan, B, force_E));
+   LGH_PASS(vcg_start(c, plan, B, force_E));
    // The first chunk is enqueued without looking at the flag first (an all-zero right-hand side just makes its launches
    // return at once): one host round trip, with the GPU idle meanwhile, less per solve.
    for (bool first_look = true;; first_look = false)
@@ -1243,14 +1243,14 @@ int vcg_solve(lgh_ctx *c, double *B, double *X, double rel_tol, int max_iter, in
       if (!first_look || max_iter <= 0)
       {
          bool stop = false;
-         LGH_VCG_TRY(vcg_look(c, plan, r, stop));
+         LGH_PASS(vcg_look(c, plan, r, stop));
          if (stop) { break; }
       }
       const int upto = std::min(max_iter, r.it + r.chunk);
       while (r.it < upto)
       {
          a.iter = ++r.it;
-         LGH_VCG_TRY(m.direct ? vcg_iterate_direct(c, plan, a) : vcg_iterate_exchange(c, plan, a, r, upto));
+         LGH_PASS(m.direct ? vcg_iterate_direct(c, plan, a) : vcg_iterate_exchange(c, plan, a, r, upto));
       }
    }
    return vcg_finish(c, plan, r, X, iters);

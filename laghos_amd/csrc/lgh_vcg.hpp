@@ -432,7 +432,6 @@ __device__ __forceinline__ long long wave_sum_i64(long long v)
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-#define LGH_VCG_TRY(call) do { const int rc_ = (call); if (rc_) { return rc_; } } while (0) // (an LGH_* status: passed on)
 // Tables and buffers of the solve that outlive a call (lgh_ctx::vcg_aux; lgh_vcg_tables.hip builds them, vcg_free drops them)
 struct VcgAux
 {

@@ -185,9 +185,9 @@ struct MergedDev { DevPtr<int> pos; DevPtr<uint8_t> sec; };
 static int merged_to_device(lgh_ctx *c, const VcgAux *aux, MergedDev &m)
 {
    SlabLayout L;
-   LGH_VCG_TRY(slab_merge_layout(c, aux, L));
-   LGH_VCG_TRY(m.pos.upload(L.pos.data(), L.pos.size()));
-   LGH_VCG_TRY(m.sec.upload(L.sec.data(), L.sec.size()));
+   LGH_PASS(slab_merge_layout(c, aux, L));
+   LGH_PASS(m.pos.upload(L.pos.data(), L.pos.size()));
+   LGH_PASS(m.sec.upload(L.sec.data(), L.sec.size()));
    return LGH_OK;
 }
 // lgh_test_vcg_merged_faces: mask[e * ND + d] = 1 where K1 of this context has already summed the entry into its left
@@ -199,10 +199,10 @@ int vcg_test_merged_faces(lgh_ctx *c, unsigned char *mask, long *n_merged)
    *n_merged = 0;
    if (!vcg_available(c)) { return LGH_OK; }
    VcgPlan plan;
-   LGH_VCG_TRY(vcg_prepare(c, nullptr, nullptr, 0.0, plan));
+   LGH_PASS(vcg_prepare(c, nullptr, nullptr, 0.0, plan));
    if (!plan.a.settab) { return LGH_OK; }
    SlabLayout L;
-   LGH_VCG_TRY(slab_merge_layout(c, plan.aux, L));
+   LGH_PASS(slab_merge_layout(c, plan.aux, L));
    // (the layout is that of the order the solve runs in; the caller's E-vector is in the caller's zone order)
    const MeshOrder *ord = plan.aux->ord;
    if (ord)
@@ -225,12 +225,12 @@ int vcg_layout_stats(lgh_ctx *c, long out[4])
    out[0] = (long)c->NE * c->ND; out[1] = 16L * c->N; out[2] = 16L * c->N; out[3] = 0;
    if (!vcg_available(c)) { return LGH_OK; }
    VcgPlan plan;
-   LGH_VCG_TRY(vcg_prepare(c, nullptr, nullptr, 0.0, plan));
+   LGH_PASS(vcg_prepare(c, nullptr, nullptr, 0.0, plan));
    const VcgArgs &a = plan.a;
    if (a.settab)
    {
       SlabLayout L;
-      LGH_VCG_TRY(slab_merge_layout(c, plan.aux, L));
+      LGH_PASS(slab_merge_layout(c, plan.aux, L));
       long used = 0;
       for (size_t i = 0; i < L.pos.size(); i++) { used = std::max(used, (long)L.pos[i] + 1); }
       out[0] = used;
@@ -265,15 +265,15 @@ int vcg_test_k1(lgh_ctx *c, const double *r, const double *d_old, const double r
    if (!vcg_available(c)) { set_error("lgh_test_vcg_k1: no lockstep solve for kernel 0x%x", c->kid); return LGH_ERR_UNSUPPORTED; }
    if (c->multi != 0) { set_error("lgh_test_vcg_k1: single rank only"); return LGH_ERR_ARG; }
    VcgPlan plan;
-   LGH_VCG_TRY(vcg_prepare(c, nullptr, nullptr, 0.0, plan));
+   LGH_PASS(vcg_prepare(c, nullptr, nullptr, 0.0, plan));
    VcgArgs &a = plan.a;
    const size_t N = (size_t)c->N, nE = (size_t)c->NE * c->ND;
    VcgScalars *ds = (VcgScalars *)c->vcg_s;
    const MeshOrder *ord = plan.aux->ord; // (the solve's own order: the caller's vectors and E-vector go through the permutation)
-   if (ord) { LGH_VCG_TRY(order_gather_nodes(c, r, a.r, kVC)); }
+   if (ord) { LGH_PASS(order_gather_nodes(c, r, a.r, kVC)); }
    else { LGH_HIP_CHECK(hipMemcpyAsync(a.r, r, kVC * N * sizeof(double), hipMemcpyDeviceToDevice, c->stream)); }
    if (first) { LGH_HIP_CHECK(hipMemsetAsync(a.d, 0, kVC * N * sizeof(double), c->stream)); }
-   else if (ord) { LGH_VCG_TRY(order_gather_nodes(c, d_old, a.d, kVC)); }
+   else if (ord) { LGH_PASS(order_gather_nodes(c, d_old, a.d, kVC)); }
    else { LGH_HIP_CHECK(hipMemcpyAsync(a.d, d_old, kVC * N * sizeof(double), hipMemcpyDeviceToDevice, c->stream)); }
    LGH_HIP_CHECK(hipStreamSynchronize(c->stream)); // (vcg_set_tol_k has cleared the accumulators and the set counters)
    VcgScalars h;
@@ -303,9 +303,9 @@ int vcg_test_k1(lgh_ctx *c, const double *r, const double *d_old, const double r
    LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
    LGH_HIP_CHECK(hipMemcpy(&h, ds, sizeof(h), hipMemcpyDeviceToHost));
    MergedDev md;
-   if (a.settab) { LGH_VCG_TRY(merged_to_device(c, plan.aux, md)); }
+   if (a.settab) { LGH_PASS(merged_to_device(c, plan.aux, md)); }
    DevPtr<double> tmp; // (internal order: a plane in the solve's zone order on its way to the caller's)
-   if (ord) { LGH_VCG_TRY(tmp.alloc(nE)); }
+   if (ord) { LGH_PASS(tmp.alloc(nE)); }
    for (int k = 0; k < kVC; k++)
    {
       den_out[k] = h.den[k];
@@ -316,7 +316,7 @@ int vcg_test_k1(lgh_ctx *c, const double *r, const double *d_old, const double r
          LGH_HIP_CHECK(hipGetLastError());
       }
       else { LGH_HIP_CHECK(hipMemcpyAsync(dst, a.YE + (size_t)k * a.ye_stride, nE * sizeof(double), hipMemcpyDeviceToDevice, c->stream)); }
-      if (ord) { LGH_VCG_TRY(order_zone_blocks(c, tmp.p, YE_out + (size_t)k * nE, c->ND, true)); }
+      if (ord) { LGH_PASS(order_zone_blocks(c, tmp.p, YE_out + (size_t)k * nE, c->ND, true)); }
    }
    LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
    return LGH_OK;
@@ -335,16 +335,16 @@ int vcg_test_k2(lgh_ctx *c, int it, const double *YE_in, double *r, double *d, d
    if (!vcg_available(c)) { set_error("lgh_test_vcg_k2: no lockstep solve for kernel 0x%x", c->kid); return LGH_ERR_UNSUPPORTED; }
    if (c->multi != 0 || it < 1) { set_error("lgh_test_vcg_k2: single rank, it >= 1"); return LGH_ERR_ARG; }
    VcgPlan plan;
-   LGH_VCG_TRY(vcg_prepare(c, nullptr, x, 0.0, plan));
+   LGH_PASS(vcg_prepare(c, nullptr, x, 0.0, plan));
    VcgArgs &a = plan.a;
    const size_t N = (size_t)c->N, nE = (size_t)c->NE * c->ND;
    VcgScalars *ds = (VcgScalars *)c->vcg_s;
    const MeshOrder *ord = plan.aux->ord; // (the solve's own order: the caller's vectors and E-vector go through the permutation)
    if (ord)
    {
-      LGH_VCG_TRY(order_gather_nodes(c, r, a.r, kVC));
-      LGH_VCG_TRY(order_gather_nodes(c, d, a.d, kVC));
-      LGH_VCG_TRY(order_gather_nodes(c, x, a.x, kVC));
+      LGH_PASS(order_gather_nodes(c, r, a.r, kVC));
+      LGH_PASS(order_gather_nodes(c, d, a.d, kVC));
+      LGH_PASS(order_gather_nodes(c, x, a.x, kVC));
    }
    else
    {
@@ -352,13 +352,13 @@ int vcg_test_k2(lgh_ctx *c, int it, const double *YE_in, double *r, double *d, d
       LGH_HIP_CHECK(hipMemcpyAsync(a.d, d, kVC * N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
    }
    MergedDev md;
-   if (a.settab) { LGH_VCG_TRY(merged_to_device(c, plan.aux, md)); }
+   if (a.settab) { LGH_PASS(merged_to_device(c, plan.aux, md)); }
    DevPtr<double> tmp;
-   if (ord) { LGH_VCG_TRY(tmp.alloc(nE)); }
+   if (ord) { LGH_PASS(tmp.alloc(nE)); }
    for (int k = 0; k < kVC; k++)
    {
       const double *src = YE_in + (size_t)k * nE;
-      if (ord) { LGH_VCG_TRY(order_zone_blocks(c, src, tmp.p, c->ND, false)); src = tmp.p; }
+      if (ord) { LGH_PASS(order_zone_blocks(c, src, tmp.p, c->ND, false)); src = tmp.p; }
       if (a.settab)
       {
          hipLaunchKernelGGL(vcg_pack_merged_k, dim3((unsigned)((nE + 255) / 256)), dim3(256), 0, c->stream, src, md.pos, md.sec, c->ND, a.YE + (size_t)k * a.ye_stride, nE);
@@ -398,9 +398,9 @@ int vcg_test_k2(lgh_ctx *c, int it, const double *YE_in, double *r, double *d, d
    for (int k = 0; k < kVC; k++) { rz_out[k] = (a.rzl && plan.mode.k2p) ? h.rzh[it & 1][k] : h.rz[k]; }
    if (ord)
    {
-      LGH_VCG_TRY(order_scatter_nodes(c, a.r, r, kVC));
-      LGH_VCG_TRY(order_scatter_nodes(c, a.d, d, kVC));
-      LGH_VCG_TRY(order_scatter_nodes(c, a.x, x, kVC));
+      LGH_PASS(order_scatter_nodes(c, a.r, r, kVC));
+      LGH_PASS(order_scatter_nodes(c, a.d, d, kVC));
+      LGH_PASS(order_scatter_nodes(c, a.x, x, kVC));
       LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
       return LGH_OK;
    }

@@ -967,7 +967,7 @@ template <int D, int Q, int HY, int NEB> static void launch_vcg_plane_ho(lgh_ctx
 
 template <int D, int Q> static void launch_vcg_apply(lgh_ctx *c, const VcgArgs &a)
 {
-   constexpr int NEB = (256 / (Q * Q)) > 0 ? (256 / (Q * Q)) : 1;
+   constexpr int NEB = zones_per_wg(Q);
    const int nbatch = ceil_div(c->NE, NEB);
    const int grid = vcg_resident_grid(c, vcg_apply_3d<D, Q, NEB>, Q * Q * NEB, nbatch);
    hipLaunchKernelGGL((vcg_apply_3d<D, Q, NEB>), dim3(grid), dim3(Q * Q * NEB), 0, c->stream, a, nbatch);
@@ -977,7 +977,13 @@ template <int D, int NEB> static void launch_vcg_kron(lgh_ctx *c, const VcgArgs 
 
 bool vcg_available(const lgh_ctx *c)
 {
-   return c->dim == 3 && (c->kid == 0x322 || c->kid == 0x334 || c->kid == 0x346 || c->kid == 0x358 || c->kid == 0x36A);
+   return c->dim == 3 && order_supported(c->kid);
+}
+
+// f(IC<D>, IC<Q>) for the order of a context that has the lockstep solve (vcg_available)
+template <class F> static VcgK1 visit_k1(const lgh_ctx *c, F &&f)
+{
+   return order_row(c->kid, [&](auto Dc, auto Qc, auto) { return f(Dc, Qc); }, [] { return VcgK1{kK1None, nullptr}; });
 }
 
 // The form of K1 and its launcher.  LGH_VCG_VARIANT (sw.vcg_variant): 0 = (qx,qy)-column K1, otherwise the plane-per-thread
@@ -1003,37 +1009,26 @@ VcgK1 vcg_resolve_k1(lgh_ctx *c)
          //  in a CU's LDS - instead of eight / four (two workgroups per CU): 433 -> 345 us per launch at config 5, Q4Q3 steps
          //  - 2 %, profiles/r6_kron_neb.txt; LGH_KRON_NEB=0: eight / four)
          const bool kron_small = c->sw.kron_neb != 0;
-         switch (c->D1D)
-         {
-            case 2: return {kK1Kron, launch_vcg_kron<2, 64>};
-            case 3: return {kK1Kron, launch_vcg_kron<3, 32>};
-            case 4: return {kK1Kron, launch_vcg_kron<4, 16>};
-            case 5: return {kK1Kron, kron_small ? launch_vcg_kron<5, 3> : launch_vcg_kron<5, 8>};
-            default: return {kK1Kron, kron_small ? launch_vcg_kron<6, 2> : launch_vcg_kron<6, 4>};
-         }
+         return visit_k1(c, [&](auto Dc, auto) -> VcgK1 {
+            constexpr int D = Dc, NEB = 256 >> D, SMALL = (D == 5) ? 3 : (D == 6) ? 2 : NEB; // zones per workgroup: 64, 32, 16, 8 or 3, 4 or 2
+            return {kK1Kron, kron_small ? launch_vcg_kron<D, SMALL> : launch_vcg_kron<D, NEB>};
+         });
       }
    }
-   const bool high = c->kid == 0x358 || c->kid == 0x36A;
-   if (v == 0 || (high && !c->b_h1_sym)) // (the plane form for D1D >= 5 uses half a table)
+   if (v == 0 || (c->D1D >= 5 && !c->b_h1_sym)) // (the plane form for D1D >= 5 uses half a table)
    {
-      switch (c->kid)
-      {
-         case 0x322: return {kK1Column, launch_vcg_apply<2, 2>};
-         case 0x334: return {kK1Column, launch_vcg_apply<3, 4>};
-         case 0x346: return {kK1Column, launch_vcg_apply<4, 6>};
-         case 0x358: return {kK1Column, launch_vcg_apply<5, 8>};
-         default: return {kK1Column, launch_vcg_apply<6, 10>};
-      }
+      return visit_k1(c, [](auto Dc, auto Qc) -> VcgK1 {
+         constexpr int D = Dc, Q = Qc;
+         return {kK1Column, launch_vcg_apply<D, Q>};
+      });
    }
-   switch (c->kid)
-   {
-      case 0x322: return {kK1Plane, launch_vcg_plane<2, 2>};
-      case 0x334: return {kK1Plane, launch_vcg_plane<3, 4>};
-      case 0x346: return {kK1Plane, launch_vcg_plane<4, 6>};
+   return visit_k1(c, [&](auto Dc, auto Qc) -> VcgK1 {
+      constexpr int D = Dc, Q = Qc;
       // LGH_VCG_VARIANT=1: the two-lanes-per-plane split at Q1D = 8 as well (A/B, tests)
-      case 0x358: return {kK1Plane, v == 1 ? launch_vcg_plane_ho<5, 8, 2, 5> : launch_vcg_plane_ho<5, 8, 1, 5>};
-      default: return {kK1Plane, launch_vcg_plane_ho<6, 10, 2, 4>};
-   }
+      if constexpr (D == 5) { return {kK1Plane, v == 1 ? launch_vcg_plane_ho<D, Q, 2, 5> : launch_vcg_plane_ho<D, Q, 1, 5>}; }
+      else if constexpr (D == 6) { return {kK1Plane, launch_vcg_plane_ho<D, Q, 2, 4>}; }
+      else { return {kK1Plane, launch_vcg_plane<D, Q>}; }
+   });
 }
 int vcg_k1_form(lgh_ctx *c) { return vcg_resolve_k1(c).form; }
 

@@ -172,7 +172,7 @@ int make_essbits(lgh_ctx *c, DevPtr<uint8_t> &out)
 static int vcg_build_merged_tables(lgh_ctx *c, VcgAux *x)
 {
    SlabLayout L;
-   LGH_VCG_TRY(slab_merge_layout(c, x, L));
+   LGH_PASS(slab_merge_layout(c, x, L));
    const size_t N = (size_t)c->N;
    const int deg = c->t_deg;
    std::vector<int> ell((size_t)deg * N), ellm((size_t)8 * N, -1), val(N, 0);
@@ -192,9 +192,9 @@ static int vcg_build_merged_tables(lgh_ctx *c, VcgAux *x)
       degm = std::max(degm, cnt);
    }
    x->degm = degm;
-   LGH_VCG_TRY(x->settab.upload(L.settab.data(), L.settab.size()));
-   LGH_VCG_TRY(x->ellm.upload(ellm.data(), ellm.size()));
-   LGH_VCG_TRY(make_ellz(c, x->ellzm, x->ellm, 8));
+   LGH_PASS(x->settab.upload(L.settab.data(), L.settab.size()));
+   LGH_PASS(x->ellm.upload(ellm.data(), ellm.size()));
+   LGH_PASS(make_ellz(c, x->ellzm, x->ellm, 8));
    return partition_nodes_by_cost(c, x->grid2, x->nstartm, &val);
 }
 
@@ -221,7 +221,7 @@ static int vcg_build_internal_tables(lgh_ctx *c, VcgAux *x)
       const size_t e = (size_t)o->zorder[i];
       for (size_t d = 0; d < ND; d++) { om[i * ND + d] = o->nnum[hm[e * ND + d]]; }
    }
-   LGH_VCG_TRY(x->o_map.upload(om.data(), nmap));
+   LGH_PASS(x->o_map.upload(om.data(), nmap));
    // transpose, ascending E-position per node (as lgh_create builds the caller's)
    std::vector<int> off(N + 1, 0);
    for (size_t i = 0; i < nmap; i++) { off[(size_t)om[i] + 1]++; }
@@ -235,26 +235,26 @@ static int vcg_build_internal_tables(lgh_ctx *c, VcgAux *x)
       if (k >= deg) { set_error("vcg_build_internal_tables: valence above the mesh's"); return LGH_ERR_ARG; }
       ell[(size_t)k * N + n] = (int)i;
    }
-   LGH_VCG_TRY(x->o_ell.upload(ell.data(), ell.size()));
+   LGH_PASS(x->o_ell.upload(ell.data(), ell.size()));
    // the caller's transpose, rows taken in internal node order: positions in an E-vector of the CALLER's zone order, in the
    // caller's (ascending) order of contributions - the right-hand side has the bits of the unfused E -> L sum
    std::vector<int> tell((size_t)deg * N);
    LGH_HIP_CHECK(hipMemcpy(tell.data(), c->t_ell, tell.size() * sizeof(int), hipMemcpyDeviceToHost));
    for (int k = 0; k < deg; k++)
       for (size_t m = 0; m < N; m++) { ell[(size_t)k * N + m] = tell[(size_t)k * N + (size_t)o->ncaller[m]]; }
-   LGH_VCG_TRY(x->o_ellc.upload(ell.data(), ell.size()));
+   LGH_PASS(x->o_ellc.upload(ell.data(), ell.size()));
    for (int k = 0; k < kVC; k++)
    {
       if (!c->essmask[k]) { continue; }
-      LGH_VCG_TRY(x->o_ess[k].alloc(N));
-      LGH_VCG_TRY(order_gather_bytes(c, c->essmask[k], x->o_ess[k]));
+      LGH_PASS(x->o_ess[k].alloc(N));
+      LGH_PASS(order_gather_bytes(c, c->essmask[k], x->o_ess[k]));
    }
    if (c->multi != 0)
    {
       if (c->owner)
       {
-         LGH_VCG_TRY(x->o_owner.alloc(N));
-         LGH_VCG_TRY(order_gather_nodes(c, c->owner, x->o_owner, 1));
+         LGH_PASS(x->o_owner.alloc(N));
+         LGH_PASS(order_gather_nodes(c, c->owner, x->o_owner, 1));
       }
       const uint8_t *hmask = nullptr;
       const int *sh_node = nullptr, *nodes = nullptr;
@@ -262,8 +262,8 @@ static int vcg_build_internal_tables(lgh_ctx *c, VcgAux *x)
       comm_shared_nodes(c, &hmask, &sh_node, &n_shared);
       if (hmask)
       {
-         LGH_VCG_TRY(x->o_hmask.alloc(N));
-         LGH_VCG_TRY(order_gather_bytes(c, hmask, x->o_hmask));
+         LGH_PASS(x->o_hmask.alloc(N));
+         LGH_PASS(order_gather_bytes(c, hmask, x->o_hmask));
       }
       comm_node_lists(c, &nodes, &total, &sh_node, &n_shared);
       auto translate = [&](const int *src, const int n, DevPtr<int> &dst) -> int {
@@ -274,14 +274,14 @@ static int vcg_build_internal_tables(lgh_ctx *c, VcgAux *x)
       };
       if (nodes && sh_node)
       {
-         LGH_VCG_TRY(translate(nodes, total, x->o_nodes));
-         LGH_VCG_TRY(translate(sh_node, n_shared, x->o_shnode));
+         LGH_PASS(translate(nodes, total, x->o_nodes));
+         LGH_PASS(translate(sh_node, n_shared, x->o_shnode));
          x->o_alias = {x->o_nodes, x->o_shnode};
       }
    }
-   LGH_VCG_TRY(x->o_dinv.alloc(N));
-   LGH_VCG_TRY(x->o_Se.alloc(NE));
-   LGH_VCG_TRY(x->o_x.alloc(kVC * N, true));
+   LGH_PASS(x->o_dinv.alloc(N));
+   LGH_PASS(x->o_Se.alloc(NE));
+   LGH_PASS(x->o_x.alloc(kVC * N, true));
    LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
    x->o_mass_gen = ~0ul;
    return LGH_OK;
@@ -296,12 +296,12 @@ int vcg_build_aux(lgh_ctx *c)
    VcgAux *x = owner.get();
    // the CG's own E-vector (the force E-vector of the fused init stays in c->YE) and the tables of K2
    const size_t ye_n = (size_t)kVC * ((size_t)c->NE * c->ND + kYePad);
-   LGH_VCG_TRY(x->ye.alloc(ye_n, true));
+   LGH_PASS(x->ye.alloc(ye_n, true));
    // The library's own order of zones and nodes (lgh_order.hip), when the caller's is another one: the solve's tables are
    // built for THAT order.  (Several ranks: the exchange tables of lgh_comm.hip are in the caller's numbering - see
    // vcg_order_for.)
    x->ord = vcg_order_for(c);
-   if (x->ord) { LGH_VCG_TRY(vcg_build_internal_tables(c, x)); }
+   if (x->ord) { LGH_PASS(vcg_build_internal_tables(c, x)); }
    const int *v_map = x->o_map ? x->o_map : c->h1map;
    if (c->t_deg <= 8 && (size_t)c->N * 8 * kVC < 0xffffffffull && ((size_t)c->NE * c->ND + kYePad) * 8 < 0xffffffffull)
    {
@@ -312,24 +312,24 @@ int vcg_build_aux(lgh_ctx *c)
       if (c->sw.k2_grid > 0) { x->grid2 = c->sw.k2_grid * ncu; }
       else { x->grid2 = (int)std::max<long>(4L * ncu, (((long)c->N + 1023) / 1024 + 7) & ~7L); }
       x->grid2 = std::min<long>(x->grid2, (long)c->vcg_stride - (long)kShards); // (one partial per workgroup in a reduction slot)
-      LGH_VCG_TRY(make_ellz(c, x->ellz, x->o_ell, x->o_ell ? c->t_deg : 0));
-      LGH_VCG_TRY(make_essbits(c, x->essbits));
+      LGH_PASS(make_ellz(c, x->ellz, x->o_ell, x->o_ell ? c->t_deg : 0));
+      LGH_PASS(make_essbits(c, x->essbits));
       if (x->ord)
       {
          // (the flag bytes were built from the caller's masks: into the internal numbering)
          DevPtr<uint8_t> tmp;
-         LGH_VCG_TRY(tmp.alloc((size_t)c->N));
+         LGH_PASS(tmp.alloc((size_t)c->N));
          LGH_HIP_CHECK(hipStreamSynchronize(nullptr));
-         LGH_VCG_TRY(order_gather_bytes(c, x->essbits, tmp));
+         LGH_PASS(order_gather_bytes(c, x->essbits, tmp));
          LGH_HIP_CHECK(hipStreamSynchronize(c->stream));
          x->essbits = std::move(tmp);
       }
-      LGH_VCG_TRY(partition_nodes_by_cost(c, x->grid2, x->nstart, x->ord ? &x->o_valence : nullptr));
+      LGH_PASS(partition_nodes_by_cost(c, x->grid2, x->nstart, x->ord ? &x->o_valence : nullptr));
       if ((size_t)kVC * (c->NE + 1) * c->ND * 8 < 0xffffffffull)
       {
          // (the FORCE E-vector is in the caller's zone order: o_ellc)
          const size_t ell_n = (size_t)8 * c->N;
-         LGH_VCG_TRY(x->ellf.alloc(ell_n));
+         LGH_PASS(x->ellf.alloc(ell_n));
          hipLaunchKernelGGL(vcg_ellf_k, dim3((unsigned)((ell_n + 255) / 256)), dim3(256), 0, nullptr, x->o_ellc ? x->o_ellc : c->t_ell, x->ellf,
                             (size_t)c->t_deg * c->N, ell_n, c->ND, c->NE);
          LGH_HIP_CHECK(hipGetLastError());
@@ -338,7 +338,7 @@ int vcg_build_aux(lgh_ctx *c)
    if (vcg_resolve_k1(c).form == kK1Slab) // what the slab form reads: whoever dispatches it (vcg_resolve_k1) finds it here
    {
       const size_t nm = (size_t)c->NE * c->ND;
-      LGH_VCG_TRY(x->mapb.alloc(nm));
+      LGH_PASS(x->mapb.alloc(nm));
       hipLaunchKernelGGL(vcg_mapb_k, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, nullptr, v_map, x->mapb, nm);
       LGH_HIP_CHECK(hipGetLastError());
       int *flag = (int *)c->scal.p, h = 1;
@@ -346,10 +346,10 @@ int vcg_build_aux(lgh_ctx *c)
       hipLaunchKernelGGL(vcg_map_xrows_k, dim3((unsigned)((nm / c->D1D + 255) / 256)), dim3(256), 0, nullptr, v_map, nm / c->D1D, c->D1D, flag);
       LGH_HIP_CHECK(hipMemcpy(&h, flag, sizeof(int), hipMemcpyDeviceToHost));
       x->map_xrows = (h == 0) ? 1 : 0;
-      LGH_VCG_TRY(x->limbs.alloc(2 * kLimbWords + 8 * 16 + 32 * 4096, true)); // accumulators, set counters, queue
-      LGH_VCG_TRY(x->rzl.alloc(3 * kLimbWords, true));
+      LGH_PASS(x->limbs.alloc(2 * kLimbWords + 8 * 16 + 32 * 4096, true)); // accumulators, set counters, queue
+      LGH_PASS(x->rzl.alloc(3 * kLimbWords, true));
       // (LGH_SLAB_MERGE=0, A/B: element-local E-vector for every set, the layout of rounds 3 and 4)
-      if (x->ellz && c->sw.slab_merge) { LGH_VCG_TRY(vcg_build_merged_tables(c, x)); }
+      if (x->ellz && c->sw.slab_merge) { LGH_PASS(vcg_build_merged_tables(c, x)); }
    }
    LGH_HIP_CHECK(hipStreamSynchronize(nullptr)); // the fills run asynchronously on the null stream
    c->vcg_aux = std::move(owner);

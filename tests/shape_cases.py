@@ -15,9 +15,9 @@ The kernels group zones by constants such grids never stress.  Read off the disp
   Kronecker K1      64, 32, 16 zones at D1D = 2, 3, 4; 3 (LGH_KRON_NEB=0: 8) at D1D = 5; 2 (4) at D1D = 6
                                                           lgh_vcg_k1.hip::vcg_resolve_k1
   L2 Kronecker      256, 128, 64, 32 zones at L1D = 1 ... 4; 10 (LGH_L2_NEB=0: 16) at L1D = 5
-                                                          lgh_mass.hip::launch_mass (LGH_L2K)
+                                                          lgh_mass.hip::launch_l2_kron
   mass column forms, force kernels, 2D point form of the quadrature update
-                    256 / Q^2 zones                       lgh_mass.hip::neb_for, lgh_force.hip::neb3, lgh_qpoint.hpp (NEB_)
+                    256 / Q^2 zones                       lgh_common.hpp::zones_per_wg
   K2                node ranges over max(4 CUs, N / 1024 rounded up to 8) workgroups (LGH_K2_GRID=<n>: n per CU), every
                     second launch with the update of x        lgh_vcg.hip (grid2), vcg_launch_k2p
 

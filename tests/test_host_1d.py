@@ -106,6 +106,48 @@ def test_lgh_create_accepts_dim1():
     assert b"Unknown kernel 0x135" in L.lgh_last_error()
 
 
+def test_kernel_id_table():
+    """The table of orders (visit_order / order_supported, lgh_common.hpp): of all (dim, D1D, Q1D) with dim 1..3, D1D 1..8,
+    Q1D 1..12 and L1D = D1D - 1, lgh_create refuses exactly those off the fifteen ids - five orders in three dimensions -
+    as LGH_ERR_UNSUPPORTED with 'Unknown kernel 0x<id>'.  It checks the id before it looks for a device and before cfl, so
+    with cfl = 0 the fifteen fail further on: at the device check without a GPU, at the cfl argument with one."""
+    from laghos_amd import _lib
+    L = _lib.load()
+    LGH_ERR_UNSUPPORTED = 2  # (include/laghos_hip.h)
+    orders = {(2, 2), (3, 4), (4, 6), (5, 8), (6, 10)}
+    h1 = np.zeros(4096, np.int32)
+    ones = np.ones(4096)
+    cfg = _lib.LghConfig()
+    ip, dp = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)
+    cfg.h1_map = h1.ctypes.data_as(ip)
+    for f in ("B_h1", "G_h1", "B_l2", "weights", "gamma"):
+        setattr(cfg, f, ones.ctypes.data_as(dp))
+    cfg.NE, cfg.N, cfg.cfl = 1, 1, 0.0
+    h = ctypes.c_void_p()
+    known = 0
+    for dim in (1, 2, 3):
+        for D in range(1, 9):
+            for Q in range(1, 13):
+                cfg.dim, cfg.D1D, cfg.Q1D, cfg.L1D = dim, D, Q, D - 1
+                kid = (dim << 8) | (D << 4) | Q
+                rc = L.lgh_create(ctypes.byref(cfg), ctypes.byref(h))
+                err = L.lgh_last_error()
+                assert rc != 0, hex(kid)
+                if (D, Q) in orders:
+                    known += 1
+                    assert rc != LGH_ERR_UNSUPPORTED and b"Unknown kernel" not in err, (hex(kid), rc, err)
+                else:
+                    assert rc == LGH_ERR_UNSUPPORTED and err == b"Unknown kernel 0x%x" % kid, (hex(kid), rc, err)
+    assert known == 15
+    # sizes that do not fit their four bits would alias one of the fifteen ids: refused as well, by the id they pack to
+    for dim, D, Q, kid in ((1, 18, 2, 0x122), (2, 18, 2, 0x322), (2, 2, 34, 0x222), (3, 3, 20, 0x334)):
+        assert ((dim << 8) | (D << 4) | Q) == kid
+        cfg.dim, cfg.D1D, cfg.Q1D, cfg.L1D = dim, D, Q, D - 1
+        rc = L.lgh_create(ctypes.byref(cfg), ctypes.byref(h))
+        err = L.lgh_last_error()
+        assert rc == LGH_ERR_UNSUPPORTED and err == b"Unknown kernel 0x%x" % kid, (dim, D, Q, rc, err)
+
+
 def test_driver_switches_pa_to_fa_in_1d():
     """-pa (the default) in 1D prints the reference's switch message; -fa stays refused in 2D with the same words."""
     p = subprocess.run([EXE, "-p", "2", "-m", "data/segment01.mesh", "-rs", "1", "-ms", "1", "-pa"], capture_output=True,
